@@ -9,7 +9,7 @@ programs on the device, one scoring launch, count table in HBM — and, with mor
 (sum, int64) of the count table.  A *motif-site* = one (candidate x reference bp x strand) match test: a candidate on a
 bin of L bp is 2·L sites.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a torch.distributed.run child,
 before this process touches the GPU); under torchrun it is one of the ranks.  Multi-GPU is STRONG scaling on the
@@ -21,10 +21,13 @@ the candidates of the bins it holds and the int64[n_candidates, 2] count tables 
 the default run only as the ``weak_scaling`` key, never as ``value``.
 
 Inputs are generated on the device (nanomotif_amd/synth_device.py, bit-identical to the numpy generator) and are
-resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  Extra keys of the default run:
-``roofline_hbm_bound_round`` (one greedy lock-step round, the HBM-bound regime), ``e2e`` (the whole motif_discovery
-pipeline on the same metagenome, generation excluded), ``cfg5_all`` (every candidate against every bin),
-``cpu_baseline`` (the oracle on all host cores and on one), ``per_rank`` (kernel / host / all-reduce times).
+resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K
+steps of the headline pass and prints the line (with the N = 1 checksum of its last table when the configuration's is
+known).  ``--full`` adds every other measurement and check: ``roofline_hbm_bound_round`` (one greedy lock-step round,
+the HBM-bound regime), ``e2e`` (the whole motif_discovery pipeline on the same metagenome, generation excluded),
+``cfg5_all`` (every candidate against every bin), ``cpu_baseline`` (the oracle on all host cores and on
+one, with parity), the other scoring-lanes pass, the all-reduce alone and the re-verification of sharded counts.
+``--dump-outputs DIR`` writes the count table of the last timed step as ``DIR/counts.npy`` (float64).
 """
 from __future__ import annotations
 
@@ -287,6 +290,22 @@ def load_traffic(workload, total_bp, n_cand):
 def checksum(table):
     return [int(table[:, 0].sum()), int(table[:, 1].sum()),
             int((table * np.arange(1, table.size + 1).reshape(table.shape) % 1000003).sum() % (2**61 - 1))]
+
+
+DUMP_MAX_ROWS = 1 << 20          # per array: 16 MB of float64 for a [rows, 2] table, + 8 MB of row indices when sampled
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float64 (the int64 counts are far below 2**53: exact).  An array
+    of more than DUMP_MAX_ROWS rows is replaced by a fixed seeded sample of its rows, their indices in <name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if len(a) > DUMP_MAX_ROWS:
+            rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(len(a), size=DUMP_MAX_ROWS, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
 
 
 def run_e2e(mg, eng_device, device, my_bins=None, lanes=1):
@@ -575,7 +594,7 @@ def main():
                          "each (e2e_synth.run_lanes).  Measured in round 6 (profiles/r6/e2e/lanes.jsonl): two lanes 62-72 ms against 70-79 of one, "
                          "three and more slower than one; same rows.  Not the default: the gain is within the box's noise")
     ap.add_argument("--per-group", type=int, default=2, help="greedy workload: children per (bin, mod type)")
-    ap.add_argument("--cpu-bins", type=int, default=-1, help="bins in the CPU-baseline sample (-1: two per worker, at most all; 0: skip)")
+    ap.add_argument("--cpu-bins", type=int, default=-1, help="--full: bins in the CPU-baseline sample (-1: two per worker, at most all; 0: skip)")
     ap.add_argument("--cpu-procs", type=int, default=0, help="CPU-baseline worker processes (0: os.cpu_count())")
     ap.add_argument("--cpu-t1-bins", type=int, default=3, help="bins scored by the single-core (-t 1) CPU leg")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (debug: several ranks on one GPU)")
@@ -584,8 +603,8 @@ def main():
     ap.add_argument("--force-device", type=int, default=-1, help="debug: CUDA device for every rank")
     ap.add_argument("--cooldown", type=float, default=0.0, help="seconds of idle GPU before the warmup steps")
     ap.add_argument("--force-allreduce", action="store_true", help="debug: run the C-ABI all-reduce step even with one rank (RCCL world of 1)")
-    ap.add_argument("--hbm-round-steps", type=int, default=20, help="extra launches of a greedy round for the HBM-bound roofline (0: skip)")
-    ap.add_argument("--extras", default="auto", help="comma list of extra measurements of the cfg5 run: e2e,cfg5_all,weak,two_lanes,files (auto: those that apply; none; files = BASELINE cfg 3 from FASTA + .bed.gz + .tbi through one cold CLI process, N = 1 only), the opt-in cli (cfg 3 as FILES, plain and bgzip: writes ~9 GB to a tmpfs, four CLI processes) and the opt-in cli1g (the CLI at 1 Gbp from FASTA + .bed.gz + .tbi: ~16 GB on a tmpfs, minutes of writing)")
+    ap.add_argument("--hbm-round-steps", type=int, default=20, help="--full: extra launches of a greedy round for the HBM-bound roofline (0: skip)")
+    ap.add_argument("--extras", default="auto", help="--full: comma list of extra measurements of the cfg5 run: e2e,cfg5_all,weak,two_lanes,files (auto: those that apply; none; files = BASELINE cfg 3 from FASTA + .bed.gz + .tbi through one cold CLI process, N = 1 only), the opt-in cli (cfg 3 as FILES, plain and bgzip: writes ~9 GB to a tmpfs, four CLI processes) and the opt-in cli1g (the CLI at 1 Gbp from FASTA + .bed.gz + .tbi: ~16 GB on a tmpfs, minutes of writing)")
     ap.add_argument("--cli-bp", type=int, default=100_000_000, help="size of the file-to-bin-motifs.tsv extra (cfg 3: 100 Mbp = 7.8 GB of bedMethyl text)")
     ap.add_argument("--cli1g-bp", type=int, default=1_000_000_000, help="size of the opt-in cli1g extra (the CLI on FASTA + .bed.gz + .tbi at the headline size; "
                     "falls back to the largest size the tmpfs / cgroup holds and says which)")
@@ -603,6 +622,12 @@ def main():
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="N > 1: strong = ONE metagenome, contigs sharded, count tables all-reduced every step (default, the BASELINE "
                          "configuration); weak = every rank its own --total-bp metagenome, no collective")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the --extras, the CPU baseline and its parity, the HBM-bound round, the other scoring-lanes "
+                         "pass, the all-reduce alone and the re-verification of sharded counts.  Without it a run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64): counts.npy = its int64[candidates, 2] "
+                         "count table (n_mod, n_nomod per candidate); --workload e2e: motif_rows.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -674,7 +699,7 @@ def main():
     else:
         mine = assign_contigs(mg.lengths, world, bins=mg.bin_names)[rank]
     extras = {"e2e", "cfg5_all", "weak", "two_lanes", "files"} if args.extras == "auto" else set(x for x in args.extras.split(",") if x and x != "none")
-    if args.workload != "cfg5" or weak:
+    if args.workload != "cfg5" or weak or not args.full:
         extras = set()
     if world == 1:
         extras.discard("weak")
@@ -693,6 +718,11 @@ def main():
             dist.barrier()
         lanes = args.e2e_lanes if world == 1 else 1
         rows, t = run_e2e(mg, local_rank, device, my_bins, lanes=lanes)
+        if args.dump_outputs and rank == 0:
+            # the motif rows (of rank 0's bins), in the order bin-motifs.tsv is written: mod_position, n_mod, n_nomod, score
+            srt = sorted(rows, key=lambda r: (r.reference, r.mod_type, r.motif))
+            dump_outputs(args.dump_outputs, {"motif_rows": np.array([[r.mod_position, r.n_mod, r.n_nomod, r.score] for r in srt],
+                                                                    dtype=np.float64).reshape(-1, 4)})
         pipeline = t["wall_s"] if lanes > 1 else t["upload_filter_s"] + t["search_s"]
         planted = {(b, m[0]) for b, ms in mg.bin_motifs.items() if my_bins is None or b in set(my_bins) for m in ms}
         found = {(r.reference, r.motif_iupac) for r in rows}
@@ -897,23 +927,28 @@ def main():
     for _ in range(args.prewarm):
         step()
     drain()
-    strict = timed_region(1)
+    # a plain run times the headline pass only; --full times the strict-order pass too when two lanes are the headline
+    # (it gives the roofline's kernel duration and checks the two-lane counts)
+    strict = timed_region(1) if (want == 1 or args.full) else None
     piped = timed_region(2) if (lanes_ok and args.lanes != 1 and (want == 2 or "two_lanes" in extras or args.lanes == 2)) else None
-    lanes_agree = None if piped is None else bool(np.array_equal(strict["table"], piped["table"]))
+    lanes_agree = None if (piped is None or strict is None) else bool(np.array_equal(strict["table"], piped["table"]))
     if lanes_agree is False:
         log("COUNT MISMATCH between the strict-order and the two-lane pass: the strict-order pass is the headline")
-    head = piped if (want == 2 and piped and lanes_agree) else strict
+    head = piped if (want == 2 and piped and lanes_agree is not False) else strict
     elapsed, elapsed_local = head["elapsed"], head["elapsed_local"]
-    kernel_ms, kernel_ms_local = strict["kernel_ms"], strict["kernel_ms_local"]
+    kernel_ms, kernel_ms_local = (strict["kernel_ms"], strict["kernel_ms_local"]) if strict else (None, None)
     host_s[0] = head["host_ms"] * args.steps * 1e-3
     final = head["table"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"counts": final})
 
     # ---- the line proves its own counts (untimed).  (1) independent sum: every rank scores its shard once more in strict
     # order into a fresh table, the tables travel by all_gather (torch.distributed, not the C ABI's communicator) and are
     # summed on the host; (2) rank 0 loads ALL contigs of a few sampled bins into a second engine — the single-shard, N = 1
     # computation of those bins — and compares their rows; (3) the N = 1 checksum of this configuration, when it is known.
+    # (1) and (2) take launches of their own: --full only.
     verification = {"lanes_agree": lanes_agree}
-    if reduce_counts:
+    if reduce_counts and args.full:
         loc = torch.zeros((n_cand, 2), dtype=torch.int64, device=device)
         eng.score_into_device(batch, loc.data_ptr())
         eng.sync()
@@ -947,7 +982,7 @@ def main():
 
     # the collective alone: K all-reduces of the table back to back, slowest rank
     allreduce_ms, allreduce_ms_local = None, None
-    if coll:
+    if coll and args.full:
         torch.cuda.synchronize(device)
         if world > 1:
             dist.barrier()
@@ -961,15 +996,15 @@ def main():
         allreduce_ms = allmax([allreduce_ms_local])[0]
         # (the tables are multiples of the counts now: `final` and the verification tables were read before)
     info = eng.comm_info() if (coll and coll.kind == "native") else {"world": 0, "rank": -1, "device": -1, "rccl_version": 0}
-    per_rank = gather([elapsed_local / args.steps * 1e3, kernel_ms_local, host_s[0] / args.steps * 1e3, float(len(mine)),
-                       float(sum(my_bin_bp.values())), algo_bytes_rank, allreduce_ms_local if coll else -1.0,
+    per_rank = gather([elapsed_local / args.steps * 1e3, kernel_ms_local if strict else -1.0, host_s[0] / args.steps * 1e3, float(len(mine)),
+                       float(sum(my_bin_bp.values())), algo_bytes_rank, allreduce_ms_local if allreduce_ms_local is not None else -1.0,
                        float(info["world"]), float(info["rank"]), float(info["device"])])
 
     # ---- the same engine in its HBM-bound regime: one lock-step greedy round (2 sibling children per (bin, mod type),
     # the shape MotifSearcher.run submits), kernel time from HIP events; reported next to the main roofline
     hbm_round = None
     try:
-        if args.workload == "cfg5" and args.hbm_round_steps > 0:
+        if args.workload == "cfg5" and args.hbm_round_steps > 0 and args.full:
             g_cands = build_candidates(mg, "greedy", 0, 2)
             g_batch = eng.make_batch(g_cands)
             g_counts = torch.zeros((len(g_cands), 2), dtype=torch.int64, device=device)
@@ -1012,7 +1047,7 @@ def main():
     if rank == 0:
         nw = world if weak else 1
         value = sites_per_step * nw * args.steps / elapsed
-        achieved = algo_bytes_rank / (kernel_ms * 1e-3) / 1e9
+        achieved = algo_bytes_rank / (kernel_ms * 1e-3) / 1e9 if strict else 0.0
         if weak:
             workload = (f"{args.workload} (weak scaling): {world} x ({n_cand} candidate motifs x {args.total_bp:,} bp metagenome, {args.contigs} contigs, "
                         f"{args.bins} bins, 6mA+5mC), both strands, no collective")
@@ -1046,7 +1081,7 @@ def main():
                          "algorithmic_bytes_per_launch": algo_bytes_rank,
                          "note": "0.5 B/bp per (bin, mod type) step + 16 B per candidate; slowest rank at N>1"},
             # of the strict-order pass (with two lanes consecutive launches overlap: a step is then SHORTER than one launch)
-            "kernel_share_of_step": kernel_ms / (strict["elapsed"] / args.steps * 1e3),
+            "kernel_share_of_step": kernel_ms / (strict["elapsed"] / args.steps * 1e3) if strict else None,
             "per_rank": [dict(zip(["ms_per_step", "kernel_ms", "host_call_ms_per_step", "contigs", "bp", "algorithmic_bytes", "allreduce_ms",
                                    "rccl_world", "rccl_rank", "rccl_device"], p)) for p in per_rank],
             "allreduce_ms": allreduce_ms,
@@ -1057,6 +1092,9 @@ def main():
             "counts_checksum": checksum(final),
             "verification": verification,
         }
+        if strict is None:
+            # two lanes are the headline and the strict-order pass (the kernel's own duration) is --full's: no roofline
+            del result["roofline"], result["kernel_share_of_step"]
         if coll:
             # what the communicator reports about itself (ncclCommCount / ncclCommUserRank through nm_comm_info), every rank
             worlds = sorted({int(p[7]) for p in per_rank})
@@ -1076,7 +1114,7 @@ def main():
                 "ms_per_step": other["elapsed"] / args.steps * 1e3, "steps": args.steps, "warmup": args.warmup}
         if hbm_round:
             result["roofline_hbm_bound_round"] = hbm_round
-        if tr and tr.get("sq_insts_valu_per_launch"):
+        if tr and tr.get("sq_insts_valu_per_launch") and strict:
             # second roofline: the kernel is integer-VALU-issue bound once a (bin, mod type) carries more than ~2
             # candidates; instruction count from rocprofv3 (SQ_INSTS_VALU, profiles/), peak from tools/valu_peak.hip
             rate = tr["sq_insts_valu_per_launch"] / (kernel_ms * 1e-3)
@@ -1122,7 +1160,7 @@ def main():
 
     # ---- CPU baseline (rank 0, N = 1 only): the oracle on a bounded sample of the same workload, and parity
     try:
-        if rank == 0 and world == 1 and args.cpu_bins != 0 and cands is not None:
+        if rank == 0 and world == 1 and args.cpu_bins != 0 and cands is not None and args.full:
             cpu_baseline(result, final, cands, mg, spec_kw, args)
     except Exception as exc:                    # an extra must not take the headline line down with it (one rank only:
         if world > 1:                           #  with several ranks a lone survivor would hang in the next collective)

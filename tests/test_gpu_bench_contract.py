@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--total-bp", "20000000", "--contigs", "200",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--total-bp", "20000000", "--contigs", "200",
                         "--bins", "10", "--candidates", "200", "--cpu-bins", "2", "--cpu-procs", "2", "--hbm-round-steps", "2"],
                        cwd=ROOT, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -48,8 +48,36 @@ def test_bench_json_contract():
     assert d["two_lanes"]["steps"] == 3 and d["prewarm_steps"] == 200
 
 
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full: the headline pass alone, --steps of it; --dump-outputs writes the last timed step's count table,
+    the same table on every run of the same arguments."""
+    import numpy as np
+    lines, tables = [], []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--total-bp", "20000000", "--contigs", "200",
+                            "--bins", "10", "--candidates", "200", "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        got = [l for l in r.stdout.strip().split("\n") if l.startswith("{")]
+        assert len(got) == 1
+        lines.append(json.loads(got[0]))
+        assert sorted(os.listdir(out)) == ["counts.npy"]
+        tables.append(np.load(out / "counts.npy"))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "counts_checksum"):
+        assert k in d, k
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(d["config"]["motif_sites_per_step"] / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    for k in ("e2e", "e2e_files", "cfg5_all", "cpu_baseline", "parity", "roofline_hbm_bound_round", "two_lanes", "strict_order"):
+        assert k not in d, k
+    t = tables[0]
+    assert t.dtype == np.float64 and t.shape == (200, 2) and t.sum() > 0
+    assert [int(t[:, 0].sum()), int(t[:, 1].sum())] == d["counts_checksum"][:2]
+    assert np.array_equal(tables[0], tables[1]) and lines[0]["counts_checksum"] == lines[1]["counts_checksum"]
+
+
 def _bench(extra, nproc=1, launcher=True):
-    small = ["--steps", "3", "--warmup", "1", "--total-bp", "20000000", "--contigs", "200", "--bins", "10", "--candidates", "200",
+    small = ["--full", "--steps", "3", "--warmup", "1", "--total-bp", "20000000", "--contigs", "200", "--bins", "10", "--candidates", "200",
              "--cpu-bins", "0", "--hbm-round-steps", "0"]
     if nproc == 1:
         cmd = [sys.executable, "bench.py", "--extras", "none"]

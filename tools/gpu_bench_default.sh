@@ -1,11 +1,12 @@
 #!/bin/bash
-# the default bench line (as the driver runs it), timed
+# the --full bench line (extras included), timed; output under ${OUT_DIR:-runs}/bench_default
 cd ${GRAFT_REPO_ROOT:-.}
-mkdir -p gpurun_out/bench_default
+out=${OUT_DIR:-runs}/bench_default
+mkdir -p $out
 start=$(date +%s.%N)
-timeout 1200 python bench.py > gpurun_out/bench_default/bench.json 2> gpurun_out/bench_default/bench.log
+timeout 1200 python bench.py --full > $out/bench.json 2> $out/bench.log
 echo "bench rc=$? in $(echo "$(date +%s.%N) - $start" | bc) s"
-python3 - gpurun_out/bench_default/bench.json <<'PY'
+python3 - $out/bench.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])
 print({k: d.get(k) for k in ("value", "ms_per_step", "vs_baseline")}, "kernel_ms", d["roofline"].get("kernel_ms"), "frac", d["roofline"].get("frac"))

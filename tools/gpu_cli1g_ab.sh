@@ -1,12 +1,13 @@
 #!/bin/bash
-# the CLI at 1 Gbp from files (bench.py --extras cli1g) with A/B legs given as NM_BENCH_CLI1G_LEGS syntax in $1 (default: the single
-# inflate kernel of rounds 4 - 5 against the two-phase inflate, twice each), one box; log under gpurun_out/$2
+# the CLI at 1 Gbp from files (bench.py --full --extras cli1g) with A/B legs given as NM_BENCH_CLI1G_LEGS syntax in $1 (default: the single
+# inflate kernel of rounds 4 - 5 against the two-phase inflate, twice each), one box; log under ${OUT_DIR:-runs}/$2
 cd ${GRAFT_REPO_ROOT:-.}
 tag=${2:-cli1g_ab}
-mkdir -p gpurun_out/$tag
+out=${OUT_DIR:-runs}/$tag
+mkdir -p $out
 legs=${1:-"v1a:NM_BED_INFLATE_V1=1;NM_BED_TIMING=1,two_a:NM_BED_TIMING=1,v1b:NM_BED_INFLATE_V1=1;NM_BED_TIMING=1,two_b:NM_BED_TIMING=1"}
-NM_BENCH_CLI1G_LEGS="$legs" timeout 2700 python bench.py --extras cli1g --cpu-bins 0 --steps 3 --warmup 1 > gpurun_out/$tag/cli1g.log 2>&1
-echo "cli1g rc=$?"; tail -1 gpurun_out/$tag/cli1g.log > gpurun_out/$tag/line.json; python3 - gpurun_out/$tag/line.json <<'PY'
+NM_BENCH_CLI1G_LEGS="$legs" timeout 2700 python bench.py --full --extras cli1g --cpu-bins 0 --steps 3 --warmup 1 > $out/cli1g.log 2>&1
+echo "cli1g rc=$?"; tail -1 $out/cli1g.log > $out/line.json; python3 - $out/line.json <<'PY'
 import sys, json
 d = json.loads(open(sys.argv[1]).readline()); c = d.get('cli1g', d.get('extra_errors'))
 if isinstance(c, dict) and 'legs' in c:

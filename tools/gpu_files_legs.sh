@@ -1,11 +1,12 @@
 #!/bin/bash
-# the default bench's from-files leg (cfg 3, 100 Mbp) with extra CLI legs ($1: NM_BENCH_CLI1G_LEGS syntax) and every leg's timing lines
+# the --full bench's from-files leg (cfg 3, 100 Mbp) with extra CLI legs ($1: NM_BENCH_CLI1G_LEGS syntax) and every leg's timing lines
 cd ${GRAFT_REPO_ROOT:-.}
 tag=${2:-files_legs}
-mkdir -p gpurun_out/$tag
-NM_BENCH_CLI1G_LEGS="$1" timeout 1200 python bench.py --extras files --steps 3 --warmup 1 > gpurun_out/$tag/line.json 2> gpurun_out/$tag/bench.err
+out=${OUT_DIR:-runs}/$tag
+mkdir -p $out
+NM_BENCH_CLI1G_LEGS="$1" timeout 1200 python bench.py --full --extras files --steps 3 --warmup 1 > $out/line.json 2> $out/bench.err
 echo "rc=$?"
-python3 - gpurun_out/$tag/line.json <<'PY'
+python3 - $out/line.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])
 f = d.get("e2e_files", {})

@@ -2,7 +2,7 @@
 # Strict stream order against two scoring lanes (nm_set_score_lanes): full metagenome and the shard shapes of 2 / 4 / 8 ranks
 # (whole bins per rank, as shard.assign_contigs deals them), with the all-reduce step of the C ABI (RCCL world of 1)
 mkdir -p gpurun_out/lanes
-B="python bench.py --extras two_lanes --cpu-bins 0 --hbm-round-steps 0 --steps 100 --warmup 5"
+B="python bench.py --full --extras two_lanes --cpu-bins 0 --hbm-round-steps 0 --steps 100 --warmup 5"
 for rep in 1 2; do
   $B 2>/dev/null | python tools/bench_brief.py "1Gbp"
   $B --force-allreduce 2>/dev/null | python tools/bench_brief.py "1Gbp+ar"

@@ -27,7 +27,7 @@ note "1. tests/test_gpu_comm.py rc=$rc ($(grep -E 'passed|failed' "$out/test_gpu
 if [ "$n_gpus" -ge 2 ] && grep -q "SKIPPED.*needs at least 2 GPUs" "$out/test_gpu_comm.log"; then note "   the >= 2-GPU test was SKIPPED although $n_gpus GPUs are visible"; fail=1; fi
 
 # ---- 3. (first, it is the reference) N = 1
-timeout 1800 python3 bench.py --gpus 1 --extras e2e > "$out/bench_n1.json" 2> "$out/bench_n1.log" || { note "3. bench N=1 FAILED"; fail=1; }
+timeout 1800 python3 bench.py --gpus 1 --full --extras e2e > "$out/bench_n1.json" 2> "$out/bench_n1.log" || { note "3. bench N=1 FAILED"; fail=1; }
 ref=$(python3 -c "import json,sys; print(json.load(open('$out/bench_n1.json'))['counts_checksum'])" 2>/dev/null)
 note "3. N=1 checksum: $ref"
 
@@ -36,7 +36,7 @@ for n in 2 4 8; do
   [ "$n" -gt "$n_gpus" ] && { note "2. N=$n skipped (only $n_gpus GPUs)"; continue; }
   for lanes in 1 2; do
     f="$out/bench_n${n}_lanes${lanes}"
-    timeout 1800 python3 bench.py --gpus $n --lanes $lanes --extras none > "$f.json" 2> "$f.log"
+    timeout 1800 python3 bench.py --gpus $n --lanes $lanes --full --extras none > "$f.json" 2> "$f.log"
     rc=$?
     line=$(python3 - "$f.json" "$n" <<'PY'
 import json, sys
