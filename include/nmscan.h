@@ -359,6 +359,13 @@ int nm_bin_contigs(nm_ctx *ctx, uint32_t bin, uint32_t *contig_ids, uint32_t cap
 int nm_readstats_upload(nm_ctx *ctx, uint32_t slot, uint64_t n_rows, const uint32_t *contig_id, const uint32_t *position,
                         const uint8_t *strand, const int32_t *n_valid_cov, const int32_t *n_modified, const int32_t *n_diff,
                         int32_t min_valid_read_coverage, double min_valid_cov_to_diff_fraction, int rows_on_device, uint64_t *n_kept);
+typedef struct nm_bedcols nm_bedcols;               /* the device bedMethyl parser's columns (nm_bed_parse_device, below) */
+/* nm_readstats_upload_bedcols: nm_readstats_upload(rows_on_device = 1) of the rows of mod code `mod_id` (the parser's mod ids:
+ *   0 m, 1 a, 2 21839, 3 + k others) straight from the DEVICE columns of nm_bed_parse_device_counts — rows of other codes are
+ *   skipped in place, none is compacted or copied to the host.  nm_bedcols_map_contigs must come first (NM_ESTATE otherwise);
+ *   contigs it mapped to 0xFFFFFFFF are ignored.  Kept set, planes and errors as nm_readstats_upload of the same rows. */
+int nm_readstats_upload_bedcols(nm_ctx *ctx, nm_bedcols *cols, uint32_t slot, int8_t mod_id, int32_t min_valid_read_coverage,
+                                double min_valid_cov_to_diff_fraction, uint64_t *n_kept);
 int nm_contig_methylation(nm_ctx *ctx, uint32_t n_motifs, const uint8_t *motif_slot, const uint8_t *motif_len, const uint8_t *motif_modpos,
                           const uint32_t *motif_mask_offset, const uint8_t *motif_masks, uint32_t *out_n_obs, double *out_mean_cov,
                           double *out_median, double *out_weighted_mean);
@@ -579,7 +586,6 @@ int nm_bed_close(nm_bed *bed);
  *   nm_bedcols_map_contigs     contig column = contig_lut[file contig id] (engine contig id or 0xFFFFFFFF)
  *   nm_bedcols_device_columns  DEVICE pointers; contig_id is valid after nm_bedcols_map_contigs
  */
-typedef struct nm_bedcols nm_bedcols;
 int nm_bed_parse_device(nm_ctx *ctx, const char *path, uint32_t threads, nm_bedcols **out);
 int nm_bed_parse_device_indexed(nm_ctx *ctx, const char *path, const char *tbi_path, uint32_t n_contigs, const char *names,
                                 const uint32_t *name_offset, uint32_t threads, nm_bedcols **out, uint64_t stats[4]);
@@ -591,6 +597,12 @@ int nm_bedcols_map_contigs(nm_bedcols *cols, const uint32_t *contig_lut, uint32_
 int nm_bedcols_device_columns(nm_bedcols *cols, const uint32_t **contig_id, const uint32_t **file_contig_id, const uint32_t **position,
                               const int8_t **mod_type, const uint8_t **strand, const double **fraction_mod, const int32_t **nvalid_cov);
 int nm_bedcols_phase_seconds(nm_bedcols *cols, double out[4]);
+/* nm_bed_parse_device_counts: nm_bed_parse_device (plain text or bgzip) that also keeps N_mod (col 12) and N_diff (col 17) as int32
+ * DEVICE columns — the device twin of nm_bed_open_counts: every row equals it bit for bit, a count that is not an integer in
+ * [0, 0x7FFFFFFF] is refused with its code (NM_EINVAL) and message; NM_EDECLINED where the host reader must decide (a count of more
+ * than 18 digits).  nm_bedcols_count_columns returns those DEVICE pointers; NM_ESTATE for columns parsed without counts. */
+int nm_bed_parse_device_counts(nm_ctx *ctx, const char *path, uint32_t threads, nm_bedcols **out);
+int nm_bedcols_count_columns(nm_bedcols *cols, const int32_t **n_modified, const int32_t **n_diff);
 /* nm_bed_parse_device_indexed in two halves (round 5).  nm_bed_plan_indexed is its HOST-ONLY half — the tabix index read, the wanted
  * contigs' regions, the walk over their BGZF blocks (half a second at 1 Gbp) — with no GPU involved: a caller runs it on a thread
  * while the HIP runtime comes up and the assembly is parsed (python -m nanomotif_amd does; find_motifs_bin.py:382-396 needs the .tbi

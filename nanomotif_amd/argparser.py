@@ -1,6 +1,6 @@
 """Command line of the MI355X build: the ``motif_discovery`` sub-command with the reference's arguments
-(nanomotif/argparser.py:13-136), plus ``--device`` for the GPU to use.  The reference's other sub-commands
-(detect_contamination, include_contigs, MTase-linker) are out of scope."""
+(nanomotif/argparser.py:13-136), plus ``--device`` for the GPU to use, and the binnary sub-commands ``detect_contamination`` and
+``include_contigs`` with the reference's flags (argparser.py:139-236).  MTase-linker is out of scope."""
 import argparse
 
 __version__ = "1.1.2+mi355x.r1"
@@ -12,7 +12,7 @@ def create_parser():
                                      formatter_class=formatter)
     parser.add_argument("--version", action="version", version="%(prog)s {}".format(__version__))
     sub = parser.add_subparsers(help="-- Command descriptions --", dest="command", title="commands",
-                                metavar="{motif_discovery, check_installation}")
+                                metavar="{motif_discovery, detect_contamination, include_contigs, check_installation}")
     p = sub.add_parser("motif_discovery", help="Finds motifs directly on bin level in provided assembly", add_help=False)
     p.add_argument("assembly", type=str, help="path to the assembly file.")
     p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
@@ -49,5 +49,43 @@ def create_parser():
     gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
     gen.add_argument("--seed", type=int, default=1, help="Seed for random number generator. Default: %(default)s")
     gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
+    add_binnary_parsers(sub)
     sub.add_parser("check_installation", help="Run motif_discovery on a small synthetic data set", add_help=True)
     return parser
+
+
+def add_binnary_parsers(sub):
+    """detect_contamination / include_contigs (argparser.py:139-236): flags, defaults and help of the reference."""
+    shared = argparse.ArgumentParser(description="Contamination DNA Methylation Pattern", add_help=False)
+    mandatory = shared.add_argument_group("Mandatory Arguments")
+    mandatory.add_argument("--pileup", type=str, help="Path to pileup.bed", required=True)
+    mandatory.add_argument("--assembly", type=str, help="Path to assembly file [fasta format required]", required=True)
+    mandatory.add_argument("--bin_motifs", type=str, help="Path to bin-motifs.tsv file", required=True)
+    mandatory.add_argument("--contig_bins", type=str, help="Path to bins.tsv file for contig bins", required=True)
+    shared.add_argument("-t", "--threads", type=int, default=1, help="Number of threads to use for multiprocessing")
+    shared.add_argument("--min_valid_read_coverage", type=int, default=3,
+                        help="Minimum read coverage for calculating methylation [used with methylation_util executable]")
+    shared.add_argument("--methylation_threshold", type=int, default=24,
+                        help="Filtering criteria for trusting contig methylation. It is the product of mean_read_coverage and "
+                             "N_motif_observation. Higher value means stricter criteria. [default: 24]")
+    shared.add_argument("--num_consensus", type=int, default=4, help="Number of models that has to agree for classifying as contaminant")
+    shared.add_argument("--force", action="store_true",
+                        help="Force override of motifs-scored-read-methylation.tsv. If not set existing file will be used.")
+    shared.add_argument("--write_bins", action="store_true",
+                        help="If specified, new bins will be written to a bins folder. Requires --assembly_file to be specified.")
+    shared.add_argument("--methylation_output_type", default="median", choices=["median", "weighted_mean"],
+                        help="Specify whether to use the median of mean methylated motif positions or the weighted mean. [default: median]")
+    mandatory.add_argument("--out", type=str, help="Path to output directory", required=True, default="nanomotif")
+    shared.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
+
+    cont = sub.add_parser("detect_contamination", help="Detect contamination in bins", parents=[shared])
+    cont.add_argument("--contamination_file", type=str,
+                      help="Path to an existing contamination file if bins should be outputtet as a post-processing step")
+
+    inc = sub.add_parser("include_contigs", help="Include contigs in bins", parents=[shared])
+    inc.add_argument("--mean_model_confidence", type=float, default=0.8,
+                     help="Mean probability between models for including contig. Contigs above this value will be included. [default: 0.8]")
+    group = inc.add_mutually_exclusive_group(required=False)
+    group.add_argument("--contamination_file", type=str, help="Path to an existing contamination file to include in the analysis")
+    group.add_argument("--run_detect_contamination", action="store_true",
+                       help="Indicate that the detect_contamination workflow should be run first")

@@ -20,6 +20,7 @@ find_motifs_bin.py:1285-1331): thresholded site counts, a different quantity und
 from __future__ import annotations
 
 import ctypes as C
+import logging as log
 import os
 
 import numpy as np
@@ -98,17 +99,110 @@ def methylation_pattern(pileup, assembly, motifs, threads=1, min_valid_read_cove
     """Drop-in for the call at main.py:167-178: ``pileup`` / ``assembly`` are paths (bedMethyl text, gzip or bgzip; FASTA),
     ``motifs`` the motif_mod strings; writes ``output`` (TSV with COLUMNS) when given and returns the rows.  ``batch_size``
     is accepted for signature compatibility (the device batches motifs itself).  Pileup contigs that are not in the
-    assembly are ignored when ``allow_assembly_pileup_mismatch`` (the reference passes True), else an error."""
+    assembly are ignored when ``allow_assembly_pileup_mismatch`` (the reference passes True), else an error.
+
+    Both files are parsed ON THE DEVICE: a plain-text assembly by nm_fasta_parse_device, the pileup (plain text or bgzip) by
+    nm_bed_parse_device_counts, whose columns feed nm_readstats_upload_bedcols once per wanted mod code — no pileup row becomes a
+    host array.  A gzip assembly, a parser that declines its input (NM_EDECLINED) and NANOMOTIF_HOST_PARSER=1 take the host
+    readers (load_fasta, nm_bed_open_counts); both paths give the same rows."""
     from . import fasta
     from .engine import ScanEngine
     lib = _lib.load()
-    asm = fasta.load_fasta(assembly)
-    names = list(asm)
+    host_only = os.environ.get("NANOMOTIF_HOST_PARSER") == "1"
+    nthreads = max(int(threads), 0) if int(threads) > 1 else 0
     eng = ScanEngine(device)
+    try:
+        asm = None
+        if not host_only and not str(assembly).endswith(".gz"):
+            try:
+                asm = fasta.DeviceAssembly(eng, assembly, threads=nthreads)
+            except _lib.NmScanError as e:
+                if e.code != _lib.NM_EDECLINED:
+                    raise
+                log.info(f"assembly: the device parser declined ({e}); using the host parser")
+        if asm is not None:
+            try:
+                names = list(asm)
+                eng.upload_assembly_fasta(asm, names, ["all"] * len(names))
+            finally:
+                asm.close()
+            log.info(f"assembly: {len(names)} records parsed on the device")
+        else:
+            host_asm = fasta.load_fasta(assembly)
+            names = list(host_asm)
+            eng.upload_assembly(names, [host_asm[n] for n in names], ["all"] * len(names))
+            del host_asm
+            log.info(f"assembly: {len(names)} records read on the host")
+        wanted = {parse_motif_mod(m)[1] if isinstance(m, str) else m[1] for m in motifs}
+        local = {c: i for i, c in enumerate(names)}
+        done = False
+        if not host_only:
+            try:
+                _read_statistics_device(eng, lib, pileup, nthreads, local, wanted, allow_assembly_pileup_mismatch,
+                                        min_valid_read_coverage, min_valid_cov_to_diff_fraction)
+                done = True
+                log.info("pileup: read statistics from the device parser's columns")
+            except _lib.NmScanError as e:
+                if e.code != _lib.NM_EDECLINED:
+                    raise
+                log.info(f"pileup: the device parser declined ({e}); using the host parser")
+        if not done:
+            _read_statistics_host(eng, lib, pileup, threads, local, wanted, allow_assembly_pileup_mismatch,
+                                  min_valid_read_coverage, min_valid_cov_to_diff_fraction)
+            log.info("pileup: read statistics from the host parser's rows")
+        rows = read_methylation_table(eng, motifs, output_type)
+    finally:
+        eng.close()
+    if output:
+        write_tsv(rows, output)
+    return rows
+
+
+def _contig_lut(file_names, local, allow_assembly_pileup_mismatch):
+    missing = [c for c in file_names if c not in local]
+    if missing and not allow_assembly_pileup_mismatch:
+        raise ValueError(f"{len(missing)} pileup contigs are not in the assembly (e.g. {missing[0]})")
+    return np.array([local.get(c, 0xFFFFFFFF) for c in file_names], dtype=np.uint32)
+
+
+def _check_mod_code(mt):
+    if mt not in MOD_CODES:
+        raise ValueError(f"unknown modification type '{mt}' (constants.py:28-37 knows m, a, 21839)")
+
+
+def _read_statistics_device(eng, lib, pileup, threads, local, wanted, allow_assembly_pileup_mismatch, min_valid_read_coverage,
+                            min_valid_cov_to_diff_fraction):
+    """The pileup parsed on the device with its count columns -> one read-statistics slot per wanted mod code, straight from the
+    device columns (rows of the other codes are skipped in place)."""
     h = C.c_void_p()
     try:
-        eng.upload_assembly(names, [asm[n] for n in names], ["all"] * len(names))
-        _lib.check(lib.nm_bed_open_counts(os.fsencode(pileup), int(threads), C.byref(h)))
+        _lib.check(lib.nm_bed_parse_device_counts(eng.ctx, os.fsencode(str(pileup)), int(threads), C.byref(h)))
+        n, nc = C.c_uint64(0), C.c_uint32(0)
+        _lib.check(lib.nm_bedcols_shape(h, C.byref(n), C.byref(nc), None, None))
+        file_names = []
+        for i in range(nc.value):
+            s = C.c_char_p()
+            _lib.check(lib.nm_bedcols_contig_name(h, i, C.byref(s)))
+            file_names.append(_lib.text_of(s.value, "a pileup contig name"))
+        lut = _contig_lut(file_names, local, allow_assembly_pileup_mismatch)
+        _lib.check(lib.nm_bedcols_map_contigs(h, lut.ctypes.data_as(C.POINTER(C.c_uint32)), len(lut)))
+        for mt in sorted(wanted):
+            _check_mod_code(mt)
+            slot = MOD_CODES.index(mt)            # (the parser's mod ids: 0 m, 1 a, 2 21839 — MOD_CODES' order)
+            kept = C.c_uint64(0)
+            _lib.check(lib.nm_readstats_upload_bedcols(eng.ctx, h, slot, slot, int(min_valid_read_coverage),
+                                                       float(min_valid_cov_to_diff_fraction), C.byref(kept)))
+    finally:
+        if h:
+            lib.nm_bedcols_close(h)
+
+
+def _read_statistics_host(eng, lib, pileup, threads, local, wanted, allow_assembly_pileup_mismatch, min_valid_read_coverage,
+                          min_valid_cov_to_diff_fraction):
+    """The same from the host reader's rows (nm_bed_open_counts), uploaded per mod code."""
+    h = C.c_void_p()
+    try:
+        _lib.check(lib.nm_bed_open_counts(os.fsencode(str(pileup)), int(threads), C.byref(h)))
         n, nc = C.c_uint64(0), C.c_uint32(0)
         _lib.check(lib.nm_bed_shape(h, C.byref(n), C.byref(nc)))
         file_names = []
@@ -116,11 +210,7 @@ def methylation_pattern(pileup, assembly, motifs, threads=1, min_valid_read_cove
             s = C.c_char_p()
             _lib.check(lib.nm_bed_contig_name(h, i, C.byref(s)))
             file_names.append(s.value.decode())
-        local = {c: i for i, c in enumerate(names)}
-        missing = [c for c in file_names if c not in local]
-        if missing and not allow_assembly_pileup_mismatch:
-            raise ValueError(f"{len(missing)} pileup contigs are not in the assembly (e.g. {missing[0]})")
-        lut = np.array([local.get(c, 0xFFFFFFFF) for c in file_names], dtype=np.uint32)
+        lut = _contig_lut(file_names, local, allow_assembly_pileup_mismatch)
         ptr = [C.c_void_p() for _ in range(6)]
         _lib.check(lib.nm_bed_columns(h, *[C.byref(x) for x in ptr]))
         cnt = [C.c_void_p(), C.c_void_p()]
@@ -129,21 +219,14 @@ def methylation_pattern(pileup, assembly, motifs, threads=1, min_valid_read_cove
         contig, position, mod = view(ptr[0], C.c_uint32), view(ptr[1], C.c_int64), view(ptr[2], C.c_int8)
         strand, nvalid = view(ptr[3], C.c_uint8), view(ptr[5], C.c_int64)
         nmod, ndiff = view(cnt[0], C.c_int32), view(cnt[1], C.c_int32)
-        wanted = {parse_motif_mod(m)[1] if isinstance(m, str) else m[1] for m in motifs}
         for mt in sorted(wanted):
-            if mt not in MOD_CODES:
-                raise ValueError(f"unknown modification type '{mt}' (constants.py:28-37 knows m, a, 21839)")
+            _check_mod_code(mt)
             sel = np.flatnonzero(mod == MOD_CODES.index(mt))
             upload_read_statistics(eng, mt, lut[contig[sel]], position[sel], strand[sel], np.clip(nvalid[sel], -1, 2**31 - 1), nmod[sel],
                                    ndiff[sel], min_valid_read_coverage, min_valid_cov_to_diff_fraction)
-        rows = read_methylation_table(eng, motifs, output_type)
     finally:
         if h:
             lib.nm_bed_close(h)
-        eng.close()
-    if output:
-        write_tsv(rows, output)
-    return rows
 
 
 def write_tsv(rows, path, columns=COLUMNS):

@@ -44,7 +44,8 @@ constexpr uint32_t BLOCK_BYTES = 16384;           // bytes per workgroup in the 
 constexpr uint64_t SLAB_BYTES = 32ull << 20;            // per slab: 3 pinned + 2 device buffers of this size (pinning memory costs ~0.2 ms per MB)
 constexpr uint32_t PATCH_CAP = 1u << 22;
 
-enum RowError : uint32_t { E_NONE = 0, E_COLUMNS = 1, E_START = 2, E_COV = 3, E_PCT = 4, E_POS_RANGE = 5, E_STRAND = 6, E_START_NEG = 7 };
+enum RowError : uint32_t { E_NONE = 0, E_COLUMNS = 1, E_START = 2, E_COV = 3, E_PCT = 4, E_POS_RANGE = 5, E_STRAND = 6, E_START_NEG = 7,
+                           E_COUNTS = 8, E_DECLINE = 9 };
 
 // bit k of the result = byte k of the 64 bytes at `base` is the first byte of a non-empty line.  The 64 bytes come as four
 // 16-byte loads (the text buffers are 16-byte aligned and padded); the bytes before and after them decide the edges.
@@ -156,6 +157,10 @@ struct BedOut {
     unsigned int *n_patch;
     uint4 *patch;               // (row, flags, file offset lo, hi) — a pileup holds fewer than 2^32 rows (checked)
 };
+// the count-columns parse (nm_bed_parse_device_counts) also writes columns 12 (N_mod) and 17 (N_diff)
+struct BedCountOut : BedOut {
+    int32_t *nmod, *ndiff;
+};
 
 __device__ __forceinline__ bool field_is_null(const uint8_t *p, uint32_t n) {
     return n == 0 || (n == 2 && p[0] == 'N' && p[1] == 'A') || (n == 4 && p[0] == 'n' && p[1] == 'u' && p[2] == 'l' && p[3] == 'l');
@@ -189,13 +194,18 @@ __device__ __forceinline__ uint32_t bytes_equal_mask8(uint32_t lo, uint32_t hi, 
 // The fields of one line, as byte offsets from its first byte: b/e of the six columns that are read (1 contig, 2 start, 4 mod code,
 // 6 strand, 10 N_valid_cov, 11 percent; numbered from 0 here) and the number of tab-separated fields up to the end of the line.
 struct BedFields { uint32_t b0, e0, b1, e1, b3, e3, b5, e5, b9, e9, b10, e10, nf; };
+// ... and for the count-columns parse also 12 (N_mod) and 17 (N_diff)
+struct BedCountFields : BedFields { uint32_t b11, e11, b16, e16; };
+template <bool COUNTS> using BedFieldsOf = typename std::conditional<COUNTS, BedCountFields, BedFields>::type;
+template <bool COUNTS> using BedOutOf = typename std::conditional<COUNTS, BedCountOut, BedOut>::type;
 
 // The line's tabs WITHOUT walking it byte by byte (round 6: the walk — ~80 dependent byte loads per line, a dozen instructions each —
 // was two thirds of this kernel, and with the inflate kernels no longer waiting on memory beside it, this kernel became the largest
 // consumer of the GPU in a from-files run): the line is loaded in pieces of 16 bytes (unaligned 16-byte loads), every piece gives 16
 // bits "is a tab" and 16 bits "is a newline", the first newline ends the line, and the tabs below it are taken out of a 128-bit mask one
-// by one.  false: no newline within 128 bytes (bed_split_walk does such lines).
-__device__ __forceinline__ bool bed_split_masks(const uint8_t *__restrict__ p, uint64_t avail, BedFields &f) {
+// by one.  false: no newline within 128 bytes (bed_split_walk does such lines).  COUNTS: seventeen tabs are taken out, not eleven.
+template <bool COUNTS>
+__device__ __forceinline__ bool bed_split_masks(const uint8_t *__restrict__ p, uint64_t avail, BedFieldsOf<COUNTS> &f) {
     const uint32_t want = avail < 128 ? (uint32_t)avail : 128u;
     unsigned long long tab[2] = {0, 0}, nl[2] = {0, 0};
     bool open = true;                                                   // no newline seen yet
@@ -224,10 +234,12 @@ __device__ __forceinline__ bool bed_split_masks(const uint8_t *__restrict__ p, u
     else if (end < 128) tab[1] &= (1ull << (end - 64)) - 1;
     f.nf = (uint32_t)__popcll(tab[0]) + (uint32_t)__popcll(tab[1]) + 1u;
     f.b0 = 0; f.e0 = f.b1 = f.e1 = f.b3 = f.e3 = f.b5 = f.e5 = f.b9 = f.e9 = f.b10 = f.e10 = 0;
-    if (f.nf < 12) return true;                                         // (fewer than eleven tabs: the caller refuses the line)
-    uint32_t t[11];
+    constexpr int NT = COUNTS ? 17 : 11;
+    if constexpr (COUNTS) f.b11 = f.e11 = f.b16 = f.e16 = 0;
+    if (f.nf < NT + 1) return true;                                     // (fewer than NT tabs: the caller refuses the line)
+    uint32_t t[NT];
 #pragma unroll
-    for (int k = 0; k < 11; ++k) {
+    for (int k = 0; k < NT; ++k) {
         if (tab[0]) { t[k] = (uint32_t)__builtin_ctzll(tab[0]); tab[0] &= tab[0] - 1; }
         else { t[k] = 64u + (uint32_t)__builtin_ctzll(tab[1]); tab[1] &= tab[1] - 1; }
     }
@@ -237,12 +249,18 @@ __device__ __forceinline__ bool bed_split_masks(const uint8_t *__restrict__ p, u
     f.b5 = t[4] + 1; f.e5 = t[5];
     f.b9 = t[8] + 1; f.e9 = t[9];
     f.b10 = t[9] + 1; f.e10 = t[10];
+    if constexpr (COUNTS) {
+        f.b11 = t[10] + 1; f.e11 = t[11];
+        f.b16 = t[15] + 1; f.e16 = t[16];
+    }
     return true;
 }
 
 // the same by walking the line (lines of more than 128 bytes)
-__device__ __forceinline__ void bed_split_walk(const uint8_t *__restrict__ p, const uint8_t *__restrict__ end, BedFields &f) {
+template <bool COUNTS>
+__device__ __forceinline__ void bed_split_walk(const uint8_t *__restrict__ p, const uint8_t *__restrict__ end, BedFieldsOf<COUNTS> &f) {
     uint32_t b0 = 0, e0 = 0, b1 = 0, e1 = 0, b3 = 0, e3 = 0, b5 = 0, e5 = 0, b9 = 0, e9 = 0, b10 = 0, e10 = 0;
+    uint32_t b11 = 0, e11 = 0, b16 = 0, e16 = 0;                      // (COUNTS only)
     uint32_t nf = 0, at = 0, start = 0;
     for (;;) {
         const bool stop = p + at >= end || p[at] == '\n';
@@ -256,18 +274,35 @@ __device__ __forceinline__ void bed_split_walk(const uint8_t *__restrict__ p, co
                 case 10: b10 = start; e10 = at; break;
                 default: break;
             }
+            if constexpr (COUNTS) {
+                if (nf == 11) { b11 = start; e11 = at; }
+                else if (nf == 16) { b16 = start; e16 = at; }
+            }
             ++nf;
             if (stop) break;
             start = at + 1;
         }
         ++at;
     }
-    f = BedFields{b0, e0, b1, e1, b3, e3, b5, e5, b9, e9, b10, e10, nf};
+    static_cast<BedFields &>(f) = BedFields{b0, e0, b1, e1, b3, e3, b5, e5, b9, e9, b10, e10, nf};
+    if constexpr (COUNTS) { f.b11 = b11; f.e11 = e11; f.b16 = b16; f.e16 = e16; }
 }
 
-// (3) one thread per line
+// a count column (12 N_mod, 17 N_diff) by the host reader's rule (nmbed.cpp): an integer in [0, 0x7FFFFFFF].  0: the value,
+// E_COUNTS: refused; E_DECLINE: more than 18 digits (the host reader's 64-bit accumulation could wrap: the host decides)
+__device__ __forceinline__ uint32_t dev_parse_count(const uint8_t *p, uint32_t n, int32_t *out) {
+    if (n - (n && p[0] == '-') > 18) return E_DECLINE;
+    long long v = 0;
+    if (!dev_parse_int(p, n, &v) || v < 0 || v > 0x7FFFFFFFll) return E_COUNTS;
+    *out = (int32_t)v;
+    return E_NONE;
+}
+
+// (3) one thread per line.  COUNTS (nm_bed_parse_device_counts): also columns 12 and 17 — a separate instantiation, the
+// motif_discovery parse (COUNTS = false) is the same code as without it
+template <bool COUNTS>
 __global__ __launch_bounds__(256) void bed_parse_kernel(const uint8_t *__restrict__ b, uint64_t n, const uint32_t *__restrict__ line_start,
-                                                        uint32_t n_lines, uint64_t row0, uint64_t slab_file_off, BedOut o) {
+                                                        uint32_t n_lines, uint64_t row0, uint64_t slab_file_off, BedOutOf<COUNTS> o) {
     const uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
     if (li >= n_lines) return;
     const uint64_t row = row0 + li;
@@ -275,8 +310,8 @@ __global__ __launch_bounds__(256) void bed_parse_kernel(const uint8_t *__restric
     const uint8_t *end = b + n;
     // a bedMethyl row has exactly 18 tab-separated columns (dataload.py:15-34: the reference reads the file against a fixed 18-column
     // schema), so every tab of the line is counted
-    BedFields f;
-    if (!bed_split_masks(p, n - line_start[li], f)) bed_split_walk(p, end, f);
+    BedFieldsOf<COUNTS> f;
+    if (!bed_split_masks<COUNTS>(p, n - line_start[li], f)) bed_split_walk<COUNTS>(p, end, f);
     const uint32_t b0 = f.b0, e0 = f.e0, b1 = f.b1, e1 = f.e1, b3 = f.b3, e3 = f.e3, b5 = f.b5, e5 = f.e5, b9 = f.b9, e9 = f.e9, b10 = f.b10, e10 = f.e10;
     const uint32_t nf = f.nf;
     // ("\r\n" line ends: the '\r' can only sit in the eighteenth field, which is not read)
@@ -340,6 +375,13 @@ __global__ __launch_bounds__(256) void bed_parse_kernel(const uint8_t *__restric
         if (e5 - b5 == 1 && (p[b5] == '+' || p[b5] == '-')) st = p[b5];
         else err = E_STRAND;
     }
+    int32_t nmod = 0, ndiff = 0;
+    if constexpr (COUNTS) {
+        // the host reader checks these last (nmbed.cpp); a percentage left to the host may be refused there first: such a row declines
+        if (!err) err = dev_parse_count(p + f.b11, f.e11 - f.b11, &nmod);
+        if (!err) err = dev_parse_count(p + f.b16, f.e16 - f.b16, &ndiff);
+        if (err == E_COUNTS && (flags & 2u)) err = E_DECLINE;
+    }
     if (err) {
         atomicMin(o.first_error, ((unsigned long long)row << 8) | err);
         o.hash[li] = 0;
@@ -351,6 +393,10 @@ __global__ __launch_bounds__(256) void bed_parse_kernel(const uint8_t *__restric
     o.strand[row] = st;
     o.frac[row] = frac;
     o.nvalid[row] = cov < 0 ? -1 : (int32_t)(cov > 0x7FFFFFFF ? 0x7FFFFFFF : cov);
+    if constexpr (COUNTS) {
+        o.nmod[row] = nmod;
+        o.ndiff[row] = ndiff;
+    }
     if (flags) {
         const unsigned int k = atomicAdd(o.n_patch, 1u);
         const uint64_t off = slab_file_off + line_start[li];
@@ -430,6 +476,9 @@ struct nm_bedcols {
     uint8_t *d_strand = nullptr;
     double *d_frac = nullptr;
     int32_t *d_nvalid = nullptr;
+    int32_t *d_nmod = nullptr, *d_ndiff = nullptr;      // columns 12 / 17: only for nm_bed_parse_device_counts
+    bool counts = false;
+    bool mapped = false;                    // nm_bedcols_map_contigs has filled d_contig
     std::vector<std::string> names, other_mods;
     std::vector<const char *> name_ptrs;
     std::vector<uint64_t> run_row;          // ascending, + n_rows at the end
@@ -441,11 +490,12 @@ struct nm_bedcols {
 namespace {
 
 void free_cols(nm_bedcols *b) {
-    void *ptrs[] = {b->d_file_contig, b->d_contig, b->d_position, b->d_mod, b->d_strand, b->d_frac, b->d_nvalid};
+    void *ptrs[] = {b->d_file_contig, b->d_contig, b->d_position, b->d_mod, b->d_strand, b->d_frac, b->d_nvalid, b->d_nmod, b->d_ndiff};
     for (void *p : ptrs)
         if (p) (void)dev_free(p);
     b->d_file_contig = b->d_contig = b->d_position = nullptr;
     b->d_mod = nullptr; b->d_strand = nullptr; b->d_frac = nullptr; b->d_nvalid = nullptr;
+    b->d_nmod = b->d_ndiff = nullptr;
 }
 
 // grow the six output columns (+ hash) to hold `rows`; device-to-device copies of what is there
@@ -467,6 +517,7 @@ int grow(nm_bedcols *b, uint64_t rows, hipStream_t s) {
     if ((rc = regrow((void **)&b->d_position, 4)) || (rc = regrow((void **)&b->d_mod, 1)) || (rc = regrow((void **)&b->d_strand, 1)) ||
         (rc = regrow((void **)&b->d_frac, 8)) || (rc = regrow((void **)&b->d_nvalid, 4)))
         return rc;
+    if (b->counts && ((rc = regrow((void **)&b->d_nmod, 4)) || (rc = regrow((void **)&b->d_ndiff, 4)))) return rc;
     b->cap = ncap;
     return NM_OK;
 }
@@ -480,6 +531,7 @@ const char *row_error_text(uint32_t code) {
         case E_POS_RANGE: return "pileup position beyond 4 Gbp";
         case E_STRAND: return "pileup column 6 (strand) is neither '+' nor '-'";
         case E_START_NEG: return "pileup column 2 (start) is negative";
+        case E_COUNTS: return "pileup column 12 (N_mod) or 17 (N_diff) is not a non-negative integer";     // (the host reader's words)
         default: return "malformed pileup line";
     }
 }
@@ -592,7 +644,9 @@ int map_file(const char *path, TextSource *src) {
 }
 
 // *row_error (may be NULL): NM_EINVAL came from the TEXT — a line that is no bedMethyl row — not from the file, its blocks or an argument
-int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t threads, nm_bedcols **out, bool *row_error = nullptr);
+// counts: also columns 12 (N_mod) and 17 (N_diff) (nm_bed_parse_device_counts)
+int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t threads, nm_bedcols **out, bool *row_error = nullptr,
+                      bool counts = false);
 
 }  // namespace
 
@@ -603,9 +657,10 @@ struct nm_bedplan {                          // nm_bed_plan_indexed: the pieces 
     uint64_t stats[4] = {0, 0, 0, 0};
 };
 
-extern "C" {
+namespace {
 
-int nm_bed_parse_device(nm_ctx *c, const char *path, uint32_t threads, nm_bedcols **out) {
+// a whole plain-text or bgzip file (nm_bed_parse_device, nm_bed_parse_device_counts)
+int parse_device_file(nm_ctx *c, const char *path, uint32_t threads, nm_bedcols **out, bool counts) {
     if (!c || !path || !out) return fail(NM_EINVAL, "NULL argument");
     *out = nullptr;
     TextSource src;
@@ -629,7 +684,19 @@ int nm_bed_parse_device(nm_ctx *c, const char *path, uint32_t threads, nm_bedcol
             return fail(NM_EDECLINED, "%s: compressed input that is not bgzip: the device parser reads plain text and BGZF (use nm_bed_open)", path);
         src.bgzf = true;
     }
-    return parse_device_impl(c, path, src, threads, out);
+    return parse_device_impl(c, path, src, threads, out, nullptr, counts);
+}
+
+}  // namespace
+
+extern "C" {
+
+int nm_bed_parse_device(nm_ctx *c, const char *path, uint32_t threads, nm_bedcols **out) {
+    return parse_device_file(c, path, threads, out, false);
+}
+
+int nm_bed_parse_device_counts(nm_ctx *c, const char *path, uint32_t threads, nm_bedcols **out) {
+    return parse_device_file(c, path, threads, out, true);
 }
 
 // The HOST-ONLY half of the indexed parse — the tabix index read, the wanted contigs' regions, the walk over their BGZF blocks (half a
@@ -733,7 +800,7 @@ int nm_bed_parse_device_indexed(nm_ctx *c, const char *path, const char *tbi_pat
 
 namespace {
 
-int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t threads, nm_bedcols **out, bool *row_error) {
+int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t threads, nm_bedcols **out, bool *row_error, bool counts) {
     bool row_error_unused = false;
     if (!row_error) row_error = &row_error_unused;
     *row_error = false;
@@ -746,6 +813,7 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
     nm_bedcols *b = new (std::nothrow) nm_bedcols();
     if (!b) return fail(NM_ENOMEM, "out of host memory");
     b->ctx = c;
+    b->counts = counts;
     struct Fail { nm_bedcols *b; bool keep = false; ~Fail() { if (!keep) (void)nm_bedcols_close(b); } } guard{b};
     // bgzip: the blocks are inflated ON THE DEVICE (bed_inflate_kernel) unless NM_BED_HOST_INFLATE=1 asks for the copy threads
     const bool dev_inflate = src.bgzf && getenv("NM_BED_HOST_INFLATE") == nullptr;
@@ -958,9 +1026,18 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
                     (unsigned long long)want, clock_s() - tp2);
         if (n_lines) {
             hipLaunchKernelGGL(bed_starts_kernel, dim3(nblk), dim3(256), 0, c->stream, d_text, len, d_block_off, d_line_start);
-            BedOut o{d_hash, b->d_position, b->d_mod, b->d_strand, b->d_frac, b->d_nvalid, d_first_error, d_counters, d_patch};
-            hipLaunchKernelGGL(bed_parse_kernel, dim3((n_lines + 255) / 256), dim3(256), 0, c->stream, d_text, len, d_line_start, n_lines, b->n_rows,
-                               text_base, o);
+            const BedOut o{d_hash, b->d_position, b->d_mod, b->d_strand, b->d_frac, b->d_nvalid, d_first_error, d_counters, d_patch};
+            if (counts) {
+                BedCountOut oc;
+                static_cast<BedOut &>(oc) = o;
+                oc.nmod = b->d_nmod;
+                oc.ndiff = b->d_ndiff;
+                hipLaunchKernelGGL(bed_parse_kernel<true>, dim3((n_lines + 255) / 256), dim3(256), 0, c->stream, d_text, len, d_line_start, n_lines,
+                                   b->n_rows, text_base, oc);
+            } else {
+                hipLaunchKernelGGL(bed_parse_kernel<false>, dim3((n_lines + 255) / 256), dim3(256), 0, c->stream, d_text, len, d_line_start, n_lines,
+                                   b->n_rows, text_base, o);
+            }
             hipLaunchKernelGGL(bed_runs_kernel, dim3((n_lines + 255) / 256), dim3(256), 0, c->stream, d_hash, d_line_start, n_lines, b->n_rows, text_base,
                                first_rows ? 1 : 0, d_prev + (n_parsed & 1), d_prev + ((n_parsed + 1) & 1), d_counters + 1, d_runs, RUN_CAP,
                                d_text, len, d_run_names, RUN_NAME_CAP);
@@ -1342,6 +1419,9 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
     unsigned long long first_error = ~0ull;
     HIP_TRY(hipMemcpyAsync(&first_error, d_first_error, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    if (first_error != ~0ull && (first_error & 0xFF) == E_DECLINE)
+        return fail(NM_EDECLINED, "%s: a count column (12 N_mod / 17 N_diff) the host reader decides (more than 18 digits, or beside a "
+                    "percentage left to the host): use nm_bed_open_counts", path);
     if (first_error != ~0ull) return fail_row(fail(NM_EINVAL, "%s: %s", path, row_error_text((uint32_t)(first_error & 0xFF))));
     std::vector<char> line_buf(1u << 16);
     // k-th tab-separated field of the line at text offset `line` (buf: scratch of the calling thread).  A short window first:
@@ -1560,7 +1640,7 @@ int nm_bedcols_runs(nm_bedcols *b, uint64_t *run_row, uint32_t *run_contig) {
 int nm_bedcols_map_contigs(nm_bedcols *b, const uint32_t *contig_lut, uint32_t n_lut) {
     if (!b || !contig_lut) return fail(NM_EINVAL, "NULL argument");
     if (n_lut != b->names.size()) return fail(NM_EINVAL, "contig_lut has %u entries, the pileup names %zu contigs", n_lut, b->names.size());
-    if (b->n_rows == 0) return NM_OK;
+    if (b->n_rows == 0) { b->mapped = true; return NM_OK; }
     nm_ctx *c = b->ctx;
     HIP_TRY(hipSetDevice(c->device));
     uint32_t *d_lut = nullptr;
@@ -1571,6 +1651,7 @@ int nm_bedcols_map_contigs(nm_bedcols *b, const uint32_t *contig_lut, uint32_t n
     const hipError_t e2 = hipStreamSynchronize(c->stream);
     (void)dev_free(d_lut);
     if (e != hipSuccess || e2 != hipSuccess) return fail(NM_EHIP, "contig mapping failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    b->mapped = true;
     return NM_OK;
 }
 
@@ -1595,4 +1676,25 @@ int nm_bedcols_device_columns(nm_bedcols *b, const uint32_t **contig_id, const u
     return NM_OK;
 }
 
+int nm_bedcols_count_columns(nm_bedcols *b, const int32_t **n_modified, const int32_t **n_diff) {
+    if (!b || !n_modified || !n_diff) return fail(NM_EINVAL, "NULL argument");
+    if (!b->counts) return fail(NM_ESTATE, "the pileup was not parsed with nm_bed_parse_device_counts");
+    *n_modified = b->d_nmod;
+    *n_diff = b->d_ndiff;
+    return NM_OK;
+}
+
 }  // extern "C"
+
+namespace nmdetail {
+
+int bedcols_readstats_view(nm_bedcols *b, nm_ctx *c, BedcolsView *v) {
+    if (!b || !v) return fail(NM_EINVAL, "NULL argument");
+    if (b->ctx != c) return fail(NM_EINVAL, "the pileup columns live on another ctx");
+    if (!b->counts) return fail(NM_ESTATE, "the pileup was not parsed with nm_bed_parse_device_counts");
+    if (!b->mapped) return fail(NM_ESTATE, "nm_bedcols_map_contigs must come first");
+    *v = BedcolsView{b->n_rows, b->d_contig, b->d_position, b->d_mod, b->d_strand, b->d_nvalid, b->d_nmod, b->d_ndiff};
+    return NM_OK;
+}
+
+}  // namespace nmdetail

@@ -27,15 +27,17 @@ using namespace nmdetail;
 
 namespace {
 
-// (1) rows that pass the read filters set their bit in the presence plane of their strand
+// (1) rows that pass the read filters set their bit in the presence plane of their strand.  mod_type (may be NULL): the rows of
+// every mod code, of which only those of mod_id are read (nm_readstats_upload_bedcols: the parser's columns, uncompacted)
 __global__ void rs_mark_kernel(uint64_t n_rows, const uint32_t *__restrict__ contig_id, const uint32_t *__restrict__ position,
                                const uint8_t *__restrict__ strand, const int32_t *__restrict__ n_valid,
-                               const int32_t *__restrict__ n_diff, int32_t min_cov, double min_frac,
-                               const uint32_t *__restrict__ contig_chunk, const uint64_t *__restrict__ contig_len,
+                               const int32_t *__restrict__ n_diff, const int8_t *__restrict__ mod_type, int8_t mod_id, int32_t min_cov,
+                               double min_frac, const uint32_t *__restrict__ contig_chunk, const uint64_t *__restrict__ contig_len,
                                uint32_t n_contigs, uint32_t *Pp, uint32_t *Pm, uint8_t *__restrict__ pass, unsigned int *err) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rows) return;
     pass[i] = 0;
+    if (mod_type && mod_type[i] != mod_id) return;                    // a row of another mod code
     const uint32_t cid = contig_id[i];
     if (cid == 0xFFFFFFFFu) return;                                   // contig not resident on this device
     const uint32_t pos = position[i];
@@ -265,15 +267,13 @@ void free_readstats(nm_ctx *c) {
 
 }  // namespace nmdetail
 
-extern "C" {
+namespace {
 
-int nm_readstats_upload(nm_ctx *c, uint32_t slot, uint64_t n_rows, const uint32_t *contig_id, const uint32_t *position,
-                        const uint8_t *strand, const int32_t *n_valid_cov, const int32_t *n_modified, const int32_t *n_diff,
-                        int32_t min_valid_read_coverage, double min_valid_cov_to_diff_fraction, int rows_on_device, uint64_t *n_kept) {
-    if (!c) return fail(NM_EINVAL, "ctx is NULL");
-    if (!c->dH) return fail(NM_ESTATE, "nm_upload_contigs must come first");
-    if (slot >= NM_MAX_MOD_SLOTS) return fail(NM_EINVAL, "slot %u >= %d", slot, NM_MAX_MOD_SLOTS);
-    if (n_rows && (!contig_id || !position || !strand || !n_valid_cov || !n_modified)) return fail(NM_EINVAL, "NULL column");
+// nm_readstats_upload; mod_type (device, may be NULL): read only the rows whose mod type is mod_id
+int readstats_upload_impl(nm_ctx *c, uint32_t slot, uint64_t n_rows, const uint32_t *contig_id, const uint32_t *position,
+                          const uint8_t *strand, const int32_t *n_valid_cov, const int32_t *n_modified, const int32_t *n_diff,
+                          const int8_t *mod_type, int8_t mod_id, int32_t min_valid_read_coverage, double min_valid_cov_to_diff_fraction,
+                          int rows_on_device, uint64_t *n_kept) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     ReadStats &rs = c->readstats[slot];
@@ -331,8 +331,8 @@ int nm_readstats_upload(nm_ctx *c, uint32_t slot, uint64_t n_rows, const uint32_
     const dim3 blk(256), grid((unsigned)((n_rows + 255) / 256));
     if (n_rows) {
         hipLaunchKernelGGL(rs_mark_kernel, grid, blk, 0, c->stream, n_rows, (const uint32_t *)col[0], (const uint32_t *)col[1],
-                           (const uint8_t *)col[2], (const int32_t *)col[3], (const int32_t *)col[5], min_valid_read_coverage,
-                           min_valid_cov_to_diff_fraction, c->d_contig_chunk, c->d_contig_len, c->n_contigs, Pp, Pm, d_pass, c->d_err);
+                           (const uint8_t *)col[2], (const int32_t *)col[3], (const int32_t *)col[5], mod_type, mod_id,
+                           min_valid_read_coverage, min_valid_cov_to_diff_fraction, c->d_contig_chunk, c->d_contig_len, c->n_contigs, Pp, Pm, d_pass, c->d_err);
         HIP_TRY(hipGetLastError());
     }
     uint64_t *d_total = nullptr;
@@ -378,6 +378,33 @@ int nm_readstats_upload(nm_ctx *c, uint32_t slot, uint64_t n_rows, const uint32_
     guard.keep = true;
     if (n_kept) *n_kept = rs.n_rows[0] + rs.n_rows[1];
     return NM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nm_readstats_upload(nm_ctx *c, uint32_t slot, uint64_t n_rows, const uint32_t *contig_id, const uint32_t *position,
+                        const uint8_t *strand, const int32_t *n_valid_cov, const int32_t *n_modified, const int32_t *n_diff,
+                        int32_t min_valid_read_coverage, double min_valid_cov_to_diff_fraction, int rows_on_device, uint64_t *n_kept) {
+    if (!c) return fail(NM_EINVAL, "ctx is NULL");
+    if (!c->dH) return fail(NM_ESTATE, "nm_upload_contigs must come first");
+    if (slot >= NM_MAX_MOD_SLOTS) return fail(NM_EINVAL, "slot %u >= %d", slot, NM_MAX_MOD_SLOTS);
+    if (n_rows && (!contig_id || !position || !strand || !n_valid_cov || !n_modified)) return fail(NM_EINVAL, "NULL column");
+    return readstats_upload_impl(c, slot, n_rows, contig_id, position, strand, n_valid_cov, n_modified, n_diff, nullptr, 0,
+                                 min_valid_read_coverage, min_valid_cov_to_diff_fraction, rows_on_device, n_kept);
+}
+
+int nm_readstats_upload_bedcols(nm_ctx *c, nm_bedcols *cols, uint32_t slot, int8_t mod_id, int32_t min_valid_read_coverage,
+                                double min_valid_cov_to_diff_fraction, uint64_t *n_kept) {
+    if (!c || !cols) return fail(NM_EINVAL, "NULL argument");
+    if (!c->dH) return fail(NM_ESTATE, "nm_upload_contigs must come first");
+    if (slot >= NM_MAX_MOD_SLOTS) return fail(NM_EINVAL, "slot %u >= %d", slot, NM_MAX_MOD_SLOTS);
+    BedcolsView v;
+    int rc = bedcols_readstats_view(cols, c, &v);
+    if (rc) return rc;
+    return readstats_upload_impl(c, slot, v.n_rows, v.contig_id, v.position, v.strand, v.n_valid_cov, v.n_modified, v.n_diff, v.mod_type,
+                                 mod_id, min_valid_read_coverage, min_valid_cov_to_diff_fraction, 1, n_kept);
 }
 
 int nm_contig_methylation(nm_ctx *c, uint32_t n_motifs, const uint8_t *motif_slot, const uint8_t *motif_len, const uint8_t *motif_modpos,

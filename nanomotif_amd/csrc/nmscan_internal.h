@@ -333,6 +333,16 @@ int score_batch_spec_begin(nm_ctx *c, int flight, uint32_t n_cand, const uint32_
 int upload_contigs_gather(nm_ctx *c, uint32_t n_contigs, const uint64_t *offsets, const uint64_t *src_off, const uint32_t *bin_id,
                           uint32_t n_bins, const uint8_t *d_seq_ascii);
 void free_readstats(nm_ctx *c);
+// the DEVICE columns nm_readstats_upload_bedcols reads from a count-columns parse (nmbedgpu.hip); NM_ESTATE unless the parse had
+// counts and nm_bedcols_map_contigs has filled contig_id
+struct BedcolsView {
+    uint64_t n_rows;
+    const uint32_t *contig_id, *position;
+    const int8_t *mod_type;
+    const uint8_t *strand;
+    const int32_t *n_valid_cov, *n_modified, *n_diff;
+};
+int bedcols_readstats_view(nm_bedcols *cols, nm_ctx *c, BedcolsView *view);
 // nm_timing_reset(ctx, 2): one event pair around a device phase of the library on the ctx stream (no-ops otherwise); the
 // pairs are summed by nm_timing_total_ms together with the scoring launches
 void busy_begin(nm_ctx *c);

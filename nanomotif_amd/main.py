@@ -509,6 +509,66 @@ class _LazyTables:
         return len(self._keys)
 
 
+def binnary(args):
+    """main.py:114-281: the read-methylation table (computed on the device, or read back from OUT when it exists and --force is
+    not given), the methylation filter, then contamination detection and / or contig inclusion and their files."""
+    import pandas as pd
+    from . import binnary as bn
+    from .contig_methylation import COLUMNS, methylation_pattern
+    log.info(f"Starting Binnary {args.command} analysis...")
+    contig_bins = bn.load_contig_bins(args.contig_bins)
+    motifs = bn.motif_mods_of_bin_motifs(args.bin_motifs)
+    # the reference's choice is spelled weighted_mean but compared with "weighted-mean" (main.py:144-148): both mean the weighted mean
+    output_type = "weighted-mean" if args.methylation_output_type == "weighted_mean" else args.methylation_output_type
+    table_path = os.path.join(args.out, f"motifs-scored-read-methylation_{args.methylation_output_type}.tsv")
+    if os.path.isfile(table_path) and not args.force:
+        log.info(f"{os.path.basename(table_path)} exists. Using existing file! Use --force to override this.")
+        table = pd.read_csv(table_path, sep="\t", dtype={"contig": str, "motif": str, "mod_type": str, "mod_position": np.int64,
+                                                          "methylation_value": np.float64, "mean_read_cov": np.float64, "n_motif_obs": np.int64},
+                            keep_default_na=False)
+    else:
+        log.info(f"Computing {os.path.basename(table_path)}")
+        device = args.device if args.device is not None else int(os.environ.get("LOCAL_RANK", "0") or 0)
+        rows = methylation_pattern(pileup=args.pileup, assembly=args.assembly, motifs=motifs, threads=args.threads,
+                                   min_valid_read_coverage=args.min_valid_read_coverage, batch_size=1000, min_valid_cov_to_diff_fraction=0.8,
+                                   output=table_path, allow_assembly_pileup_mismatch=True, output_type=output_type, device=device)
+        if not rows:
+            log.warning("the read-methylation table is empty")
+            sys.exit(1)
+        table = pd.DataFrame(rows, columns=COLUMNS)
+    log.info("Loading assembly file...")
+    assembly = bn.read_fasta(args.assembly)
+    lengths = bn.contig_lengths(assembly)
+    table = bn.filter_methylation(table, args.methylation_threshold)
+    contamination = None
+    if args.command == "detect_contamination" and args.contamination_file:
+        contamination = bn.load_contamination_file(args.contamination_file)
+    if (args.command == "detect_contamination" and not args.contamination_file) or (args.command == "include_contigs" and args.run_detect_contamination):
+        contamination = bn.detect_contamination(bn.add_bin(table, contig_bins), lengths, args.num_consensus, args.threads)
+        bn.generate_output(contamination, args.out, "bin_contamination.tsv")
+    if args.command == "detect_contamination":
+        new_contig_bins = bn.create_contig_bin_file(contig_bins, contamination)
+        bn.generate_output(new_contig_bins, args.out, "decontaminated_contig_bin.tsv")
+    else:
+        if args.contamination_file:
+            log.info("Loading contamination file...")
+            contamination = bn.load_contamination_file(args.contamination_file)
+        if contamination is None:
+            contamination = pd.DataFrame({"contig": []}, dtype=str)
+        log.info("Removing contaminants from bins")
+        contig_bins = contig_bins[~contig_bins["contig"].isin(contamination["contig"])]
+        included = bn.include_contigs(bn.add_bin(table, contig_bins), lengths, mean_probability=args.mean_model_confidence)
+        bn.generate_output(included, args.out, "include_contigs.tsv")
+        unique = (included[included["confidence"] == "high_confidence"][["contig", "assigned_bin"]].rename(columns={"assigned_bin": "bin"})
+                  .drop_duplicates())
+        new_contig_bins = bn.create_contig_bin_file(contig_bins, contamination, include=unique)
+        bn.generate_output(new_contig_bins, args.out, "new_contig_bin.tsv")
+    if args.write_bins:
+        log.info("Write bins flag is set. Writing bins to file...")
+        bn.write_bins_from_contigs(new_contig_bins, assembly, os.path.join(args.out, args.command + "_bins"))
+    log.info(f"Analysis Completed. Results are saved to: {args.out}")
+
+
 def check_installation():
     """main.py:330-346 runs motif_discovery on the packaged geobacillus data; its pileup is not distributable, so
     this build runs the same command on a small synthetic data set with the same planted motifs."""
@@ -551,6 +611,11 @@ def main(argv=None):
         if result is None and rank == 0:
             with open(os.path.join(args.out, "bin-motifs.tsv"), "w") as f:     # main.py:317-321
                 f.write(HEADER)
+    elif args.command in ("detect_contamination", "include_contigs"):
+        args.verbose = False                     # main.py:310-312: binnary runs with seed 1
+        args.seed = 1
+        shared_setup(args, args.out)
+        binnary(args)
     elif args.command == "check_installation":
         sys.exit(check_installation())
     else:
