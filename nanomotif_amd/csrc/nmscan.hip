@@ -148,6 +148,68 @@ __device__ __forceinline__ void apply_single(uint32_t idx, uint32_t r, const Til
     }
 }
 
+// Candidate k's two counters of this wave: one (candidate, contig) row of the count table (PC), or the lane's LDS slots.
+template <class K>
+__device__ __forceinline__ void emit_counts(const ScoreArgs &a, uint32_t n_mod, uint32_t n_non, uint32_t k0, uint32_t k,
+                                            uint32_t *lds_acc, uint32_t lds_row0, int lane, uint32_t contig_rank) {
+    if (K::PC) {
+        // per-contig counters (motif_model_contig per contig, find_motifs_bin.py:1285-1331): a chunk lies inside ONE
+        // contig, so the wave's sum goes straight to that (candidate, contig) row
+#pragma unroll
+        for (int o = 32; o; o >>= 1) {
+            n_mod += __shfl_xor(n_mod, o);
+            n_non += __shfl_xor(n_non, o);
+        }
+        if (lane == 0 && (n_mod | n_non)) {
+            unsigned long long *row = a.out + (a.row_base[k0 + k] + contig_rank) * 2;
+            if (n_mod) atomicAdd(row, (unsigned long long)n_mod);
+            if (n_non) atomicAdd(row + 1, (unsigned long long)n_non);
+        }
+        return;
+    }
+    atomicAdd(&lds_acc[((k * K::NS + lds_row0) * 2 + 0) * 64 + lane], n_mod);
+    atomicAdd(&lds_acc[((k * K::NS + lds_row0) * 2 + 1) * 64 + lane], n_non);
+}
+
+// Heavy batches (the non-CF variants): both strands of a candidate from its forward masks (JointWalk, nmscan_device.h), one
+// s_load_dwordx16 per candidate.
+template <class K, int CAN>
+__device__ __forceinline__ void score_heavy(const ScoreArgs &a, const Tile<K> &tile, const uint32_t (&sw)[K::NST][T_WORDS],
+                                            uint32_t k0, uint32_t nb, uint32_t *lds_acc, uint32_t lds_row0, int lane,
+                                            uint32_t contig_rank) {
+    constexpr int PF = CAN == 0 ? 0 : 1;   // plane of the canonical base: A or C
+    constexpr int PR = CAN == 0 ? 3 : 2;   // plane of its complement:     T or G
+    uint32_t basef[T_WORDS], baser[T_WORDS];
+#pragma unroll
+    for (int t = 0; t < T_WORDS; ++t) {
+        // compact batches: the canonical literal at the modified position is left out of the program, the plane is the
+        // walk's base
+        basef[t] = K::COMPACT ? tile.w[PF][t + K::GN] : 0xFFFFFFFFu;
+        baser[t] = K::COMPACT ? tile.w[PR][t + K::GN] : 0xFFFFFFFFu;
+    }
+    JointWalk<K> jw;
+    for (uint32_t k = 0; k < nb; ++k) {
+        cu32p prog = (cu32p)(a.programs + (size_t)(k0 + k) * (2 * K::PDW));
+        uint32_t m[K::PDW];
+#pragma unroll
+        for (int i = 0; i < K::PDW; ++i) m[i] = prog[i];
+        jw.walk(m, tile, basef, baser);
+        uint32_t n_mod = 0, n_non = 0;
+#pragma unroll
+        for (int t = 0; t < T_WORDS; ++t) {
+            if (K::COMPACT) {
+                const uint32_t sites = jw.accf[t] | jw.accr[t];  // forward sites sit on the canonical base, reverse on its complement
+                n_mod += __popc(sites & sw[0][t]);
+                n_non += __popc(sites & sw[1][t]);
+            } else {
+                n_mod += __popc(jw.accf[t] & sw[0][t]) + __popc(jw.accr[t] & sw[K::COMPACT ? 0 : 2][t]);
+                n_non += __popc(jw.accf[t] & sw[1][t]) + __popc(jw.accr[t] & sw[K::COMPACT ? 1 : 3][t]);
+            }
+        }
+        emit_counts<K>(a, n_mod, n_non, k0, k, lds_acc, lds_row0, lane, contig_rank);
+    }
+}
+
 // One slot's candidates [k0, k0 + nb) against the tile this wave holds: match masks, site counts, per-lane counts into
 // LDS rows k * NS + lds_row0 (lds_row0 = the slot's index in the workgroup).  CAN: canonical base of the slot, 0 = A (reverse-strand sites sit on T), 1 = C (reverse on G).
 // common != ~0u: program index of the constraints shared by all nb candidates (their own programs hold the rest).
@@ -155,6 +217,10 @@ template <class K, int CAN>
 __device__ __forceinline__ void score_candidates(const ScoreArgs &a, const Tile<K> &tile, const uint32_t (&sw)[K::NST][T_WORDS],
                                                  uint32_t k0, uint32_t nb, uint32_t common, bool siblings, uint32_t *lds_acc,
                                                  uint32_t lds_row0, int lane, uint32_t contig_rank = 0) {
+    if constexpr (!K::CF) {
+        score_heavy<K, CAN>(a, tile, sw, k0, nb, lds_acc, lds_row0, lane, contig_rank);
+        return;
+    }
     constexpr int PF = CAN == 0 ? 0 : 1;   // plane of the canonical base: A or C
     constexpr int PR = CAN == 0 ? 3 : 2;   // plane of its complement:     T or G
     uint32_t basef[T_WORDS], baser[T_WORDS];
@@ -165,7 +231,7 @@ __device__ __forceinline__ void score_candidates(const ScoreArgs &a, const Tile<
         basef[t] = K::COMPACT ? tile.w[PF][t + K::GN] : 0xFFFFFFFFu;
         baser[t] = K::COMPACT ? tile.w[PR][t + K::GN] : 0xFFFFFFFFu;
     }
-    if (K::CF && common != 0xFFFFFFFFu) {                                    // wave-uniform
+    if (common != 0xFFFFFFFFu) {                                             // wave-uniform
         cu32p prog = (cu32p)(a.programs + (size_t)common * (2 * K::PDW));
         eval_strand<K>(prog, tile, basef);
         eval_strand<K>(prog + K::PDW, tile, baser);
@@ -175,7 +241,7 @@ __device__ __forceinline__ void score_candidates(const ScoreArgs &a, const Tile<
     // two sets of SGPRs like before, but a load's latency hides behind ~40 vector instructions instead of standing in
     // front of every strand.
     uint32_t mf[K::PDW], mr[K::PDW];
-    if (!(K::CF && siblings)) {
+    if (!siblings) {
         cu32p prog = (cu32p)(a.programs + (size_t)k0 * (2 * K::PDW));
 #pragma unroll
         for (int i = 0; i < K::PDW; ++i) mf[i] = prog[i];
@@ -183,7 +249,7 @@ __device__ __forceinline__ void score_candidates(const ScoreArgs &a, const Tile<
     for (uint32_t k = 0; k < nb; ++k) {
         cu32p prog = (cu32p)(a.programs + (size_t)(k0 + k) * (2 * K::PDW));
         uint32_t accf[T_WORDS], accr[T_WORDS];
-        if (K::CF && siblings) {                                             // wave-uniform: one constraint per strand left
+        if (siblings) {                                                      // wave-uniform: one constraint per strand left
             const uint32_t df = prog[0], dr = prog[1];
             apply_single<K>(df >> 5, df & 31u, tile, basef, accf);
             apply_single<K>(dr >> 5, dr & 31u, tile, baser, accr);
@@ -212,23 +278,7 @@ __device__ __forceinline__ void score_candidates(const ScoreArgs &a, const Tile<
                 n_non += __popc(accf[t] & sw[1][t]) + __popc(accr[t] & sw[K::COMPACT ? 1 : 3][t]);
             }
         }
-        if (K::PC) {
-            // per-contig counters (motif_model_contig per contig, find_motifs_bin.py:1285-1331): a chunk lies inside ONE
-            // contig, so the wave's sum goes straight to that (candidate, contig) row
-#pragma unroll
-            for (int o = 32; o; o >>= 1) {
-                n_mod += __shfl_xor(n_mod, o);
-                n_non += __shfl_xor(n_non, o);
-            }
-            if (lane == 0 && (n_mod | n_non)) {
-                unsigned long long *row = a.out + (a.row_base[k0 + k] + contig_rank) * 2;
-                if (n_mod) atomicAdd(row, (unsigned long long)n_mod);
-                if (n_non) atomicAdd(row + 1, (unsigned long long)n_non);
-            }
-            continue;
-        }
-        atomicAdd(&lds_acc[((k * K::NS + lds_row0) * 2 + 0) * 64 + lane], n_mod);
-        atomicAdd(&lds_acc[((k * K::NS + lds_row0) * 2 + 1) * 64 + lane], n_non);
+        emit_counts<K>(a, n_mod, n_non, k0, k, lds_acc, lds_row0, lane, contig_rank);
     }
 }
 

@@ -130,6 +130,57 @@ __device__ __forceinline__ void eval_masks(const uint32_t (&m)[K::PDW], const Ti
     }
 }
 
+// ---- both strands of a heavy candidate from its FORWARD masks (score_candidates, non-CF variants) -------------------
+// compile_one writes the reverse half as the mirror of the forward one: a forward constraint on plane p at offset
+// d = 32 (g - GN) + r is a reverse constraint on the complemented plane at -d, i.e. word-group 2 GN - 1 - g, shift 32 - r
+// for r > 0, and word-group 2 GN - g, shift 0 for r = 0 (no d = -32 GN: the host sends no offset that far to the variant).
+// So one scalar walk over the forward words drives both strands, and the reverse half is not read.
+constexpr int comp_plane(int p) { return (p & 4) | (3 - (p & 3)); }   // A<->T, C<->G, not-A<->not-T, not-C<->not-G
+
+template <class K>
+struct JointWalk {
+    uint32_t accf[T_WORDS], accr[T_WORDS];                 // the match masks once walk() returns
+
+    // r = 0 can reach word-group G unless it is d = -32 GN (beyond every variant's reach) or the modified position of a
+    // compact batch (folded into the base)
+    template <int G>
+    static constexpr bool r0_possible() { return G > 0 && !(K::COMPACT && G == K::GN); }
+
+    // acc &= the words of constraint bit r of forward mask word I shifted into place, both strands (R0: the bit-0
+    // constraint of a word whose reverse twin sits one word-group further, unshifted)
+    template <int I, bool R0 = false>
+    __device__ __forceinline__ void and_in(const Tile<K> &tile, uint32_t r) {
+        constexpr int G = I / K::NP, P = I % K::NP, CP = comp_plane(P), GR = R0 ? 2 * K::GN - G : 2 * K::GN - 1 - G;
+        const uint32_t rr = R0 ? 0u : 32u - r;
+#pragma unroll
+        for (int t = 0; t < T_WORDS; ++t) accf[t] &= alignbit(tile.w[P][t + G + 1], tile.w[P][t + G], r);
+#pragma unroll
+        for (int t = 0; t < T_WORDS; ++t) accr[t] &= alignbit(tile.w[CP][t + GR + 1], tile.w[CP][t + GR], rr);
+    }
+    // acc = base, then every constraint of the forward masks m: four v_alignbit + four v_and per strand, one s_ff1 walk.
+    template <int I = 0>
+    __device__ __forceinline__ void walk(const uint32_t (&m)[K::PDW], const Tile<K> &tile, const uint32_t (&bf)[T_WORDS],
+                                         const uint32_t (&br)[T_WORDS]) {
+        if constexpr (I == 0) {
+#pragma unroll
+            for (int t = 0; t < T_WORDS; ++t) { accf[t] = bf[t]; accr[t] = br[t]; }
+        }
+        if constexpr (I < K::PDW) {
+            uint32_t mm = m[I];
+            if (r0_possible<I / K::NP>() && (mm & 1u)) {   // wave-uniform
+                mm &= ~1u;
+                and_in<I, true>(tile, 0u);
+            }
+            while (mm) {                                   // wave-uniform
+                const uint32_t r = __builtin_ctz(mm);
+                mm &= mm - 1;
+                and_in<I>(tile, r);
+            }
+            walk<I + 1>(m, tile, bf, br);
+        }
+    }
+};
+
 template <class K>
 __device__ __forceinline__ void eval_strand(cu32p prog, const Tile<K> &tile, uint32_t (&acc)[T_WORDS]) {
     uint32_t m[K::PDW];
