@@ -335,6 +335,56 @@ int nm_score_batch_per_contig(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand
 /* resident contigs of a bin (nm_upload_contigs indices) in the order of the per-contig rows */
 int nm_bin_contigs(nm_ctx *ctx, uint32_t bin, uint32_t *contig_ids, uint32_t capacity, uint32_t *n_contigs);
 
+/* ---- per-SITE export of a batch of candidates: where every motif occurs and in which state the occurrence is ------------
+ * Reference: motif_model_contig(..., save_motif_positions=True) (find_motifs_bin.py:1285-1331) returns, for ONE motif on ONE
+ * contig, index_meth_fwd / index_nonmeth_fwd / index_meth_rev / index_nonmeth_rev — the occurrences subseq_indices
+ * (utils.py:44-67) finds, shifted to the modified base and intersected with the methylated / unmethylated pileup rows.
+ * nm_hit_positions is that call; these two serve a whole BATCH (candidates as for nm_score_batch_per_contig) over every
+ * resident contig of each candidate's bin and both strands, in a number of launches that does not depend on the batch.
+ * The occurrences that carry no call (no pileup row kept, fraction between the thresholds) are a third state the reference
+ * has no array for.
+ *
+ * A record = (contig id as in nm_upload_contigs, contig-local 0-based position of the MODIFIED base, code);
+ * code = strand (NM_SITES_MINUS for '-') | state (0 methylated, 1 unmethylated, 2 no call).  Positions and the two called
+ * states are nm_hit_positions' which = 0..3; no call = the stripped motif (its reverse complement on '-') lies wholly inside
+ * the contig with its modified base here and the state planes of the mod slot hold neither call for the strand.
+ * ORDER (part of the contract): candidate-major; within a candidate the contigs in nm_bin_contigs order; within a contig
+ * ascending position; at equal position '+' before '-'.  state_set: which states are exported (NM_SITES_MOD | NM_SITES_NOMOD |
+ * NM_SITES_NOCALL).  A candidate reaching further than [-96, 95] from its modified base fails as in nm_hit_positions.
+ *
+ * nm_motif_sites_count: the count pass alone.  contig_counts = int64[row_offset[n_cand]][6] in the row layout of
+ *   nm_score_batch_per_contig: (fwd mod, fwd nomod, fwd nocall, rev mod, rev nomod, rev nocall) per (candidate, contig), all six
+ *   whatever state_set says; cand_total[k] = records candidate k has under state_set.
+ * nm_motif_sites: count + prefix + fill.  cand_offset[n_cand + 1] = rank of every candidate's first record in the batch's
+ *   order (cand_offset[n_cand] = all records of the batch).  Written are exactly the records whose rank lies in
+ *   [first_record, first_record + capacity), to site_*[rank - first_record]; *n_written says how many that were (0 for a window
+ *   past the end).  A batch larger than the caller's buffers is exported window by window; nothing is truncated silently.
+ * NM_ESTATE without an assembly or without a pileup in a candidate's slot, NM_EINVAL for NULLs / a bad bin / an empty state_set. */
+#define NM_SITES_MOD 1u
+#define NM_SITES_NOMOD 2u
+#define NM_SITES_NOCALL 4u
+#define NM_SITES_MINUS 4u     /* strand bit of a record's code: code = strand bit | state, state 0 / 1 / 2 */
+int nm_motif_sites_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot,
+                         const uint8_t *cand_len, const uint8_t *cand_modpos, const uint32_t *cand_mask_offset,
+                         const uint8_t *cand_masks, uint32_t state_set, const uint64_t *row_offset, uint64_t *cand_total,
+                         int64_t *contig_counts);
+int nm_motif_sites(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot,
+                   const uint8_t *cand_len, const uint8_t *cand_modpos, const uint32_t *cand_mask_offset,
+                   const uint8_t *cand_masks, uint32_t state_set, uint64_t first_record, uint64_t capacity,
+                   uint32_t *site_contig, uint32_t *site_pos, uint8_t *site_code, uint64_t *cand_offset, uint64_t *n_written);
+/* The records of a span as the lines of motif-sites.bed (host code, no device needed; the reference writes no such file — the
+ * arrays of find_motifs_bin.py:1322-1329 stay in memory there):
+ *   contig \t start \t start + 1 \t name \t 0 \t strand \t state \t bin \n      state = mod / nomod / nocall
+ * The span is cut into n_seg runs of records that share name and bin (one candidate each): run s = records
+ * [seg_begin[s], seg_begin[s + 1]), its name = seg_text[seg_text_off[2 s] .. [2 s + 1]), its bin = [2 s + 1] .. [2 s + 2]);
+ * contig i's name = contig_text[contig_text_off[i] .. [i + 1]).  out == NULL: only *n_bytes (the exact size); else the text is
+ * written when capacity holds it (NM_ERANGE otherwise).  Runs on up to NM_POST_THREADS threads (default: half the cores), at most
+ * 16; the bytes do not depend on the number of threads. */
+int nm_motif_sites_text(uint64_t n_records, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code,
+                        uint32_t n_seg, const uint64_t *seg_begin, const char *seg_text, const uint64_t *seg_text_off,
+                        uint32_t n_contigs, const char *contig_text, const uint64_t *contig_text_off, char *out,
+                        uint64_t capacity, uint64_t *n_bytes);
+
 /* ---- per-contig READ methylation of motifs: the table binnary starts from -------------------------
  * Reference: nanomotif/main.py:142-193 — `contig_methylation = methylation_pattern(pileup, assembly, motifs,
  * min_valid_read_coverage, min_valid_cov_to_diff_fraction = 0.8, output_type = Median | WeightedMean)` from the

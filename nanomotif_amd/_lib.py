@@ -21,6 +21,7 @@ SYMBOLS = [
     "nm_score_batch_per_contig", "nm_bin_contigs", "nm_readstats_upload", "nm_contig_methylation", "nm_bed_open_counts", "nm_bed_count_columns", "nm_bed_parse_device", "nm_bed_parse_device_indexed", "nm_bedcols_shape", "nm_bedcols_contig_name", "nm_bedcols_mod_code", "nm_bedcols_runs", "nm_bedcols_map_contigs", "nm_bedcols_device_columns", "nm_bedcols_close", "nm_device_read", "nm_score_batch_begin", "nm_score_batch_end", "nm_win_batch_w_begin", "nm_win_batch_w_end", "nm_search_run", "nm_search_run_custom", "nm_search_result_sizes", "nm_search_result_speculation", "nm_search_result_export", "nm_search_result_gml", "nm_search_result_free", "nm_post_run", "nm_post_run_custom", "nm_post_run_rows_custom", "nm_post_sizes", "nm_post_export", "nm_post_tables", "nm_post_free", "nm_psi_posint",
     "nm_bedcols_phase_seconds", "nm_bed_plan_indexed", "nm_bed_parse_device_planned", "nm_bedplan_close", "nm_fasta_parse_device", "nm_fastadev_shape", "nm_fastadev_record", "nm_fastadev_table", "nm_fastadev_sequence_device", "nm_upload_contigs_fasta", "nm_fastadev_close",
     "nm_tabix_regions", "nm_bed_parse_device_counts", "nm_bedcols_count_columns", "nm_readstats_upload_bedcols",
+    "nm_motif_sites_count", "nm_motif_sites", "nm_motif_sites_text",
 ]
 
 class SearchParams(C.Structure):
@@ -137,6 +138,10 @@ def _load_locked():
     lib.nm_win_batch_w_end.argtypes = [p, C.POINTER(C.c_int32)]
     lib.nm_score_batch_per_contig.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, u64p, i64p]
     lib.nm_bin_contigs.argtypes = [p, C.c_uint32, u32p, C.c_uint32, u32p]
+    lib.nm_motif_sites_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, u64p, i64p]
+    lib.nm_motif_sites.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, u8p, u64p, u64p]
+    lib.nm_motif_sites_text.argtypes = [C.c_uint64, u32p, u32p, u8p, C.c_uint32, u64p, C.c_char_p, u64p, C.c_uint32, C.c_char_p, u64p, p,
+                                        C.c_uint64, u64p]
     lib.nm_readstats_upload.argtypes = [p, C.c_uint32, C.c_uint64, p, p, p, p, p, p, C.c_int32, C.c_double, C.c_int, u64p]
     lib.nm_contig_methylation.argtypes = [p, C.c_uint32, u8p, u8p, u8p, u32p, u8p, u32p, f64p, f64p, f64p]
     lib.nm_bed_open_counts.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(p)]

@@ -12,7 +12,7 @@ def create_parser():
                                      formatter_class=formatter)
     parser.add_argument("--version", action="version", version="%(prog)s {}".format(__version__))
     sub = parser.add_subparsers(help="-- Command descriptions --", dest="command", title="commands",
-                                metavar="{motif_discovery, detect_contamination, include_contigs, check_installation}")
+                                metavar="{motif_discovery, motif_sites, detect_contamination, include_contigs, check_installation}")
     p = sub.add_parser("motif_discovery", help="Finds motifs directly on bin level in provided assembly", add_help=False)
     p.add_argument("assembly", type=str, help="path to the assembly file.")
     p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
@@ -49,9 +49,51 @@ def create_parser():
     gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
     gen.add_argument("--seed", type=int, default=1, help="Seed for random number generator. Default: %(default)s")
     gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
+    add_motif_sites_parser(sub)
     add_binnary_parsers(sub)
     sub.add_parser("check_installation", help="Run motif_discovery on a small synthetic data set", add_help=True)
     return parser
+
+
+def _states(text):
+    from .engine import SITE_STATES
+    asked = [s.strip() for s in text.split(",") if s.strip()]
+    if not asked or any(s not in SITE_STATES for s in asked):
+        raise argparse.ArgumentTypeError(f"a comma-separated selection of {', '.join(SITE_STATES)} is expected, got {text!r}")
+    return tuple(s for s in SITE_STATES if s in asked)
+
+
+def add_motif_sites_parser(sub):
+    """motif_sites: the per-site view of a bin-motifs.tsv (no counterpart on the reference's command line; the data are what
+    motif_model_contig(save_motif_positions=True) returns, find_motifs_bin.py:1285-1331).  Assembly, pileup, bins, thresholds and
+    device are spelled as for motif_discovery: the pileup is ingested the same way."""
+    p = sub.add_parser("motif_sites", help="Exports where the motifs of a bin-motifs.tsv occur and which occurrences are methylated", add_help=False)
+    p.add_argument("assembly", type=str, help="path to the assembly file.")
+    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
+    gm = p.add_argument_group("contig bin arguments, use one of:")
+    g = gm.add_mutually_exclusive_group(required=True)
+    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
+    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
+    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
+    gm.add_argument("--extension", type=str, default=".fasta",
+                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
+    o = p.add_argument_group("Options")
+    o.add_argument("--bin_motifs", type=str, required=True, help="Path to the bin-motifs.tsv whose motifs are exported (motif_discovery's output)")
+    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
+    o.add_argument("--states", type=_states, default=("mod", "nomod", "nocall"),
+                   help="Comma-separated states of the occurrences to export: mod, nomod, nocall. Default: all three")
+    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
+                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
+    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
+                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
+    o.add_argument("--threshold_valid_coverage", type=int, default=5,
+                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
+    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
+    gen = p.add_argument_group("general arguments")
+    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
+    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
+    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
+    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
 
 
 def add_binnary_parsers(sub):

@@ -1,0 +1,131 @@
+// nm_motif_sites_text — the records of nm_motif_sites as the lines of motif-sites.bed, on a few host threads.
+// The reference keeps the four position arrays of motif_model_contig(save_motif_positions=True) in memory
+// (find_motifs_bin.py:1322-1329) and writes no per-site file; the line format is this project's (README.md).
+// Two passes over the span: every thread sizes its share of the records exactly, the shares' offsets are a prefix sum, then every
+// thread formats its share in place — the bytes are the same for any number of threads.
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "../../include/nmscan.h"
+
+int nm_set_error(int code, const char *fmt, ...);
+
+namespace {
+
+inline unsigned digits(uint64_t v) {
+    unsigned n = 1;
+    while (v >= 10) { v /= 10; ++n; }
+    return n;
+}
+
+inline char *put_u64(char *p, uint64_t v) {
+    const unsigned n = digits(v);
+    for (unsigned i = n; i-- > 0;) { p[i] = (char)('0' + v % 10); v /= 10; }
+    return p + n;
+}
+
+const char *const STATE_TEXT[3] = {"mod", "nomod", "nocall"};
+const unsigned STATE_LEN[3] = {3, 5, 6};
+
+struct Span {
+    const uint32_t *contig, *pos;
+    const uint8_t *code;
+    uint32_t n_seg;
+    const uint64_t *seg_begin, *seg_text_off, *contig_text_off;
+    const char *seg_text, *contig_text;
+    // segment that holds record i (the last one whose begin is <= i; empty segments are passed over)
+    uint32_t seg_of(uint64_t i) const { return (uint32_t)(std::upper_bound(seg_begin, seg_begin + n_seg + 1, i) - seg_begin) - 1; }
+};
+
+// bytes of the records [lo, hi), or their text at `out` (returns its end)
+uint64_t size_range(const Span &s, uint64_t lo, uint64_t hi) {
+    uint64_t bytes = 0;
+    uint32_t seg = lo < hi ? s.seg_of(lo) : 0;
+    for (uint64_t i = lo; i < hi; ++i) {
+        while (i >= s.seg_begin[seg + 1]) ++seg;
+        const uint64_t fixed = (s.seg_text_off[2 * seg + 2] - s.seg_text_off[2 * seg]) + 9;      // name + bin + 7 tabs + "0" + newline
+        const uint32_t c = s.contig[i];
+        const uint64_t p = s.pos[i];
+        bytes += (s.contig_text_off[c + 1] - s.contig_text_off[c]) + digits(p) + digits(p + 1) + 1 + STATE_LEN[s.code[i] & 3u] + fixed;
+    }
+    return bytes;
+}
+
+char *write_range(const Span &s, uint64_t lo, uint64_t hi, char *out) {
+    uint32_t seg = lo < hi ? s.seg_of(lo) : 0;
+    for (uint64_t i = lo; i < hi; ++i) {
+        while (i >= s.seg_begin[seg + 1]) ++seg;
+        const uint32_t c = s.contig[i];
+        const uint64_t p = s.pos[i];
+        const uint64_t cl = s.contig_text_off[c + 1] - s.contig_text_off[c];
+        memcpy(out, s.contig_text + s.contig_text_off[c], cl);
+        out += cl;
+        *out++ = '\t';
+        out = put_u64(out, p);
+        *out++ = '\t';
+        out = put_u64(out, p + 1);
+        *out++ = '\t';
+        const uint64_t nl = s.seg_text_off[2 * seg + 1] - s.seg_text_off[2 * seg];
+        memcpy(out, s.seg_text + s.seg_text_off[2 * seg], nl);
+        out += nl;
+        memcpy(out, "\t0\t", 3);
+        out += 3;
+        *out++ = (s.code[i] & NM_SITES_MINUS) ? '-' : '+';
+        *out++ = '\t';
+        const unsigned st = s.code[i] & 3u;
+        memcpy(out, STATE_TEXT[st], STATE_LEN[st]);
+        out += STATE_LEN[st];
+        *out++ = '\t';
+        const uint64_t bl = s.seg_text_off[2 * seg + 2] - s.seg_text_off[2 * seg + 1];
+        memcpy(out, s.seg_text + s.seg_text_off[2 * seg + 1], bl);
+        out += bl;
+        *out++ = '\n';
+    }
+    return out;
+}
+
+}  // namespace
+
+extern "C" int nm_motif_sites_text(uint64_t n, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code, uint32_t n_seg,
+                                   const uint64_t *seg_begin, const char *seg_text, const uint64_t *seg_text_off, uint32_t n_contigs,
+                                   const char *contig_text, const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes) {
+    if (!n_bytes) return nm_set_error(NM_EINVAL, "NULL argument");
+    *n_bytes = 0;
+    if (n == 0) return NM_OK;
+    if (!site_contig || !site_pos || !site_code || !seg_begin || !seg_text || !seg_text_off || !contig_text || !contig_text_off)
+        return nm_set_error(NM_EINVAL, "NULL argument");
+    if (n_seg == 0 || seg_begin[0] != 0 || seg_begin[n_seg] != n) return nm_set_error(NM_EINVAL, "the runs must cover the %llu records exactly", (unsigned long long)n);
+    for (uint32_t s = 0; s < n_seg; ++s)
+        if (seg_begin[s + 1] < seg_begin[s]) return nm_set_error(NM_EINVAL, "seg_begin is not ascending at run %u", s);
+    unsigned n_thr = std::max(1u, std::min(16u, std::thread::hardware_concurrency() / 2));
+    if (const char *e = getenv("NM_POST_THREADS")) n_thr = (unsigned)std::max(1, std::min(16, atoi(e)));
+    n_thr = (unsigned)std::min<uint64_t>(n_thr, (n + 255) / 256);        // (a thread is not worth starting for less)
+    const Span sp{site_contig, site_pos, site_code, n_seg, seg_begin, seg_text_off, contig_text_off, seg_text, contig_text};
+    auto lo_of = [&](unsigned t) { return n * t / n_thr; };
+    std::vector<uint64_t> bytes(n_thr + 1, 0);
+    std::vector<int> bad(n_thr, 0);
+    auto on_threads = [&](auto fn) {
+        std::vector<std::thread> pool;
+        for (unsigned t = 1; t < n_thr; ++t) pool.emplace_back([&, t] { fn(t); });
+        fn(0);
+        for (auto &th : pool) th.join();
+    };
+    on_threads([&](unsigned t) {
+        const uint64_t lo = lo_of(t), hi = lo_of(t + 1);
+        for (uint64_t i = lo; i < hi; ++i)
+            if (site_contig[i] >= n_contigs || (site_code[i] & 3u) == 3u || (site_code[i] & ~7u)) { bad[t] = 1; return; }
+        bytes[t + 1] = size_range(sp, lo, hi);
+    });
+    for (unsigned t = 0; t < n_thr; ++t)
+        if (bad[t]) return nm_set_error(NM_EINVAL, "a record names a contig >= %u or carries a code that is none of the six", n_contigs);
+    for (unsigned t = 0; t < n_thr; ++t) bytes[t + 1] += bytes[t];
+    *n_bytes = bytes[n_thr];
+    if (!out) return NM_OK;
+    if (capacity < bytes[n_thr]) return nm_set_error(NM_ERANGE, "the text takes %llu bytes, the buffer holds %llu", (unsigned long long)bytes[n_thr], (unsigned long long)capacity);
+    on_threads([&](unsigned t) { (void)write_range(sp, lo_of(t), lo_of(t + 1), out + bytes[t]); });
+    return NM_OK;
+}

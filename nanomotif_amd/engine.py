@@ -21,6 +21,32 @@ def _ptr(arr, ctype):
     return arr.ctypes.data_as(C.POINTER(ctype))
 
 
+SITE_STATES = ("mod", "nomod", "nocall")       # include/nmscan.h: NM_SITES_MOD / NM_SITES_NOMOD / NM_SITES_NOCALL, the state of a record's code
+SITE_MINUS = 4                                 # NM_SITES_MINUS: the strand bit of a record's code
+SITE_RECORD_BYTES = 9                          # a record on the device: contig (4), position (4), code (1)
+SITE_BUDGET_BYTES = 256 << 20                  # default size of one batch of records (ScanEngine.motif_sites)
+SITE_DTYPE = np.dtype([("candidate", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])
+
+
+def site_state_set(states) -> int:
+    """("mod", "nocall") -> the state_set bits of nm_motif_sites."""
+    states = tuple(states)
+    bad = [s for s in states if s not in SITE_STATES]
+    if bad or not states:
+        raise ValueError(f"states must be a non-empty selection of {SITE_STATES}, got {states!r}")
+    return sum(1 << SITE_STATES.index(s) for s in set(states))
+
+
+class SiteBatch:
+    """One delivery of ``ScanEngine.motif_sites``: the records [first_record, first_record + len(records)) of the candidates
+    [first_candidate, first_candidate + n_candidates), which hold ``batch_records`` in all; ``counts`` (first delivery of a group of
+    candidates only, else None): per candidate (contig names, int64[n_contigs, 6]) as ``motif_site_counts`` returns."""
+
+    def __init__(self, first_candidate, n_candidates, first_record, batch_records, records, counts):
+        self.first_candidate, self.n_candidates, self.first_record, self.batch_records = first_candidate, n_candidates, first_record, batch_records
+        self.records, self.counts = records, counts
+
+
 class CandidateBatch:
     """Flat SoA form of a list of candidates (include/nmscan.h: nm_score_batch arguments)."""
 
@@ -790,6 +816,75 @@ class ScanEngine:
         if len(b):
             _lib.check(self.lib.nm_score_batch_per_contig(self.ctx, *self._batch_args(b), _ptr(rows, C.c_uint64), _ptr(out, C.c_int64)))
         return [(names[int(b.bins[k])], out[int(rows[k]):int(rows[k + 1])]) for k in range(len(b))]
+
+    # ------------------------------------------------------------------ per-site export (nm_motif_sites*)
+    def _site_rows(self, b: CandidateBatch):
+        names = {int(bid): self.bin_contigs(int(bid)) for bid in np.unique(b.bins).tolist()}
+        rows = np.zeros(len(b) + 1, dtype=np.uint64)
+        np.cumsum([len(names[int(x)]) for x in b.bins], out=rows[1:])
+        return names, rows
+
+    def _site_counts(self, b: CandidateBatch, state_set: int):
+        names, rows = self._site_rows(b)
+        table = np.zeros((max(int(rows[-1]), 1), 6), dtype=np.int64)
+        totals = np.zeros(max(len(b), 1), dtype=np.uint64)
+        if len(b):
+            _lib.check(self.lib.nm_motif_sites_count(self.ctx, *self._batch_args(b), int(state_set), _ptr(rows, C.c_uint64),
+                                                     _ptr(totals, C.c_uint64), _ptr(table, C.c_int64)))
+        return names, rows, totals[:len(b)], table[:int(rows[-1])]
+
+    def motif_site_counts(self, candidates):
+        """Per (candidate, contig) the six site counts (fwd mod, fwd nomod, fwd nocall, rev mod, rev nomod, rev nocall) of every
+        resident contig of the candidate's bin (nm_motif_sites_count): ``score_per_contig`` split by strand, plus the occurrences
+        that carry no call.  Returns a list, per candidate, of (contig names, int64[n_contigs, 6])."""
+        b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(candidates)
+        names, rows, _, table = self._site_counts(b, 7)
+        return [(names[int(b.bins[k])], table[int(rows[k]):int(rows[k + 1])]) for k in range(len(b))]
+
+    def motif_sites(self, candidates, states=SITE_STATES, max_records=None):
+        """Generator over the sites of ``candidates`` (sequence of (Motif, mod_type, bin), or a CandidateBatch): what
+        ``motif_model_contig(..., save_motif_positions=True)`` returns per motif and contig (find_motifs_bin.py:1285-1331), for the
+        whole list, plus the occurrences without a call.  Yields ``SiteBatch`` objects in candidate order; their ``records``
+        (fields candidate, contig, pos, code; code = 4 for the '-' strand | 0 mod / 1 nomod / 2 nocall) concatenated are the sites
+        in the order candidate, contig (``bin_contigs`` order), position, '+' before '-'.  No batch holds more than ``max_records``
+        records (default: ``SITE_BUDGET_BYTES`` = 256 MiB of device records, 9 bytes each); a candidate with more is delivered in
+        several windows.  The concatenation does not depend on ``max_records``."""
+        b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(candidates)
+        state_set = site_state_set(states)
+        limit = SITE_BUDGET_BYTES // SITE_RECORD_BYTES if max_records is None else int(max_records)
+        if limit < 1:
+            raise ValueError("max_records must be at least 1")
+        names, rows, totals, table = self._site_counts(b, state_set)
+        totals = totals.astype(np.int64)
+        n, k = len(b), 0
+        while k < n:
+            e, held = k + 1, int(totals[k])
+            while e < n and held + int(totals[e]) <= limit:
+                held += int(totals[e])
+                e += 1
+            sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
+            counts = [(names[int(b.bins[j])], table[int(rows[j]):int(rows[j + 1])]) for j in range(k, e)]
+            first = 0
+            while True:                                    # one window, unless a single candidate exceeds the limit
+                cap = min(limit, held - first) if held else 0
+                rec = np.zeros(cap, dtype=SITE_DTYPE)
+                contig, pos, code = (np.zeros(max(cap, 1), dtype=t) for t in (np.uint32, np.uint32, np.uint8))
+                off = np.zeros(e - k + 1, dtype=np.uint64)
+                written = C.c_uint64(0)
+                _lib.check(self.lib.nm_motif_sites(self.ctx, *self._batch_args(sub), state_set, first, cap, _ptr(contig, C.c_uint32),
+                                                   _ptr(pos, C.c_uint32), _ptr(code, C.c_uint8), _ptr(off, C.c_uint64), C.byref(written)))
+                if int(off[-1]) != held or written.value != cap:
+                    raise _lib.NmScanError(f"nm_motif_sites delivered {written.value} of {cap} records ({int(off[-1])} in the batch, {held} counted)")
+                rec["contig"], rec["pos"], rec["code"] = contig[:cap], pos[:cap], code[:cap]
+                # the candidate of every record of the window: the prefix of the batch, cut to [first, first + cap)
+                cut = np.clip(off.astype(np.int64) - first, 0, cap)
+                rec["candidate"] = np.repeat(np.arange(k, e, dtype=np.uint32), np.diff(cut))
+                yield SiteBatch(first_candidate=k, n_candidates=e - k, first_record=first, batch_records=held, records=rec,
+                                counts=counts if first == 0 else None)
+                first += cap
+                if first >= held:
+                    break
+            k = e
 
     def set_score_lanes(self, lanes: int):
         """2: consecutive ``score_into_device`` calls alternate between two streams, so that independent batches

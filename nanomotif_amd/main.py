@@ -611,6 +611,20 @@ def main(argv=None):
         if result is None and rank == 0:
             with open(os.path.join(args.out, "bin-motifs.tsv"), "w") as f:     # main.py:317-321
                 f.write(HEADER)
+    elif args.command == "motif_sites":
+        from . import motif_sites
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+            sys.stderr.write("nanomotif motif_sites runs on one GPU: start it without a multi-rank launcher\n")
+            sys.exit(2)
+        shared_setup(args, args.out)
+        status = motif_sites.run(args)
+        try:
+            with open(os.path.join(args.out, "logs", "timings.motif_sites.json"), "w") as f:
+                json.dump(motif_sites.TIMINGS, f, indent=1)
+        except OSError:
+            pass
+        if status:
+            sys.exit(status)
     elif args.command in ("detect_contamination", "include_contigs"):
         args.verbose = False                     # main.py:310-312: binnary runs with seed 1
         args.seed = 1
