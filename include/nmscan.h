@@ -385,6 +385,43 @@ int nm_motif_sites_text(uint64_t n_records, const uint32_t *site_contig, const u
                         uint32_t n_contigs, const char *contig_text, const uint64_t *contig_text_off, char *out,
                         uint64_t capacity, uint64_t *n_bytes);
 
+/* ---- COVERAGE of a bin's methylation by a SET of motifs: how much the motifs of a bin-motifs.tsv explain ------------------
+ * Reference: find_best_candidates logs "x % of sequences remaining" while it removes the windows each kept motif explains
+ * (find_motifs_bin.py:801-823, the remaining_sequences_threshold stop) — a log line taken before pruning, before the missed
+ * candidates are added and before the merge stage; nothing of it is written to a file.  These two exports answer the question
+ * for any list of motifs, on the resident state planes.
+ *
+ * A SET s = (set_bin[s], set_mod_slot[s], candidates [set_cand_offset[s], set_cand_offset[s + 1])); the candidate arrays are
+ * those of nm_motif_sites (all candidates of a set share its bin and slot); a set may be empty and n_sets may be 0.
+ * Candidate j COVERS (contig, position, strand) iff nm_motif_sites with all three states writes a record for j there (same
+ * occurrence rule, [-96, 95] reach limit, contig ends, non-ACGT letters).  cover = OR over the set's candidates, once =
+ * covered by exactly one of them.  M / U = the methylated / unmethylated calls of the slot as nm_motif_sites reads them.
+ *
+ * nm_motif_coverage_count: set_counts = int64[set_row_offset[n_sets]][10], one row per (set, resident contig of its bin in
+ *   nm_bin_contigs order): forward strand (mod_total |M|, mod_explained |M & cover|, nomod_total |U|, nomod_covered
+ *   |U & cover|, nocall_covered |cover & ~(M | U)|), then the same five for the reverse strand.  cand_counts =
+ *   int64[cand_row_offset[n_cand]][4], one row per (candidate, contig): (fwd mod, fwd nomod, rev mod, rev nomod) of the
+ *   positions the candidate covers AND once holds — a motif listed twice in a set has 0 in both copies.  set_total[s] =
+ *   unexplained records of set s = sum of mod_total - mod_explained.  Both offset arrays start at 0, ascend, and give every
+ *   set / candidate at least as many rows as its bin has resident contigs.
+ * nm_motif_coverage_sites: the UNEXPLAINED records, every (contig, position, strand) in M & ~cover.  ORDER (part of the
+ *   contract): set-major; contigs in nm_bin_contigs order; ascending position; '+' before '-'.  code = NM_SITES_MINUS for '-',
+ *   else 0.  set_offset[n_sets + 1] = rank of every set's first record (set_offset[n_sets] = all records); windowing by
+ *   first_record / capacity / *n_written exactly as in nm_motif_sites: nothing is truncated silently.
+ * Launches: at most 3 (count, one per width) + scan + gather + 3 (fill) whatever the number of sets and candidates; a set runs at
+ * the width of its widest candidate.
+ * NM_ESTATE without an assembly or without a pileup in a set's slot, NM_EINVAL for NULLs / a bad bin / offsets that do not ascend,
+ * NM_ERANGE for more than 2^32 work items or rows; a candidate beyond the reach limit fails as in nm_motif_sites. */
+int nm_motif_coverage_count(nm_ctx *ctx, uint32_t n_sets, const uint32_t *set_bin, const uint8_t *set_mod_slot,
+                            const uint32_t *set_cand_offset, const uint8_t *cand_len, const uint8_t *cand_modpos,
+                            const uint32_t *cand_mask_offset, const uint8_t *cand_masks, const uint64_t *set_row_offset,
+                            const uint64_t *cand_row_offset, uint64_t *set_total, int64_t *set_counts, int64_t *cand_counts);
+int nm_motif_coverage_sites(nm_ctx *ctx, uint32_t n_sets, const uint32_t *set_bin, const uint8_t *set_mod_slot,
+                            const uint32_t *set_cand_offset, const uint8_t *cand_len, const uint8_t *cand_modpos,
+                            const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint64_t first_record, uint64_t capacity,
+                            uint32_t *site_contig, uint32_t *site_pos, uint8_t *site_code, uint64_t *set_offset,
+                            uint64_t *n_written);
+
 /* ---- per-contig READ methylation of motifs: the table binnary starts from -------------------------
  * Reference: nanomotif/main.py:142-193 — `contig_methylation = methylation_pattern(pileup, assembly, motifs,
  * min_valid_read_coverage, min_valid_cov_to_diff_fraction = 0.8, output_type = Median | WeightedMean)` from the

@@ -22,6 +22,7 @@ SYMBOLS = [
     "nm_bedcols_phase_seconds", "nm_bed_plan_indexed", "nm_bed_parse_device_planned", "nm_bedplan_close", "nm_fasta_parse_device", "nm_fastadev_shape", "nm_fastadev_record", "nm_fastadev_table", "nm_fastadev_sequence_device", "nm_upload_contigs_fasta", "nm_fastadev_close",
     "nm_tabix_regions", "nm_bed_parse_device_counts", "nm_bedcols_count_columns", "nm_readstats_upload_bedcols",
     "nm_motif_sites_count", "nm_motif_sites", "nm_motif_sites_text",
+    "nm_motif_coverage_count", "nm_motif_coverage_sites",
 ]
 
 class SearchParams(C.Structure):
@@ -140,6 +141,8 @@ def _load_locked():
     lib.nm_bin_contigs.argtypes = [p, C.c_uint32, u32p, C.c_uint32, u32p]
     lib.nm_motif_sites_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, u64p, i64p]
     lib.nm_motif_sites.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, u8p, u64p, u64p]
+    lib.nm_motif_coverage_count.argtypes = [p, C.c_uint32, u32p, u8p, u32p, u8p, u8p, u32p, u8p, u64p, u64p, u64p, i64p, i64p]
+    lib.nm_motif_coverage_sites.argtypes = [p, C.c_uint32, u32p, u8p, u32p, u8p, u8p, u32p, u8p, C.c_uint64, C.c_uint64, u32p, u32p, u8p, u64p, u64p]
     lib.nm_motif_sites_text.argtypes = [C.c_uint64, u32p, u32p, u8p, C.c_uint32, u64p, C.c_char_p, u64p, C.c_uint32, C.c_char_p, u64p, p,
                                         C.c_uint64, u64p]
     lib.nm_readstats_upload.argtypes = [p, C.c_uint32, C.c_uint64, p, p, p, p, p, p, C.c_int32, C.c_double, C.c_int, u64p]

@@ -12,7 +12,7 @@ def create_parser():
                                      formatter_class=formatter)
     parser.add_argument("--version", action="version", version="%(prog)s {}".format(__version__))
     sub = parser.add_subparsers(help="-- Command descriptions --", dest="command", title="commands",
-                                metavar="{motif_discovery, motif_sites, detect_contamination, include_contigs, check_installation}")
+                                metavar="{motif_discovery, motif_sites, motif_coverage, detect_contamination, include_contigs, check_installation}")
     p = sub.add_parser("motif_discovery", help="Finds motifs directly on bin level in provided assembly", add_help=False)
     p.add_argument("assembly", type=str, help="path to the assembly file.")
     p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
@@ -50,6 +50,7 @@ def create_parser():
     gen.add_argument("--seed", type=int, default=1, help="Seed for random number generator. Default: %(default)s")
     gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
     add_motif_sites_parser(sub)
+    add_motif_coverage_parser(sub)
     add_binnary_parsers(sub)
     sub.add_parser("check_installation", help="Run motif_discovery on a small synthetic data set", add_help=True)
     return parser
@@ -82,6 +83,38 @@ def add_motif_sites_parser(sub):
     o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
     o.add_argument("--states", type=_states, default=("mod", "nomod", "nocall"),
                    help="Comma-separated states of the occurrences to export: mod, nomod, nocall. Default: all three")
+    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
+                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
+    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
+                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
+    o.add_argument("--threshold_valid_coverage", type=int, default=5,
+                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
+    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
+    gen = p.add_argument_group("general arguments")
+    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
+    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
+    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
+    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
+
+
+def add_motif_coverage_parser(sub):
+    """motif_coverage: how much of a bin's methylation the motifs of a bin-motifs.tsv explain (the reference only logs "% of sequences
+    remaining" inside find_best_candidates, find_motifs_bin.py:801-823).  Arguments are those of motif_sites: same ingest."""
+    p = sub.add_parser("motif_coverage", help="Reports how much of each bin's methylation the motifs of a bin-motifs.tsv explain", add_help=False)
+    p.add_argument("assembly", type=str, help="path to the assembly file.")
+    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
+    gm = p.add_argument_group("contig bin arguments, use one of:")
+    g = gm.add_mutually_exclusive_group(required=True)
+    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
+    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
+    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
+    gm.add_argument("--extension", type=str, default=".fasta",
+                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
+    o = p.add_argument_group("Options")
+    o.add_argument("--bin_motifs", type=str, required=True, help="Path to the bin-motifs.tsv whose motifs are assessed (motif_discovery's output)")
+    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
+    o.add_argument("--unexplained_sites", action="store_true",
+                   help="Also write unexplained-sites.bed: the methylated positions no motif of their bin covers")
     o.add_argument("--methylation_threshold_low", type=float, default=0.30,
                    help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
     o.add_argument("--methylation_threshold_high", type=float, default=0.70,

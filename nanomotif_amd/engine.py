@@ -26,6 +26,7 @@ SITE_MINUS = 4                                 # NM_SITES_MINUS: the strand bit 
 SITE_RECORD_BYTES = 9                          # a record on the device: contig (4), position (4), code (1)
 SITE_BUDGET_BYTES = 256 << 20                  # default size of one batch of records (ScanEngine.motif_sites)
 SITE_DTYPE = np.dtype([("candidate", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])
+UNEXPLAINED_DTYPE = np.dtype([("set", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])   # ScanEngine.unexplained_sites
 
 
 def site_state_set(states) -> int:
@@ -881,6 +882,99 @@ class ScanEngine:
                 rec["candidate"] = np.repeat(np.arange(k, e, dtype=np.uint32), np.diff(cut))
                 yield SiteBatch(first_candidate=k, n_candidates=e - k, first_record=first, batch_records=held, records=rec,
                                 counts=counts if first == 0 else None)
+                first += cap
+                if first >= held:
+                    break
+            k = e
+
+    # ------------------------------------------------------------------ coverage of a set of motifs (nm_motif_coverage_*)
+    def _coverage_args(self, sets):
+        """sets = [(bin name or id, mod type or slot number, [Motif, ...]), ...] -> (the leading arguments of nm_motif_coverage_*,
+        the arrays they point into (set_bin, set_slot, set_cand_offset, the candidate arrays), the number of motifs per set)."""
+        sets = [(b, mt, list(motifs)) for b, mt, motifs in sets]
+        n_sets = len(sets)
+        bi, so = self.bin_index, self.slot_of_mod
+        set_bin = np.fromiter((bi[s[0]] if isinstance(s[0], str) else int(s[0]) for s in sets), dtype=np.uint32, count=n_sets)
+        set_slot = np.fromiter((so[s[1]] if isinstance(s[1], str) else int(s[1]) for s in sets), dtype=np.uint8, count=n_sets)
+        n_motifs = [len(s[2]) for s in sets]
+        cand_off = np.zeros(n_sets + 1, dtype=np.uint32)
+        np.cumsum(np.asarray(n_motifs, dtype=np.uint32), out=cand_off[1:])
+        flat = [(m, 0, 0) for s in sets for m in s[2]]
+        if flat:
+            b = self.make_batch(flat, slot_of=lambda mt: 0)
+            lens, modpos, moff, masks = b.lens, b.modpos, b.offsets, b.masks
+        else:
+            lens, modpos, masks = (np.zeros(1, dtype=np.uint8) for _ in range(3))
+            moff = np.zeros(1, dtype=np.uint32)
+        keep = (set_bin, set_slot, cand_off, lens, modpos, moff, masks)
+        args = (self.ctx, n_sets, _ptr(set_bin, C.c_uint32), _ptr(set_slot, C.c_uint8), _ptr(cand_off, C.c_uint32), _ptr(lens, C.c_uint8),
+                _ptr(modpos, C.c_uint8), _ptr(moff, C.c_uint32), _ptr(masks, C.c_uint8))
+        return args, keep, n_motifs
+
+    def _coverage_counts(self, sets):
+        args, keep, n_motifs = self._coverage_args(sets)
+        set_bin = keep[0]
+        n_bins = len(self.bin_index)
+        # (a bin the engine does not hold is the library's to refuse: it gets no rows here)
+        names = {int(b): (self.bin_contigs(int(b)) if int(b) < n_bins else []) for b in np.unique(set_bin).tolist()}
+        per_set = [len(names[int(b)]) for b in set_bin]
+        set_rows = np.zeros(len(per_set) + 1, dtype=np.uint64)
+        np.cumsum(np.asarray(per_set, dtype=np.uint64), out=set_rows[1:])
+        cand_rows = np.zeros(sum(n_motifs) + 1, dtype=np.uint64)
+        np.cumsum(np.repeat(np.asarray(per_set, dtype=np.uint64), np.asarray(n_motifs, dtype=np.int64)), out=cand_rows[1:])
+        set_table = np.zeros((max(int(set_rows[-1]), 1), 10), dtype=np.int64)
+        cand_table = np.zeros((max(int(cand_rows[-1]), 1), 4), dtype=np.int64)
+        totals = np.zeros(max(len(per_set), 1), dtype=np.uint64)
+        _lib.check(self.lib.nm_motif_coverage_count(*args, _ptr(set_rows, C.c_uint64), _ptr(cand_rows, C.c_uint64), _ptr(totals, C.c_uint64),
+                                                    _ptr(set_table, C.c_int64), _ptr(cand_table, C.c_int64)))
+        return names, set_bin, n_motifs, set_rows, cand_rows, totals[:len(per_set)].astype(np.int64), set_table, cand_table
+
+    def motif_coverage(self, sets):
+        """How much of the methylation of a (bin, mod type) a SET of motifs explains (nm_motif_coverage_count; the reference only logs
+        "% of sequences remaining" inside find_best_candidates, find_motifs_bin.py:801-823).  ``sets`` = [(bin, mod_type, [Motif, ...]),
+        ...]; a set may be empty.  Returns per set (contig names in ``bin_contigs`` order, int64[n_contigs, 10], [int64[n_contigs, 4]
+        per motif]): the set table holds per strand (forward, then reverse) mod_total, mod_explained, nomod_total, nomod_covered,
+        nocall_covered; a motif's table (fwd mod, fwd nomod, rev mod, rev nomod) of the positions ONLY this motif of the set covers."""
+        names, set_bin, n_motifs, set_rows, cand_rows, _, set_table, cand_table = self._coverage_counts(sets)
+        out, k = [], 0
+        for s in range(len(n_motifs)):
+            per = [cand_table[int(cand_rows[j]):int(cand_rows[j + 1])] for j in range(k, k + n_motifs[s])]
+            out.append((names[int(set_bin[s])], set_table[int(set_rows[s]):int(set_rows[s + 1])], per))
+            k += n_motifs[s]
+        return out
+
+    def unexplained_sites(self, sets, max_records=None):
+        """Generator over the methylated positions NO motif of their set covers (nm_motif_coverage_sites).  Yields structured arrays
+        (fields set, contig, pos, code; code = 4 on the '-' strand, else 0) whose concatenation is in the order set, contig
+        (``bin_contigs`` order), position, '+' before '-'.  No batch holds more than ``max_records`` records (default
+        ``SITE_BUDGET_BYTES`` of device records); the concatenation does not depend on ``max_records``."""
+        limit = SITE_BUDGET_BYTES // SITE_RECORD_BYTES if max_records is None else int(max_records)
+        if limit < 1:
+            raise ValueError("max_records must be at least 1")
+        sets = [(b, mt, list(motifs)) for b, mt, motifs in sets]
+        totals = self._coverage_counts(sets)[5]
+        n, k = len(sets), 0
+        while k < n:
+            e, held = k + 1, int(totals[k])
+            while e < n and held + int(totals[e]) <= limit:
+                held += int(totals[e])
+                e += 1
+            args, keep, _ = self._coverage_args(sets[k:e])
+            first = 0
+            while True:                                    # one window, unless a single set exceeds the limit
+                cap = min(limit, held - first) if held else 0
+                rec = np.zeros(cap, dtype=UNEXPLAINED_DTYPE)
+                contig, pos, code = (np.zeros(max(cap, 1), dtype=t) for t in (np.uint32, np.uint32, np.uint8))
+                off = np.zeros(e - k + 1, dtype=np.uint64)
+                written = C.c_uint64(0)
+                _lib.check(self.lib.nm_motif_coverage_sites(*args, first, cap, _ptr(contig, C.c_uint32), _ptr(pos, C.c_uint32),
+                                                            _ptr(code, C.c_uint8), _ptr(off, C.c_uint64), C.byref(written)))
+                if int(off[-1]) != held or written.value != cap:
+                    raise _lib.NmScanError(f"nm_motif_coverage_sites delivered {written.value} of {cap} records ({int(off[-1])} in the call, {held} counted)")
+                rec["contig"], rec["pos"], rec["code"] = contig[:cap], pos[:cap], code[:cap]
+                cut = np.clip(off.astype(np.int64) - first, 0, cap)
+                rec["set"] = np.repeat(np.arange(k, e, dtype=np.uint32), np.diff(cut))
+                yield rec
                 first += cap
                 if first >= held:
                     break

@@ -625,8 +625,22 @@ def main(argv=None):
             pass
         if status:
             sys.exit(status)
+    elif args.command == "motif_coverage":
+        from . import motif_coverage
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+            sys.stderr.write("nanomotif motif_coverage runs on one GPU: start it without a multi-rank launcher\n")
+            sys.exit(2)
+        shared_setup(args, args.out)
+        status = motif_coverage.run(args)
+        try:
+            with open(os.path.join(args.out, "logs", "timings.motif_coverage.json"), "w") as f:
+                json.dump(motif_coverage.TIMINGS, f, indent=1)
+        except OSError:
+            pass
+        if status:
+            sys.exit(status)
     elif args.command in ("detect_contamination", "include_contigs"):
-        args.verbose = False                     # main.py:310-312: binnary runs with seed 1
+        args.verbose = False                    # main.py:310-312: binnary runs with seed 1
         args.seed = 1
         shared_setup(args, args.out)
         binnary(args)
