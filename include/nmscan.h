@@ -422,6 +422,56 @@ int nm_motif_coverage_sites(nm_ctx *ctx, uint32_t n_sets, const uint32_t *set_bi
                             uint32_t *site_contig, uint32_t *site_pos, uint8_t *site_code, uint64_t *set_offset,
                             uint64_t *n_written);
 
+/* ---- TWO-SAMPLE comparison: every occurrence of a batch of candidates classified by its state in two mod slots ---------------
+ * Reference: none.  The nearest is two runs of motif_model_contig(..., save_motif_positions=True) (find_motifs_bin.py:1285-1331),
+ * one per pileup, joined on the host; two nm_motif_sites_count tables are only the MARGINALS of the table below.
+ *
+ * The same assembly, two pileups (two time points, conditions, strains mapped to one reference) resident in different mod slots
+ * (nm_ingest_pileup[_part] clears only the slots it is given; NM_MAX_MOD_SLOTS = 8 holds two pileups x three mod types).  The
+ * candidate arrays are those of nm_motif_sites with TWO slot arrays: cand_slot_a[k] (sample A) and cand_slot_b[k] (sample B), any
+ * two slots with a pileup — also the same slot twice, or two threshold pairs of one pileup.
+ * An OCCURRENCE is exactly an occurrence of nm_motif_sites (stripped motif on '+', its reverse complement on '-', wholly inside
+ * the contig, non-ACGT letters never matching a specified position, reach limit [-96, 95] and the same error beyond it).  Its STATE
+ * in a slot is nm_motif_sites' state there: 0 methylated, 1 unmethylated (a position called both ways is methylated), 2 no call.
+ * TRANSITION t = 3 * state_a + state_b, 0..8; transition_set: bit t set = transition t is exported (NM_COMPARE_ALL = all nine,
+ * NM_COMPARE_SWITCHED = the two discordant called ones, mod>nomod and nomod>mod).
+ *
+ * nm_motif_compare_count: contig_counts = int64[row_offset[n_cand]][18] in the row layout of nm_score_batch_per_contig /
+ *   nm_motif_sites_count (one row per candidate and resident contig of its bin, nm_bin_contigs order): the nine transition counts
+ *   of the forward strand (index t), then the nine of the reverse strand (9 + t); all eighteen whatever transition_set says.
+ *   Summing a row over state_b gives nm_motif_sites_count's row on slot A, over state_a its row on slot B.
+ *   cand_total[k] = records candidate k has under transition_set.
+ * nm_motif_compare_sites: count + prefix + fill.  A record = (contig id, contig-local 0-based position of the modified base,
+ *   code = (NM_COMPARE_MINUS on '-') | t).  ORDER (part of the contract): candidate-major; within a candidate the contigs in
+ *   nm_bin_contigs order; within a contig ascending position; at equal position '+' before '-'.  cand_offset[n_cand + 1] = rank
+ *   of every candidate's first record (cand_offset[n_cand] = all records of the batch).  Written are exactly the records whose rank
+ *   lies in [first_record, first_record + capacity), to site_*[rank - first_record]; *n_written says how many that were (0 for a
+ *   window past the end).  Nothing is truncated silently.
+ * Launches: at most 3 (count, one per reach width) + scan + gather + 3 (fill) whatever the batch holds.  The chunk's sequence
+ * planes are loaded once and the constraint program is walked once per strand for both samples.
+ * NM_ESTATE without an assembly or without a pileup in either slot of a candidate, NM_EINVAL for NULLs / a bad bin / an empty
+ * transition_set / bits above 8, NM_ERANGE for more than 2^32 work items or rows and for a candidate beyond the reach limit. */
+#define NM_COMPARE_MINUS 16u        /* strand bit of a record's code: code = strand bit | transition, transition 0..8 */
+#define NM_COMPARE_ALL 0x1FFu
+#define NM_COMPARE_SWITCHED ((1u << 1) | (1u << 3))     /* mod>nomod (t = 1), nomod>mod (t = 3) */
+int nm_motif_compare_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_slot_a,
+                           const uint8_t *cand_slot_b, const uint8_t *cand_len, const uint8_t *cand_modpos,
+                           const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t transition_set,
+                           const uint64_t *row_offset, uint64_t *cand_total, int64_t *contig_counts);
+int nm_motif_compare_sites(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_slot_a,
+                           const uint8_t *cand_slot_b, const uint8_t *cand_len, const uint8_t *cand_modpos,
+                           const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t transition_set,
+                           uint64_t first_record, uint64_t capacity, uint32_t *site_contig, uint32_t *site_pos, uint8_t *site_code,
+                           uint64_t *cand_offset, uint64_t *n_written);
+/* The records of a span as the lines of switched-sites.bed (host code, no device needed):
+ *   contig \t start \t start + 1 \t name \t 0 \t strand \t a>b \t bin \n      a, b = mod / nomod / nocall (sample A > sample B)
+ * Runs, names, size query (out == NULL), NM_ERANGE on a short buffer, NM_POST_THREADS and thread-independent bytes exactly as
+ * nm_motif_sites_text; NM_EINVAL for a contig >= n_contigs or a code that is none of the eighteen. */
+int nm_motif_compare_text(uint64_t n_records, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code,
+                          uint32_t n_seg, const uint64_t *seg_begin, const char *seg_text, const uint64_t *seg_text_off,
+                          uint32_t n_contigs, const char *contig_text, const uint64_t *contig_text_off, char *out,
+                          uint64_t capacity, uint64_t *n_bytes);
+
 /* ---- per-contig READ methylation of motifs: the table binnary starts from -------------------------
  * Reference: nanomotif/main.py:142-193 — `contig_methylation = methylation_pattern(pileup, assembly, motifs,
  * min_valid_read_coverage, min_valid_cov_to_diff_fraction = 0.8, output_type = Median | WeightedMean)` from the

@@ -23,6 +23,7 @@ SYMBOLS = [
     "nm_tabix_regions", "nm_bed_parse_device_counts", "nm_bedcols_count_columns", "nm_readstats_upload_bedcols",
     "nm_motif_sites_count", "nm_motif_sites", "nm_motif_sites_text",
     "nm_motif_coverage_count", "nm_motif_coverage_sites",
+    "nm_motif_compare_count", "nm_motif_compare_sites", "nm_motif_compare_text",
 ]
 
 class SearchParams(C.Structure):
@@ -143,6 +144,11 @@ def _load_locked():
     lib.nm_motif_sites.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, u8p, u64p, u64p]
     lib.nm_motif_coverage_count.argtypes = [p, C.c_uint32, u32p, u8p, u32p, u8p, u8p, u32p, u8p, u64p, u64p, u64p, i64p, i64p]
     lib.nm_motif_coverage_sites.argtypes = [p, C.c_uint32, u32p, u8p, u32p, u8p, u8p, u32p, u8p, C.c_uint64, C.c_uint64, u32p, u32p, u8p, u64p, u64p]
+    lib.nm_motif_compare_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, u64p, i64p]
+    lib.nm_motif_compare_sites.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, u8p, u64p,
+                                           u64p]
+    lib.nm_motif_compare_text.argtypes = [C.c_uint64, u32p, u32p, u8p, C.c_uint32, u64p, C.c_char_p, u64p, C.c_uint32, C.c_char_p, u64p, p,
+                                          C.c_uint64, u64p]
     lib.nm_motif_sites_text.argtypes = [C.c_uint64, u32p, u32p, u8p, C.c_uint32, u64p, C.c_char_p, u64p, C.c_uint32, C.c_char_p, u64p, p,
                                         C.c_uint64, u64p]
     lib.nm_readstats_upload.argtypes = [p, C.c_uint32, C.c_uint64, p, p, p, p, p, p, C.c_int32, C.c_double, C.c_int, u64p]

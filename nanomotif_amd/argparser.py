@@ -1,5 +1,6 @@
 """Command line of the MI355X build: the ``motif_discovery`` sub-command with the reference's arguments
-(nanomotif/argparser.py:13-136), plus ``--device`` for the GPU to use, and the binnary sub-commands ``detect_contamination`` and
+(nanomotif/argparser.py:13-136), plus ``--device`` for the GPU to use, the project's own ``motif_sites`` / ``motif_coverage`` /
+``motif_compare`` on a finished ``bin-motifs.tsv``, and the binnary sub-commands ``detect_contamination`` and
 ``include_contigs`` with the reference's flags (argparser.py:139-236).  MTase-linker is out of scope."""
 import argparse
 
@@ -12,7 +13,7 @@ def create_parser():
                                      formatter_class=formatter)
     parser.add_argument("--version", action="version", version="%(prog)s {}".format(__version__))
     sub = parser.add_subparsers(help="-- Command descriptions --", dest="command", title="commands",
-                                metavar="{motif_discovery, motif_sites, motif_coverage, detect_contamination, include_contigs, check_installation}")
+                                metavar="{motif_discovery, motif_sites, motif_coverage, motif_compare, detect_contamination, include_contigs, check_installation}")
     p = sub.add_parser("motif_discovery", help="Finds motifs directly on bin level in provided assembly", add_help=False)
     p.add_argument("assembly", type=str, help="path to the assembly file.")
     p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
@@ -51,6 +52,7 @@ def create_parser():
     gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
     add_motif_sites_parser(sub)
     add_motif_coverage_parser(sub)
+    add_motif_compare_parser(sub)
     add_binnary_parsers(sub)
     sub.add_parser("check_installation", help="Run motif_discovery on a small synthetic data set", add_help=True)
     return parser
@@ -115,6 +117,53 @@ def add_motif_coverage_parser(sub):
     o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
     o.add_argument("--unexplained_sites", action="store_true",
                    help="Also write unexplained-sites.bed: the methylated positions no motif of their bin covers")
+    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
+                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
+    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
+                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
+    o.add_argument("--threshold_valid_coverage", type=int, default=5,
+                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
+    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
+    gen = p.add_argument_group("general arguments")
+    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
+    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
+    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
+    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
+
+
+def _transitions(text):
+    from .engine import TRANSITIONS
+    asked = [t.strip() for t in text.split(",") if t.strip()]
+    if not asked or any(t not in TRANSITIONS for t in asked):
+        raise argparse.ArgumentTypeError(f"a comma-separated selection of {', '.join(TRANSITIONS)} is expected, got {text!r}")
+    return tuple(t for t in TRANSITIONS if t in asked)
+
+
+def add_motif_compare_parser(sub):
+    """motif_compare: per-motif methylation change between two pileups of one assembly (no counterpart on the reference's command line;
+    nearest: two runs of motif_model_contig(save_motif_positions=True), find_motifs_bin.py:1285-1331, joined by hand).  Arguments are
+    those of motif_sites with two pileups and one or more bin-motifs.tsv: both pileups are ingested as motif_discovery ingests its one."""
+    p = sub.add_parser("motif_compare", help="Compares the methylation of the motifs of bin-motifs.tsv files between two pileups of one assembly",
+                       add_help=False)
+    p.add_argument("assembly", type=str, help="path to the assembly file.")
+    p.add_argument("pileup_a", type=str, help="path to the modkit pileup file of sample A.")
+    p.add_argument("pileup_b", type=str, help="path to the modkit pileup file of sample B (same assembly).")
+    gm = p.add_argument_group("contig bin arguments, use one of:")
+    g = gm.add_mutually_exclusive_group(required=True)
+    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
+    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
+    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
+    gm.add_argument("--extension", type=str, default=".fasta",
+                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
+    o = p.add_argument_group("Options")
+    o.add_argument("--bin_motifs", type=str, nargs="+", required=True,
+                   help="Path(s) to the bin-motifs.tsv whose motifs are compared (typically motif_discovery's output on sample A and on sample B)")
+    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
+    o.add_argument("--switched_sites", action="store_true",
+                   help="Also write switched-sites.bed: the occurrences whose state changed between the samples (see --transitions)")
+    o.add_argument("--transitions", type=_transitions, default=("mod>nomod", "nomod>mod"),
+                   help="Comma-separated transitions A>B written to switched-sites.bed, each of mod, nomod, nocall on either side. "
+                        "Default: mod>nomod,nomod>mod")
     o.add_argument("--methylation_threshold_low", type=float, default=0.30,
                    help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
     o.add_argument("--methylation_threshold_high", type=float, default=0.70,

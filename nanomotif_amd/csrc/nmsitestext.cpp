@@ -1,4 +1,6 @@
-// nm_motif_sites_text — the records of nm_motif_sites as the lines of motif-sites.bed, on a few host threads.
+// nm_motif_sites_text — the records of nm_motif_sites as the lines of motif-sites.bed, on a few host threads — and
+// nm_motif_compare_text, the records of nm_motif_compare_sites as the lines of switched-sites.bed: the same line with the
+// transition "a>b" in the state column.
 // The reference keeps the four position arrays of motif_model_contig(save_motif_positions=True) in memory
 // (find_motifs_bin.py:1322-1329) and writes no per-site file; the line format is this project's (README.md).
 // Two passes over the span: every thread sizes its share of the records exactly, the shares' offsets are a prefix sum, then every
@@ -28,8 +30,20 @@ inline char *put_u64(char *p, uint64_t v) {
     return p + n;
 }
 
+// how a record's code reads: its label = text[code & mask] (n labels), its strand bit
+struct Labels {
+    const char *const *text;
+    const unsigned *len;
+    unsigned n, mask, minus;
+};
+
 const char *const STATE_TEXT[3] = {"mod", "nomod", "nocall"};
 const unsigned STATE_LEN[3] = {3, 5, 6};
+const Labels SITE_LABELS{STATE_TEXT, STATE_LEN, 3, 3u, NM_SITES_MINUS};
+const char *const TRANSITION_TEXT[9] = {"mod>mod", "mod>nomod", "mod>nocall", "nomod>mod", "nomod>nomod", "nomod>nocall", "nocall>mod", "nocall>nomod",
+                                        "nocall>nocall"};
+const unsigned TRANSITION_LEN[9] = {7, 9, 10, 9, 11, 12, 10, 12, 13};
+const Labels TRANSITION_LABELS{TRANSITION_TEXT, TRANSITION_LEN, 9, 15u, NM_COMPARE_MINUS};
 
 struct Span {
     const uint32_t *contig, *pos;
@@ -37,6 +51,7 @@ struct Span {
     uint32_t n_seg;
     const uint64_t *seg_begin, *seg_text_off, *contig_text_off;
     const char *seg_text, *contig_text;
+    Labels lab;
     // segment that holds record i (the last one whose begin is <= i; empty segments are passed over)
     uint32_t seg_of(uint64_t i) const { return (uint32_t)(std::upper_bound(seg_begin, seg_begin + n_seg + 1, i) - seg_begin) - 1; }
 };
@@ -50,7 +65,7 @@ uint64_t size_range(const Span &s, uint64_t lo, uint64_t hi) {
         const uint64_t fixed = (s.seg_text_off[2 * seg + 2] - s.seg_text_off[2 * seg]) + 9;      // name + bin + 7 tabs + "0" + newline
         const uint32_t c = s.contig[i];
         const uint64_t p = s.pos[i];
-        bytes += (s.contig_text_off[c + 1] - s.contig_text_off[c]) + digits(p) + digits(p + 1) + 1 + STATE_LEN[s.code[i] & 3u] + fixed;
+        bytes += (s.contig_text_off[c + 1] - s.contig_text_off[c]) + digits(p) + digits(p + 1) + 1 + s.lab.len[s.code[i] & s.lab.mask] + fixed;
     }
     return bytes;
 }
@@ -74,11 +89,11 @@ char *write_range(const Span &s, uint64_t lo, uint64_t hi, char *out) {
         out += nl;
         memcpy(out, "\t0\t", 3);
         out += 3;
-        *out++ = (s.code[i] & NM_SITES_MINUS) ? '-' : '+';
+        *out++ = (s.code[i] & s.lab.minus) ? '-' : '+';
         *out++ = '\t';
-        const unsigned st = s.code[i] & 3u;
-        memcpy(out, STATE_TEXT[st], STATE_LEN[st]);
-        out += STATE_LEN[st];
+        const unsigned st = s.code[i] & s.lab.mask;
+        memcpy(out, s.lab.text[st], s.lab.len[st]);
+        out += s.lab.len[st];
         *out++ = '\t';
         const uint64_t bl = s.seg_text_off[2 * seg + 2] - s.seg_text_off[2 * seg + 1];
         memcpy(out, s.seg_text + s.seg_text_off[2 * seg + 1], bl);
@@ -88,11 +103,9 @@ char *write_range(const Span &s, uint64_t lo, uint64_t hi, char *out) {
     return out;
 }
 
-}  // namespace
-
-extern "C" int nm_motif_sites_text(uint64_t n, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code, uint32_t n_seg,
-                                   const uint64_t *seg_begin, const char *seg_text, const uint64_t *seg_text_off, uint32_t n_contigs,
-                                   const char *contig_text, const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes) {
+int records_text(const Labels &lab, uint64_t n, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code, uint32_t n_seg,
+                 const uint64_t *seg_begin, const char *seg_text, const uint64_t *seg_text_off, uint32_t n_contigs, const char *contig_text,
+                 const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes) {
     if (!n_bytes) return nm_set_error(NM_EINVAL, "NULL argument");
     *n_bytes = 0;
     if (n == 0) return NM_OK;
@@ -104,7 +117,7 @@ extern "C" int nm_motif_sites_text(uint64_t n, const uint32_t *site_contig, cons
     unsigned n_thr = std::max(1u, std::min(16u, std::thread::hardware_concurrency() / 2));
     if (const char *e = getenv("NM_POST_THREADS")) n_thr = (unsigned)std::max(1, std::min(16, atoi(e)));
     n_thr = (unsigned)std::min<uint64_t>(n_thr, (n + 255) / 256);        // (a thread is not worth starting for less)
-    const Span sp{site_contig, site_pos, site_code, n_seg, seg_begin, seg_text_off, contig_text_off, seg_text, contig_text};
+    const Span sp{site_contig, site_pos, site_code, n_seg, seg_begin, seg_text_off, contig_text_off, seg_text, contig_text, lab};
     auto lo_of = [&](unsigned t) { return n * t / n_thr; };
     std::vector<uint64_t> bytes(n_thr + 1, 0);
     std::vector<int> bad(n_thr, 0);
@@ -117,15 +130,31 @@ extern "C" int nm_motif_sites_text(uint64_t n, const uint32_t *site_contig, cons
     on_threads([&](unsigned t) {
         const uint64_t lo = lo_of(t), hi = lo_of(t + 1);
         for (uint64_t i = lo; i < hi; ++i)
-            if (site_contig[i] >= n_contigs || (site_code[i] & 3u) == 3u || (site_code[i] & ~7u)) { bad[t] = 1; return; }
+            if (site_contig[i] >= n_contigs || (site_code[i] & lab.mask) >= lab.n || (site_code[i] & ~(lab.mask | lab.minus))) { bad[t] = 1; return; }
         bytes[t + 1] = size_range(sp, lo, hi);
     });
     for (unsigned t = 0; t < n_thr; ++t)
-        if (bad[t]) return nm_set_error(NM_EINVAL, "a record names a contig >= %u or carries a code that is none of the six", n_contigs);
+        if (bad[t]) return nm_set_error(NM_EINVAL, "a record names a contig >= %u or carries a code that is none of the %u", n_contigs, 2 * lab.n);
     for (unsigned t = 0; t < n_thr; ++t) bytes[t + 1] += bytes[t];
     *n_bytes = bytes[n_thr];
     if (!out) return NM_OK;
     if (capacity < bytes[n_thr]) return nm_set_error(NM_ERANGE, "the text takes %llu bytes, the buffer holds %llu", (unsigned long long)bytes[n_thr], (unsigned long long)capacity);
     on_threads([&](unsigned t) { (void)write_range(sp, lo_of(t), lo_of(t + 1), out + bytes[t]); });
     return NM_OK;
+}
+
+}  // namespace
+
+extern "C" int nm_motif_sites_text(uint64_t n, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code, uint32_t n_seg,
+                                   const uint64_t *seg_begin, const char *seg_text, const uint64_t *seg_text_off, uint32_t n_contigs,
+                                   const char *contig_text, const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes) {
+    return records_text(SITE_LABELS, n, site_contig, site_pos, site_code, n_seg, seg_begin, seg_text, seg_text_off, n_contigs, contig_text,
+                        contig_text_off, out, capacity, n_bytes);
+}
+
+extern "C" int nm_motif_compare_text(uint64_t n, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code, uint32_t n_seg,
+                                     const uint64_t *seg_begin, const char *seg_text, const uint64_t *seg_text_off, uint32_t n_contigs,
+                                     const char *contig_text, const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes) {
+    return records_text(TRANSITION_LABELS, n, site_contig, site_pos, site_code, n_seg, seg_begin, seg_text, seg_text_off, n_contigs, contig_text,
+                        contig_text_off, out, capacity, n_bytes);
 }

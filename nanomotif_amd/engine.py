@@ -26,6 +26,9 @@ SITE_MINUS = 4                                 # NM_SITES_MINUS: the strand bit 
 SITE_RECORD_BYTES = 9                          # a record on the device: contig (4), position (4), code (1)
 SITE_BUDGET_BYTES = 256 << 20                  # default size of one batch of records (ScanEngine.motif_sites)
 SITE_DTYPE = np.dtype([("candidate", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])
+COMPARE_MINUS = 16                             # NM_COMPARE_MINUS: the strand bit of a record of nm_motif_compare_sites; the rest is the transition
+TRANSITIONS = tuple(f"{a}>{b}" for a in SITE_STATES for b in SITE_STATES)      # transition t = 3 * state in sample A + state in sample B
+SWITCHED = ("mod>nomod", "nomod>mod")          # NM_COMPARE_SWITCHED: the two discordant called transitions
 UNEXPLAINED_DTYPE = np.dtype([("set", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])   # ScanEngine.unexplained_sites
 
 
@@ -36,6 +39,15 @@ def site_state_set(states) -> int:
     if bad or not states:
         raise ValueError(f"states must be a non-empty selection of {SITE_STATES}, got {states!r}")
     return sum(1 << SITE_STATES.index(s) for s in set(states))
+
+
+def transition_set(transitions) -> int:
+    """("mod>nomod", "nomod>mod") -> the transition_set bits of nm_motif_compare_*."""
+    transitions = tuple(transitions)
+    bad = [t for t in transitions if t not in TRANSITIONS]
+    if bad or not transitions:
+        raise ValueError(f"transitions must be a non-empty selection of {TRANSITIONS}, got {transitions!r}")
+    return sum(1 << TRANSITIONS.index(t) for t in set(transitions))
 
 
 class SiteBatch:
@@ -878,6 +890,90 @@ class ScanEngine:
                     raise _lib.NmScanError(f"nm_motif_sites delivered {written.value} of {cap} records ({int(off[-1])} in the batch, {held} counted)")
                 rec["contig"], rec["pos"], rec["code"] = contig[:cap], pos[:cap], code[:cap]
                 # the candidate of every record of the window: the prefix of the batch, cut to [first, first + cap)
+                cut = np.clip(off.astype(np.int64) - first, 0, cap)
+                rec["candidate"] = np.repeat(np.arange(k, e, dtype=np.uint32), np.diff(cut))
+                yield SiteBatch(first_candidate=k, n_candidates=e - k, first_record=first, batch_records=held, records=rec,
+                                counts=counts if first == 0 else None)
+                first += cap
+                if first >= held:
+                    break
+            k = e
+
+    # ------------------------------------------------------------------ two-sample comparison (nm_motif_compare_*)
+    def _compare_batch(self, candidates, labels_a_b):
+        """(CandidateBatch whose slots are sample A's, uint8 slots of sample B).  ``labels_a_b``: the classifications of the two
+        samples — a pair (label or slot number of A, of B) for every candidate, or a mapping / callable from a candidate's mod type to
+        such a pair."""
+        if isinstance(labels_a_b, (tuple, list)):
+            pair_of = lambda mt: labels_a_b
+        elif callable(labels_a_b):
+            pair_of = labels_a_b
+        else:
+            pair_of = labels_a_b.__getitem__
+        so = self.slot_of_mod
+        slot = lambda x: so[x] if isinstance(x, str) else int(x)
+        candidates = list(candidates)
+        b = self.make_batch(candidates, slot_of=lambda mt: slot(pair_of(mt)[0]))
+        slots_b = np.fromiter((slot(pair_of(c[1])[1]) for c in candidates), dtype=np.uint8, count=len(candidates))
+        return b, slots_b
+
+    @staticmethod
+    def _compare_args(b: CandidateBatch, slots_b):
+        return (len(b), _ptr(b.bins, C.c_uint32), _ptr(b.slots, C.c_uint8), _ptr(slots_b, C.c_uint8), _ptr(b.lens, C.c_uint8),
+                _ptr(b.modpos, C.c_uint8), _ptr(b.offsets, C.c_uint32), _ptr(b.masks, C.c_uint8))
+
+    def _compare_counts(self, b: CandidateBatch, slots_b, tset: int):
+        names, rows = self._site_rows(b)
+        table = np.zeros((max(int(rows[-1]), 1), 18), dtype=np.int64)
+        totals = np.zeros(max(len(b), 1), dtype=np.uint64)
+        if len(b):
+            _lib.check(self.lib.nm_motif_compare_count(self.ctx, *self._compare_args(b, slots_b), int(tset), _ptr(rows, C.c_uint64),
+                                                       _ptr(totals, C.c_uint64), _ptr(table, C.c_int64)))
+        return names, rows, totals[:len(b)], table[:int(rows[-1])]
+
+    def motif_compare_counts(self, candidates, labels_a_b):
+        """Per (candidate, contig) the eighteen transition counts of every resident contig of the candidate's bin between two resident
+        classifications (nm_motif_compare_count): column 3 * state_a + state_b of the forward strand, then 9 + that of the reverse
+        strand; states 0 mod, 1 nomod, 2 nocall.  ``candidates``: sequence of (Motif, mod_type, bin); ``labels_a_b``: see
+        ``_compare_batch``.  Returns a list, per candidate, of (contig names, int64[n_contigs, 18])."""
+        b, slots_b = self._compare_batch(candidates, labels_a_b)
+        names, rows, _, table = self._compare_counts(b, slots_b, 0x1FF)
+        return [(names[int(b.bins[k])], table[int(rows[k]):int(rows[k + 1])]) for k in range(len(b))]
+
+    def motif_compare_sites(self, candidates, labels_a_b, transitions=SWITCHED, max_records=None):
+        """Generator over the occurrences of ``candidates`` whose transition between the two samples is one of ``transitions``
+        (``TRANSITIONS`` spellings; default the two discordant called ones).  Yields ``SiteBatch`` objects as ``motif_sites`` does
+        (``counts``: the int64[n_contigs, 18] tables); a record's code = 16 for the '-' strand | transition 0..8.  Order: candidate,
+        contig (``bin_contigs`` order), position, '+' before '-'.  No batch holds more than ``max_records`` records; the concatenation
+        does not depend on ``max_records``."""
+        b, slots_b = self._compare_batch(candidates, labels_a_b)
+        tset = transition_set(transitions)
+        limit = SITE_BUDGET_BYTES // SITE_RECORD_BYTES if max_records is None else int(max_records)
+        if limit < 1:
+            raise ValueError("max_records must be at least 1")
+        names, rows, totals, table = self._compare_counts(b, slots_b, tset)
+        totals = totals.astype(np.int64)
+        n, k = len(b), 0
+        while k < n:
+            e, held = k + 1, int(totals[k])
+            while e < n and held + int(totals[e]) <= limit:
+                held += int(totals[e])
+                e += 1
+            sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
+            sub_b = np.ascontiguousarray(slots_b[k:e])
+            counts = [(names[int(b.bins[j])], table[int(rows[j]):int(rows[j + 1])]) for j in range(k, e)]
+            first = 0
+            while True:                                    # one window, unless a single candidate exceeds the limit
+                cap = min(limit, held - first) if held else 0
+                rec = np.zeros(cap, dtype=SITE_DTYPE)
+                contig, pos, code = (np.zeros(max(cap, 1), dtype=t) for t in (np.uint32, np.uint32, np.uint8))
+                off = np.zeros(e - k + 1, dtype=np.uint64)
+                written = C.c_uint64(0)
+                _lib.check(self.lib.nm_motif_compare_sites(self.ctx, *self._compare_args(sub, sub_b), tset, first, cap, _ptr(contig, C.c_uint32),
+                                                           _ptr(pos, C.c_uint32), _ptr(code, C.c_uint8), _ptr(off, C.c_uint64), C.byref(written)))
+                if int(off[-1]) != held or written.value != cap:
+                    raise _lib.NmScanError(f"nm_motif_compare_sites delivered {written.value} of {cap} records ({int(off[-1])} in the batch, {held} counted)")
+                rec["contig"], rec["pos"], rec["code"] = contig[:cap], pos[:cap], code[:cap]
                 cut = np.clip(off.astype(np.int64) - first, 0, cap)
                 rec["candidate"] = np.repeat(np.arange(k, e, dtype=np.uint32), np.diff(cut))
                 yield SiteBatch(first_candidate=k, n_candidates=e - k, first_record=first, batch_records=held, records=rec,

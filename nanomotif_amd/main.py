@@ -639,6 +639,20 @@ def main(argv=None):
             pass
         if status:
             sys.exit(status)
+    elif args.command == "motif_compare":
+        from . import motif_compare
+        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
+            sys.stderr.write("nanomotif motif_compare runs on one GPU: start it without a multi-rank launcher\n")
+            sys.exit(2)
+        shared_setup(args, args.out)
+        status = motif_compare.run(args)
+        try:
+            with open(os.path.join(args.out, "logs", "timings.motif_compare.json"), "w") as f:
+                json.dump(motif_compare.TIMINGS, f, indent=1)
+        except OSError:
+            pass
+        if status:
+            sys.exit(status)
     elif args.command in ("detect_contamination", "include_contigs"):
         args.verbose = False                    # main.py:310-312: binnary runs with seed 1
         args.seed = 1

@@ -88,10 +88,12 @@ def candidates_of_bin_motifs(path) -> list:
     return out
 
 
-def format_sites(contig, pos, code, seg_begin, seg_names, seg_bins, contig_names) -> bytes:
+def format_sites(contig, pos, code, seg_begin, seg_names, seg_bins, contig_names, symbol="nm_motif_sites_text") -> bytes:
     """The lines of motif-sites.bed for records (contig, pos, code) cut into runs [seg_begin[s], seg_begin[s + 1]) that share a name
-    and a bin (nm_motif_sites_text: native, on up to NM_POST_THREADS threads)."""
+    and a bin (nm_motif_sites_text: native, on up to NM_POST_THREADS threads).  ``symbol``: the writer, nm_motif_compare_text for the
+    records of ``ScanEngine.motif_compare_sites`` (switched-sites.bed)."""
     lib = _lib.load()
+    text = getattr(lib, symbol)
     n = len(contig)
     if n == 0:
         return b""
@@ -109,9 +111,9 @@ def format_sites(contig, pos, code, seg_begin, seg_names, seg_bins, contig_names
     args = (n, p(contig, C.c_uint32), p(pos, C.c_uint32), p(code, C.c_uint8), len(seg_names), p(seg_begin, C.c_uint64), b"".join(parts),
             p(seg_off, C.c_uint64), len(cparts), b"".join(cparts), p(c_off, C.c_uint64))
     size = C.c_uint64(0)
-    _lib.check(lib.nm_motif_sites_text(*args, None, 0, C.byref(size)))
+    _lib.check(text(*args, None, 0, C.byref(size)))
     buf = np.empty(size.value, dtype=np.uint8)
-    _lib.check(lib.nm_motif_sites_text(*args, buf.ctypes.data_as(C.c_void_p), size.value, C.byref(size)))
+    _lib.check(text(*args, buf.ctypes.data_as(C.c_void_p), size.value, C.byref(size)))
     return buf.tobytes()
 
 
@@ -147,10 +149,73 @@ def format_summary(summary) -> str:
     return "\n".join(lines) + "\n"
 
 
-def load_engine(args, device: int) -> ScanEngine:
+def _open_pileup(eng: ScanEngine, path: str, bin_contig: dict, threads: int):
+    """The table of one pileup file: the device-side bedMethyl parser, the host reader where it declines; a bgzip pileup through its
+    tabix index for the binned contigs."""
+    bgzip = path.endswith(".gz")
+    if bgzip and not os.path.exists(path + ".tbi"):
+        raise FileNotFoundError(f"Tabix index for {path} not found.")
+    wanted = list(dict.fromkeys(fasta.original_name(c) for c in bin_contig)) if bgzip else None
+    index = path + ".tbi" if bgzip else None
+    table = None
+    if os.environ.get("NANOMOTIF_HOST_PARSER") != "1" and not any(fasta.ALIAS_SEP in c for c in bin_contig):
+        try:
+            table = pileup_mod.DevicePileup(eng, path, threads=threads, contigs=wanted, index_path=index)
+        except _lib.NmScanError as e:
+            if e.code != _lib.NM_EDECLINED:
+                raise
+            log.info(f"pileup: the device parser declined ({e}); using the host parser")
+    if table is None:
+        table = pileup_mod.NativePileup(path, contigs=wanted, index_path=index)
+    on_device = isinstance(table, pileup_mod.DevicePileup)
+    log.info(f"pileup: {len(table):,} rows ({'device' if on_device else 'host'} parser)")
+    return table
+
+
+def _ingest_table(eng: ScanEngine, table, names: list, args, label_of=None) -> dict:
+    """Pre-filters and classification of ``motif_discovery`` for one opened pileup on the resident assembly (``names``: the engine's
+    contigs); closes the table.  ``label_of``: mod type -> label of its classification (default: the mod type itself).  Returns the
+    ingest's result (``kept``: uint32[n_contigs, 8] surviving rows per contig and mod code) — the engine's own ingest tables speak about
+    the LAST pileup only."""
+    label_of = label_of or (lambda mt: mt)
+    t0 = time.perf_counter()
+    on_device = isinstance(table, pileup_mod.DevicePileup)
+    local_id = {c: i for i, c in enumerate(names)}
+    lut = np.array([local_id.get(n, 0xFFFFFFFF) for n in table.contig_names], dtype=np.uint32)
+    labels = {i: (label_of(mt), MOD_TYPE_TO_CANONICAL[mt]) for i, mt in enumerate(pileup_mod.MOD_TYPES)}
+    low, high = args.methylation_threshold_low, args.methylation_threshold_high
+    part_rows = int(os.environ.get("NANOMOTIF_INGEST_PART_ROWS", 250_000_000))
+    if on_device:
+        res = eng.ingest_device_pileup(table, lut, labels, low=low, high=high, max_part_rows=part_rows)
+    else:
+        # further placements of a contig listed under several bins: the contig's rows once more per placement
+        file_id = {n: i for i, n in enumerate(table.contig_names)}
+        placements = [(file_id[fasta.original_name(c)], local_id[c]) for c in names
+                      if fasta.ALIAS_SEP in c and fasta.original_name(c) in file_id]
+        file_contig = table.file_contig_column().copy() if placements else None
+        cols = table.ingest_columns(lut)
+        extra = []
+        for fid, local in placements:
+            sel = np.flatnonzero(file_contig == fid)
+            extra.append(dict(contig=np.full(len(sel), local, np.uint32),
+                              **{k: cols[k][sel] for k in ("position", "mod_type", "strand", "fraction_mod", "nvalid_cov")}))
+        res = eng.ingest_pileup(cols["contig"], cols["position"], cols["mod_type"], cols["strand"], cols["fraction_mod"], cols["nvalid_cov"],
+                                labels, low=low, high=high, want_rows=False, max_part_rows=part_rows, extra_parts=extra)
+        del cols
+    table.close()
+    log.info(f"pileup: {res['n_kept']:,} rows after the device-side filters")
+    res["seconds"] = time.perf_counter() - t0
+    return res
+
+
+def load_engine(args, device: int, pileups=None) -> ScanEngine:
     """Assembly and pileup of the command line -> an engine whose state planes are ``motif_discovery``'s: the readers, the contig
     selection, the pre-filters and the classification of ``main.find_motifs_bin`` on one GPU (device-side FASTA and bedMethyl
-    parsers, the host readers where those decline; a bgzip pileup through its tabix index for the binned contigs)."""
+    parsers, the host readers where those decline; a bgzip pileup through its tabix index for the binned contigs).
+    ``pileups``: [(path, label_of), ...] to make several pileups resident on the one assembly, each under its own labels (default: the
+    one pileup of ``args.pileup`` under the mod types' names); ``eng.pileup_ingests`` holds the result of each ingest in that order
+    (``seconds``: reading and ingesting that pileup)."""
+    pileups = [(str(args.pileup), None)] if pileups is None else [(str(p), f) for p, f in pileups]
     bin_contig = fasta.generate_contig_bin(args)
     if not bin_contig:
         raise ValueError("No bin contig mapping found")
@@ -164,54 +229,23 @@ def load_engine(args, device: int) -> ScanEngine:
         bin_contig = {c: b for c, b in bin_contig.items() if c in assembly}
         if not bin_contig:
             raise ValueError("No contigs remain in bin_contig after filtering against the assembly")
-        path = str(args.pileup)
-        bgzip = path.endswith(".gz")
-        if bgzip and not os.path.exists(path + ".tbi"):
-            raise FileNotFoundError(f"Tabix index for {path} not found.")
-        wanted = list(dict.fromkeys(fasta.original_name(c) for c in bin_contig)) if bgzip else None
-        index = path + ".tbi" if bgzip else None
-        table = None
-        if os.environ.get("NANOMOTIF_HOST_PARSER") != "1" and not any(fasta.ALIAS_SEP in c for c in bin_contig):
-            try:
-                table = pileup_mod.DevicePileup(eng, path, threads=threads, contigs=wanted, index_path=index)
-            except _lib.NmScanError as e:
-                if e.code != _lib.NM_EDECLINED:
-                    raise
-                log.info(f"pileup: the device parser declined ({e}); using the host parser")
-        if table is None:
-            table = pileup_mod.NativePileup(path, contigs=wanted, index_path=index)
-        on_device = isinstance(table, pileup_mod.DevicePileup)
-        log.info(f"pileup: {len(table):,} rows ({'device' if on_device else 'host'} parser)")
+        t0 = time.perf_counter()
+        table = _open_pileup(eng, pileups[0][0], bin_contig, threads)
+        t_open = time.perf_counter() - t0
         names = list(bin_contig)
         all_bins = sorted(set(bin_contig.values()))
         if device_fasta:
             eng.upload_assembly_fasta(assembly, names, [bin_contig[c] for c in names], bin_names=all_bins)
         else:
             eng.upload_assembly(names, [assembly[c] for c in names], [bin_contig[c] for c in names], bin_names=all_bins)
-        local_id = {c: i for i, c in enumerate(names)}
-        lut = np.array([local_id.get(n, 0xFFFFFFFF) for n in table.contig_names], dtype=np.uint32)
-        labels = {i: (mt, MOD_TYPE_TO_CANONICAL[mt]) for i, mt in enumerate(pileup_mod.MOD_TYPES)}
-        low, high = args.methylation_threshold_low, args.methylation_threshold_high
-        part_rows = int(os.environ.get("NANOMOTIF_INGEST_PART_ROWS", 250_000_000))
-        if on_device:
-            res = eng.ingest_device_pileup(table, lut, labels, low=low, high=high, max_part_rows=part_rows)
-        else:
-            # further placements of a contig listed under several bins: the contig's rows once more per placement
-            file_id = {n: i for i, n in enumerate(table.contig_names)}
-            placements = [(file_id[fasta.original_name(c)], local_id[c]) for c in names
-                          if fasta.ALIAS_SEP in c and fasta.original_name(c) in file_id]
-            file_contig = table.file_contig_column().copy() if placements else None
-            cols = table.ingest_columns(lut)
-            extra = []
-            for fid, local in placements:
-                sel = np.flatnonzero(file_contig == fid)
-                extra.append(dict(contig=np.full(len(sel), local, np.uint32),
-                                  **{k: cols[k][sel] for k in ("position", "mod_type", "strand", "fraction_mod", "nvalid_cov")}))
-            res = eng.ingest_pileup(cols["contig"], cols["position"], cols["mod_type"], cols["strand"], cols["fraction_mod"], cols["nvalid_cov"],
-                                    labels, low=low, high=high, want_rows=False, max_part_rows=part_rows, extra_parts=extra)
-            del cols
-        table.close()
-        log.info(f"pileup: {res['n_kept']:,} rows after the device-side filters")
+        eng.pileup_ingests = [_ingest_table(eng, table, names, args, pileups[0][1])]
+        eng.pileup_ingests[0]["seconds"] += t_open
+        for path, label_of in pileups[1:]:
+            t0 = time.perf_counter()
+            table = _open_pileup(eng, path, bin_contig, threads)
+            t_open = time.perf_counter() - t0
+            eng.pileup_ingests.append(_ingest_table(eng, table, names, args, label_of))
+            eng.pileup_ingests[-1]["seconds"] += t_open
         return eng
     except BaseException:
         eng.close()
