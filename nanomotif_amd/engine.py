@@ -837,14 +837,66 @@ class ScanEngine:
         np.cumsum([len(names[int(x)]) for x in b.bins], out=rows[1:])
         return names, rows
 
-    def _site_counts(self, b: CandidateBatch, state_set: int):
+    def _count_table(self, call, args, b: CandidateBatch, selection: int, width: int):
+        """(contig names per bin, row prefix, totals under ``selection``, int64[rows, width]) of one count call of the per-candidate
+        exports (nm_motif_sites_count, nm_motif_compare_count); ``args``: the call's candidate arguments."""
         names, rows = self._site_rows(b)
-        table = np.zeros((max(int(rows[-1]), 1), 6), dtype=np.int64)
+        table = np.zeros((max(int(rows[-1]), 1), width), dtype=np.int64)
         totals = np.zeros(max(len(b), 1), dtype=np.uint64)
         if len(b):
-            _lib.check(self.lib.nm_motif_sites_count(self.ctx, *self._batch_args(b), int(state_set), _ptr(rows, C.c_uint64),
-                                                     _ptr(totals, C.c_uint64), _ptr(table, C.c_int64)))
+            _lib.check(call(self.ctx, *args, int(selection), _ptr(rows, C.c_uint64), _ptr(totals, C.c_uint64), _ptr(table, C.c_int64)))
         return names, rows, totals[:len(b)], table[:int(rows[-1])]
+
+    @staticmethod
+    def _record_limit(max_records) -> int:
+        limit = SITE_BUDGET_BYTES // SITE_RECORD_BYTES if max_records is None else int(max_records)
+        if limit < 1:
+            raise ValueError("max_records must be at least 1")
+        return limit
+
+    def _record_windows(self, call, group_args, totals, limit: int, dtype, owner: str, unit: str):
+        """The window loop of the three record exports: consecutive owners (candidates, sets) are grouped while their ``totals`` fit
+        ``limit``, and every group is fetched in windows of at most ``limit`` records — one, unless a single owner exceeds the limit.
+        ``call``: the library's *_sites function; ``group_args(k, e)``: its arguments before first_record for the owners [k, e);
+        ``dtype``: the records' type, whose ``owner`` field is filled in here; ``unit``: what the library's message calls a group.
+        The ctypes pointers of those arguments keep their arrays alive.  Yields (k, e, first_record, records of the group, the window's
+        records)."""
+        n, k = len(totals), 0
+        while k < n:
+            e, held = k + 1, int(totals[k])
+            while e < n and held + int(totals[e]) <= limit:
+                held += int(totals[e])
+                e += 1
+            args = group_args(k, e)
+            first = 0
+            while True:
+                cap = min(limit, held - first) if held else 0
+                rec = np.zeros(cap, dtype=dtype)
+                contig, pos, code = (np.zeros(max(cap, 1), dtype=t) for t in (np.uint32, np.uint32, np.uint8))
+                off = np.zeros(e - k + 1, dtype=np.uint64)
+                written = C.c_uint64(0)
+                _lib.check(call(*args, first, cap, _ptr(contig, C.c_uint32), _ptr(pos, C.c_uint32), _ptr(code, C.c_uint8), _ptr(off, C.c_uint64),
+                                C.byref(written)))
+                if int(off[-1]) != held or written.value != cap:
+                    raise _lib.NmScanError(f"{call.__name__} delivered {written.value} of {cap} records ({int(off[-1])} in the {unit}, {held} counted)")
+                rec["contig"], rec["pos"], rec["code"] = contig[:cap], pos[:cap], code[:cap]
+                # the owner of every record of the window: the prefix of the group, cut to [first, first + cap)
+                cut = np.clip(off.astype(np.int64) - first, 0, cap)
+                rec[owner] = np.repeat(np.arange(k, e, dtype=np.uint32), np.diff(cut))
+                yield k, e, first, held, rec
+                first += cap
+                if first >= held:
+                    break
+            k = e
+
+    def _site_batches(self, windows, b: CandidateBatch, names, rows, table):
+        """The windows of ``_record_windows`` over the candidates ``b`` as ``SiteBatch`` objects."""
+        for k, e, first, held, rec in windows:
+            counts = [(names[int(b.bins[j])], table[int(rows[j]):int(rows[j + 1])]) for j in range(k, e)] if first == 0 else None
+            yield SiteBatch(first_candidate=k, n_candidates=e - k, first_record=first, batch_records=held, records=rec, counts=counts)
+
+    def _site_counts(self, b: CandidateBatch, state_set: int):
+        return self._count_table(self.lib.nm_motif_sites_count, self._batch_args(b), b, state_set, 6)
 
     def motif_site_counts(self, candidates):
         """Per (candidate, contig) the six site counts (fwd mod, fwd nomod, fwd nocall, rev mod, rev nomod, rev nocall) of every
@@ -864,40 +916,14 @@ class ScanEngine:
         several windows.  The concatenation does not depend on ``max_records``."""
         b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(candidates)
         state_set = site_state_set(states)
-        limit = SITE_BUDGET_BYTES // SITE_RECORD_BYTES if max_records is None else int(max_records)
-        if limit < 1:
-            raise ValueError("max_records must be at least 1")
+        limit = self._record_limit(max_records)
         names, rows, totals, table = self._site_counts(b, state_set)
-        totals = totals.astype(np.int64)
-        n, k = len(b), 0
-        while k < n:
-            e, held = k + 1, int(totals[k])
-            while e < n and held + int(totals[e]) <= limit:
-                held += int(totals[e])
-                e += 1
+
+        def group_args(k, e):
             sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
-            counts = [(names[int(b.bins[j])], table[int(rows[j]):int(rows[j + 1])]) for j in range(k, e)]
-            first = 0
-            while True:                                    # one window, unless a single candidate exceeds the limit
-                cap = min(limit, held - first) if held else 0
-                rec = np.zeros(cap, dtype=SITE_DTYPE)
-                contig, pos, code = (np.zeros(max(cap, 1), dtype=t) for t in (np.uint32, np.uint32, np.uint8))
-                off = np.zeros(e - k + 1, dtype=np.uint64)
-                written = C.c_uint64(0)
-                _lib.check(self.lib.nm_motif_sites(self.ctx, *self._batch_args(sub), state_set, first, cap, _ptr(contig, C.c_uint32),
-                                                   _ptr(pos, C.c_uint32), _ptr(code, C.c_uint8), _ptr(off, C.c_uint64), C.byref(written)))
-                if int(off[-1]) != held or written.value != cap:
-                    raise _lib.NmScanError(f"nm_motif_sites delivered {written.value} of {cap} records ({int(off[-1])} in the batch, {held} counted)")
-                rec["contig"], rec["pos"], rec["code"] = contig[:cap], pos[:cap], code[:cap]
-                # the candidate of every record of the window: the prefix of the batch, cut to [first, first + cap)
-                cut = np.clip(off.astype(np.int64) - first, 0, cap)
-                rec["candidate"] = np.repeat(np.arange(k, e, dtype=np.uint32), np.diff(cut))
-                yield SiteBatch(first_candidate=k, n_candidates=e - k, first_record=first, batch_records=held, records=rec,
-                                counts=counts if first == 0 else None)
-                first += cap
-                if first >= held:
-                    break
-            k = e
+            return (self.ctx, *self._batch_args(sub), state_set)
+        windows = self._record_windows(self.lib.nm_motif_sites, group_args, totals, limit, SITE_DTYPE, "candidate", "batch")
+        yield from self._site_batches(windows, b, names, rows, table)
 
     # ------------------------------------------------------------------ two-sample comparison (nm_motif_compare_*)
     def _compare_batch(self, candidates, labels_a_b):
@@ -923,13 +949,7 @@ class ScanEngine:
                 _ptr(b.modpos, C.c_uint8), _ptr(b.offsets, C.c_uint32), _ptr(b.masks, C.c_uint8))
 
     def _compare_counts(self, b: CandidateBatch, slots_b, tset: int):
-        names, rows = self._site_rows(b)
-        table = np.zeros((max(int(rows[-1]), 1), 18), dtype=np.int64)
-        totals = np.zeros(max(len(b), 1), dtype=np.uint64)
-        if len(b):
-            _lib.check(self.lib.nm_motif_compare_count(self.ctx, *self._compare_args(b, slots_b), int(tset), _ptr(rows, C.c_uint64),
-                                                       _ptr(totals, C.c_uint64), _ptr(table, C.c_int64)))
-        return names, rows, totals[:len(b)], table[:int(rows[-1])]
+        return self._count_table(self.lib.nm_motif_compare_count, self._compare_args(b, slots_b), b, tset, 18)
 
     def motif_compare_counts(self, candidates, labels_a_b):
         """Per (candidate, contig) the eighteen transition counts of every resident contig of the candidate's bin between two resident
@@ -948,40 +968,14 @@ class ScanEngine:
         does not depend on ``max_records``."""
         b, slots_b = self._compare_batch(candidates, labels_a_b)
         tset = transition_set(transitions)
-        limit = SITE_BUDGET_BYTES // SITE_RECORD_BYTES if max_records is None else int(max_records)
-        if limit < 1:
-            raise ValueError("max_records must be at least 1")
+        limit = self._record_limit(max_records)
         names, rows, totals, table = self._compare_counts(b, slots_b, tset)
-        totals = totals.astype(np.int64)
-        n, k = len(b), 0
-        while k < n:
-            e, held = k + 1, int(totals[k])
-            while e < n and held + int(totals[e]) <= limit:
-                held += int(totals[e])
-                e += 1
+
+        def group_args(k, e):
             sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
-            sub_b = np.ascontiguousarray(slots_b[k:e])
-            counts = [(names[int(b.bins[j])], table[int(rows[j]):int(rows[j + 1])]) for j in range(k, e)]
-            first = 0
-            while True:                                    # one window, unless a single candidate exceeds the limit
-                cap = min(limit, held - first) if held else 0
-                rec = np.zeros(cap, dtype=SITE_DTYPE)
-                contig, pos, code = (np.zeros(max(cap, 1), dtype=t) for t in (np.uint32, np.uint32, np.uint8))
-                off = np.zeros(e - k + 1, dtype=np.uint64)
-                written = C.c_uint64(0)
-                _lib.check(self.lib.nm_motif_compare_sites(self.ctx, *self._compare_args(sub, sub_b), tset, first, cap, _ptr(contig, C.c_uint32),
-                                                           _ptr(pos, C.c_uint32), _ptr(code, C.c_uint8), _ptr(off, C.c_uint64), C.byref(written)))
-                if int(off[-1]) != held or written.value != cap:
-                    raise _lib.NmScanError(f"nm_motif_compare_sites delivered {written.value} of {cap} records ({int(off[-1])} in the batch, {held} counted)")
-                rec["contig"], rec["pos"], rec["code"] = contig[:cap], pos[:cap], code[:cap]
-                cut = np.clip(off.astype(np.int64) - first, 0, cap)
-                rec["candidate"] = np.repeat(np.arange(k, e, dtype=np.uint32), np.diff(cut))
-                yield SiteBatch(first_candidate=k, n_candidates=e - k, first_record=first, batch_records=held, records=rec,
-                                counts=counts if first == 0 else None)
-                first += cap
-                if first >= held:
-                    break
-            k = e
+            return (self.ctx, *self._compare_args(sub, np.ascontiguousarray(slots_b[k:e])), tset)
+        windows = self._record_windows(self.lib.nm_motif_compare_sites, group_args, totals, limit, SITE_DTYPE, "candidate", "batch")
+        yield from self._site_batches(windows, b, names, rows, table)
 
     # ------------------------------------------------------------------ coverage of a set of motifs (nm_motif_coverage_*)
     def _coverage_args(self, sets):
@@ -1044,37 +1038,13 @@ class ScanEngine:
         (fields set, contig, pos, code; code = 4 on the '-' strand, else 0) whose concatenation is in the order set, contig
         (``bin_contigs`` order), position, '+' before '-'.  No batch holds more than ``max_records`` records (default
         ``SITE_BUDGET_BYTES`` of device records); the concatenation does not depend on ``max_records``."""
-        limit = SITE_BUDGET_BYTES // SITE_RECORD_BYTES if max_records is None else int(max_records)
-        if limit < 1:
-            raise ValueError("max_records must be at least 1")
+        limit = self._record_limit(max_records)
         sets = [(b, mt, list(motifs)) for b, mt, motifs in sets]
         totals = self._coverage_counts(sets)[5]
-        n, k = len(sets), 0
-        while k < n:
-            e, held = k + 1, int(totals[k])
-            while e < n and held + int(totals[e]) <= limit:
-                held += int(totals[e])
-                e += 1
-            args, keep, _ = self._coverage_args(sets[k:e])
-            first = 0
-            while True:                                    # one window, unless a single set exceeds the limit
-                cap = min(limit, held - first) if held else 0
-                rec = np.zeros(cap, dtype=UNEXPLAINED_DTYPE)
-                contig, pos, code = (np.zeros(max(cap, 1), dtype=t) for t in (np.uint32, np.uint32, np.uint8))
-                off = np.zeros(e - k + 1, dtype=np.uint64)
-                written = C.c_uint64(0)
-                _lib.check(self.lib.nm_motif_coverage_sites(*args, first, cap, _ptr(contig, C.c_uint32), _ptr(pos, C.c_uint32),
-                                                            _ptr(code, C.c_uint8), _ptr(off, C.c_uint64), C.byref(written)))
-                if int(off[-1]) != held or written.value != cap:
-                    raise _lib.NmScanError(f"nm_motif_coverage_sites delivered {written.value} of {cap} records ({int(off[-1])} in the call, {held} counted)")
-                rec["contig"], rec["pos"], rec["code"] = contig[:cap], pos[:cap], code[:cap]
-                cut = np.clip(off.astype(np.int64) - first, 0, cap)
-                rec["set"] = np.repeat(np.arange(k, e, dtype=np.uint32), np.diff(cut))
-                yield rec
-                first += cap
-                if first >= held:
-                    break
-            k = e
+        windows = self._record_windows(self.lib.nm_motif_coverage_sites, lambda k, e: self._coverage_args(sets[k:e])[0], totals, limit,
+                                       UNEXPLAINED_DTYPE, "set", "call")
+        for _, _, _, _, rec in windows:
+            yield rec
 
     def set_score_lanes(self, lanes: int):
         """2: consecutive ``score_into_device`` calls alternate between two streams, so that independent batches
