@@ -11,16 +11,18 @@ import logging as log
 import os
 import random
 import sys
+import threading
 import time
 import warnings
 from pathlib import Path
 
 import numpy as np
 
-from . import fasta, pileup as pileup_mod, postprocess
+from . import _lib, fasta, pileup as pileup_mod, postprocess
 from .argparser import __version__, create_parser
 from .find_motifs_bin import FilteredPileup, ProcessorConfig, allreduce_counts, discover, engine_scorer, use_native_allreduce
-from .engine import MAX_DEVICE_WINDOW_WIDTH
+from .engine import MAX_DEVICE_WINDOW_WIDTH, ScanEngine
+from .loading import PileupIngest, open_pileup, parser_threads, upload_assembly, wanted_contigs
 from .motif import MOD_TYPE_TO_CANONICAL
 from .shard import assign_bins, assign_contigs
 
@@ -56,112 +58,222 @@ def shared_setup(args, working_dir, rank=0):
 TIMINGS = {}          # seconds per phase of the last find_motifs_bin call in this process (written to OUT/logs/timings.*.json)
 
 
-def find_motifs_bin(args):
-    """main.py:46-104."""
-    TIMINGS.clear()
-    t_phase = [time.perf_counter()]
+class _Laps:
+    """``lap(name)`` adds the time since the lap before (or ``start``) to ``TIMINGS[key.format(name)]``."""
 
-    def lap(name):
+    def __init__(self, key="{}", start=None):
+        self.key, self.t = key, time.perf_counter() if start is None else start
+
+    def __call__(self, name):
         now = time.perf_counter()
-        TIMINGS[name] = TIMINGS.get(name, 0.0) + now - t_phase[0]
-        t_phase[0] = now
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    device = args.device if args.device is not None else local_rank
-    dist = None
-    if world > 1:
-        # torch is plumbing for the multi-rank run only (process group, RCCL); a single-GPU run never imports it
-        import torch
-        import torch.distributed as dist
-        if not torch.cuda.is_available():
-            raise RuntimeError("nanomotif_amd needs an AMD GPU (MI355X); there is no CPU fallback")
-        torch.cuda.set_device(device)
-        if not dist.is_initialized():
-            # RCCL unless NANOMOTIF_DIST_BACKEND=gloo (debugging aid: lets several ranks share one GPU with --device)
-            backend = os.environ.get("NANOMOTIF_DIST_BACKEND", "nccl")
-            if backend == "nccl":
-                dist.init_process_group("nccl", device_id=torch.device("cuda", device))
-            else:
-                dist.init_process_group(backend)
-    from ._lib import NmScanError
-    from . import _lib as _lib_codes
-    from .engine import ScanEngine
-    # The HIP runtime takes 0.1-0.3 s to come up in a fresh process: it does so on a side thread while this one reads the
-    # contig-bin table and parses the assembly (native code, the interpreter lock is released).  Fails loudly without a
-    # GPU: there is no CPU fallback.
-    import threading
-    started = {}
+        key = self.key.format(name)
+        TIMINGS[key] = TIMINGS.get(key, 0.0) + now - self.t
+        self.t = now
 
-    def start_engine():
+
+def _start_distributed(device):
+    """The process group of a multi-rank run; returns torch.distributed.  torch is plumbing for the multi-rank run only (process
+    group, RCCL); a single-GPU run never imports it."""
+    import torch
+    import torch.distributed as dist
+    if not torch.cuda.is_available():
+        raise RuntimeError("nanomotif_amd needs an AMD GPU (MI355X); there is no CPU fallback")
+    torch.cuda.set_device(device)
+    if not dist.is_initialized():
+        # RCCL unless NANOMOTIF_DIST_BACKEND=gloo (debugging aid: lets several ranks share one GPU with --device)
+        backend = os.environ.get("NANOMOTIF_DIST_BACKEND", "nccl")
+        if backend == "nccl":
+            dist.init_process_group("nccl", device_id=torch.device("cuda", device))
+        else:
+            dist.init_process_group(backend)
+    return dist
+
+
+class _EngineStart:
+    """The HIP runtime takes 0.1-0.3 s to come up in a fresh process: it does so on a side thread while the main one reads the
+    contig-bin table and parses the assembly (native code, the interpreter lock is released).  Fails loudly without a GPU: there is
+    no CPU fallback."""
+
+    def __init__(self, device):
+        self.device, self.eng, self.error = device, None, None
+        self.thread = threading.Thread(target=self._start, name="nm-engine-start")
+        self.thread.start()
+
+    def _start(self):
         try:
             # large device blocks stay with the process when the library frees them (nm_block_cache: memory another process used is
             # scrubbed by the driver on its way back in — the pre-filters' state planes waited 0.19 s for that at 1 Gbp — and hipFree
             # synchronises the device); NANOMOTIF_BLOCK_CACHE_GB=0 turns it off
-            from . import _lib as _l
             early = None
-            if _l.early_engine_thread is not None:       # (__main__.py: the context may exist already, made beside the imports)
-                _l.early_engine_thread.join()
-                _l.early_engine_thread, early, _l.early_engine = None, _l.early_engine, None
-                if _l.early_pin_thread is not None:
-                    _l.early_pin_thread.join()
-                    _l.early_pin_thread = None
+            if _lib.early_engine_thread is not None:     # (__main__.py: the context may exist already, made beside the imports)
+                _lib.early_engine_thread.join()
+                _lib.early_engine_thread, early, _lib.early_engine = None, _lib.early_engine, None
+                if _lib.early_pin_thread is not None:
+                    _lib.early_pin_thread.join()
+                    _lib.early_pin_thread = None
             cache_gb = float(os.environ.get("NANOMOTIF_BLOCK_CACHE_GB", "16"))
-            if early is not None and early[0] != device:
-                _l.load().nm_ctx_destroy(early[1])       # (another --device than the command line showed at a glance)
+            if early is not None and early[0] != self.device:
+                _lib.load().nm_ctx_destroy(early[1])     # (another --device than the command line showed at a glance)
                 early = None
             if cache_gb > 0 and not (early is not None and early[2]):
-                _l.use_block_cache(int(cache_gb * (1 << 30)))
-            started["eng"] = ScanEngine(device, ctx=early[1]) if early is not None else ScanEngine(device)
+                _lib.use_block_cache(int(cache_gb * (1 << 30)))
+            self.eng = ScanEngine(self.device, ctx=early[1]) if early is not None else ScanEngine(self.device)
             TIMINGS["engine_context_made_beside_the_imports"] = early is not None
-        except BaseException as e:               # re-raised on the main thread below
-            started["error"] = e
-    starter = threading.Thread(target=start_engine, name="nm-engine-start")
-    starter.start()
+        except BaseException as e:               # re-raised on the main thread by engine()
+            self.error = e
 
-    def engine():
-        starter.join()
-        if "error" in started:
-            e = started["error"]
-            if isinstance(e, NmScanError):
-                raise RuntimeError(f"nanomotif_amd needs an AMD GPU (MI355X); there is no CPU fallback ({e})") from e
-            raise e
-        return started["eng"]
+    def engine(self) -> ScanEngine:
+        self.thread.join()
+        if self.error is not None:
+            if isinstance(self.error, _lib.NmScanError):
+                raise RuntimeError(f"nanomotif_amd needs an AMD GPU (MI355X); there is no CPU fallback ({self.error})") from self.error
+            raise self.error
+        return self.eng
 
-    log.info("Starting nanomotif motif finder")
-    bin_contig = fasta.generate_contig_bin(args)
-    if not bin_contig:
-        log.error("No bin contig mapping found")
-        eng = engine()
-        eng.close()
-        return None
-    # A bgzip pileup: the host-only half of its indexed parse (tabix index, the walk over the BGZF blocks: half a second at 1 Gbp)
-    # starts NOW on a thread, for the contigs the bin table names — beside the HIP runtime coming up and the assembly being parsed.
-    # It is used when the assembly turns out to hold them all (else the plan is dropped and made again for the ones it holds).
-    plan_box = {}
-    if str(args.pileup).endswith(".gz") and os.path.exists(str(args.pileup) + ".tbi") and os.environ.get("NANOMOTIF_HOST_PARSER") != "1" \
-            and not any(fasta.ALIAS_SEP in c for c in bin_contig) and os.environ.get("NANOMOTIF_NO_PREPLAN") != "1":
-        guess = list(dict.fromkeys(fasta.original_name(c) for c in bin_contig))
+    def abandon(self):
+        """An error before the engine was put to use: whatever came up is closed."""
+        self.thread.join()
+        if self.eng is not None:
+            self.eng.close()
 
-        def make_plan():
-            try:
-                plan_box["plan"] = pileup_mod.BedPlan(str(args.pileup), str(args.pileup) + ".tbi", guess, threads=max(args.threads, 0) if args.threads > 1 else 0)
-            except BaseException as e:           # (the regular path will meet the same problem and report it)
-                plan_box["error"] = e
-        plan_box["thread"] = threading.Thread(target=make_plan, name="nm-bed-plan")
-        plan_box["thread"].start()
-    def drop_plan():
-        """An error path between the plan thread's start and its use: the thread is waited for (it is not a daemon: the process would
-        wait for its half-second walk at exit anyway) and the plan's mapping of the pileup released now, not by a finaliser."""
-        th = plan_box.pop("thread", None)
-        if th is not None:
-            th.join()
-        made = plan_box.pop("plan", None)
-        if made is not None:
-            made.close()
-        if "error" in plan_box:
-            log.debug(f"the pre-planned indexed parse failed (the regular path reports the cause): {plan_box.pop('error')!r}")
 
+class _PlanAhead:
+    """A bgzip pileup: the host-only half of its indexed parse (tabix index, the walk over the BGZF blocks: half a second at 1 Gbp)
+    starts NOW on a thread, for the contigs the bin table names — beside the HIP runtime coming up and the assembly being parsed.
+    ``take(wanted)`` hands the plan out when the assembly turns out to hold them all (else it is closed: ``open_pileup`` plans again
+    for the ones it holds)."""
+
+    def __init__(self, path: str, bin_contig: dict, threads: int):
+        self.thread = self.plan = self.error = None
+        if path.endswith(".gz") and os.path.exists(path + ".tbi") and os.environ.get("NANOMOTIF_HOST_PARSER") != "1" \
+                and not any(fasta.ALIAS_SEP in c for c in bin_contig) and os.environ.get("NANOMOTIF_NO_PREPLAN") != "1":
+            guess = wanted_contigs(path, bin_contig)
+
+            def make_plan():
+                try:
+                    self.plan = pileup_mod.BedPlan(path, path + ".tbi", guess, threads=threads)
+                except BaseException as e:       # (the regular path will meet the same problem and report it)
+                    self.error = e
+            self.thread = threading.Thread(target=make_plan, name="nm-bed-plan")
+            self.thread.start()
+
+    def take(self, wanted):
+        """The plan when it was made for exactly ``wanted``, else None; the thread is waited for (it is not a daemon: the process
+        would wait for its half-second walk at exit anyway) and a plan not handed out releases its mapping of the pileup now, not by
+        a finaliser."""
+        if self.thread is not None:
+            self.thread.join()
+        plan, self.thread, self.plan = self.plan, None, None
+        if self.error is not None:
+            log.debug(f"the pre-planned indexed parse failed (the regular path reports the cause): {self.error!r}")
+            self.error = None
+        if plan is not None and (wanted is None or list(plan.contigs) != list(wanted)):
+            plan.close()                         # the assembly lacks some of the binned contigs: plan again for the ones it holds
+            plan = None
+        return plan
+
+    def drop(self):
+        """An error path between the plan thread's start and its use."""
+        self.take(None)
+
+
+def _native_communicator_up(eng, dist, rank, world, device) -> bool:
+    """Whether EVERY rank has the C ABI's own RCCL communicator up, so that the per-round count tables can travel through it
+    (nm_allreduce_counts_host); torch.distributed only carries the 128-byte id to the ranks.  Every rank must end up on the SAME path.
+    What is guaranteed: a rank on which librccl does not load says so BEFORE anybody enters ncclCommInitRank (every rank makes a unique
+    id as a probe; MIN all-reduce), and a rank whose ncclCommInitRank RETURNS an error says so after it (second MIN all-reduce) — the
+    run then falls back to torch.distributed as a whole.  What no agreement can cover is a rank that never arrives inside the
+    collective init (it died, or hangs): the others would wait there for ever, so the init runs under a watchdog that ends this
+    process with a message (NANOMOTIF_COMM_TIMEOUT seconds, default 300)."""
+    import torch
+
+    def comm_init_watched(uid):
+        limit = float(os.environ.get("NANOMOTIF_COMM_TIMEOUT", "300"))
+        done = threading.Event()
+
+        def watchdog():
+            if not done.wait(limit):
+                sys.stderr.write(f"rank {rank}: nm_comm_init did not return within {limit:.0f} s (a rank missing from ncclCommInitRank?): "
+                                 "giving up; NANOMOTIF_ALLREDUCE=torch takes torch.distributed instead\n")
+                sys.stderr.flush()
+                os._exit(3)
+        threading.Thread(target=watchdog, name="nm-comm-watchdog", daemon=True).start()
+        try:
+            eng.comm_init(rank, world, uid)
+        finally:
+            done.set()
+
+    def agreed(ok_here: int) -> bool:
+        flag = torch.tensor([ok_here], dtype=torch.int32, device=torch.device("cuda", device))
+        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+        return int(flag[0]) == 1
+
+    ok = 1
+    uid = [None]
+    try:
+        probe = eng.comm_unique_id()             # EVERY rank: proves that librccl loads here before anybody waits in CommInitRank
+        uid = [probe if rank == 0 else None]
+    except _lib.NmScanError as e:
+        ok = 0
+        log.warning(f"rank {rank}: nm_comm_unique_id failed ({e})")
+    if agreed(ok):
+        dist.broadcast_object_list(uid, src=0)
+        try:
+            comm_init_watched(uid[0])
+        except _lib.NmScanError as e:
+            ok = 0
+            log.warning(f"rank {rank}: nm_comm_init failed ({e})")
+    else:
+        ok = 0
+    if agreed(ok):
+        log.info(f"rank {rank}: count tables all-reduced by nm_allreduce_counts (RCCL, {eng.comm_info()['world']} ranks)")
+        return True
+    log.warning(f"rank {rank}: the C ABI's communicator is not up on every rank: count tables go through torch.distributed")
+    return False
+
+
+def _filter_stage(eng, cfg, assembly, table, names, shard, world, lap):
+    """This rank's contigs of ``names`` (shard ``shard`` of ``world``) and the opened pileup ``table`` -> the engine's planes: upload,
+    the pre-filters and the classification, the window pipeline, the merge stage's classification.  Closes ``table`` (and a device
+    assembly once its packed bases have served).  Returns (this rank's FilteredPileup, window store, extractor)."""
+    parts = assign_contigs([fasta.assembly_length(assembly, c) for c in names], world, bins=[cfg.bin_contig[c] for c in names])
+    mine = [names[i] for i in parts[shard]]
+    all_bins = sorted(set(cfg.bin_contig[c] for c in names))         # bin ids must be identical on every rank
+    upload_assembly(eng, assembly, mine, [cfg.bin_contig[c] for c in mine], all_bins)
+    part = _Laps("filters_{}_s", start=lap.t)    # (what upload_filter_s is made of, from the end of the phase before: the pileup parse)
+    part("upload_assembly")
+    ingest = PileupIngest(eng, table, mine)
+    part("tables")
+    t0 = time.perf_counter()
+    low, high = cfg.methylation_threshold_low, cfg.methylation_threshold_high
+    res = ingest.classify(lambda mt: mt, low, high)
+    part("ingest")
+    if 2 * cfg.padding + 1 > MAX_DEVICE_WINDOW_WIDTH:
+        # a search frame beyond the device's window planes (default 40; nobody runs such frames): windows are extracted and
+        # filtered on the host (search.HostWindowStore), candidates scored on the device (far-reaching ones by the plain kernel)
+        log.info(f"search frame {cfg.search_frame_size}: windows of {2 * cfg.padding + 1} positions stay on the host")
+        store, extractor = None, None
+    else:
+        store, extractor = device_window_pipeline(eng, {c: fasta.assembly_length(assembly, c) for c in names}, mine, cfg.padding, world)
+    if isinstance(assembly, fasta.DeviceAssembly) and extractor is not None:
+        assembly.close()                         # the packed bases have served; (host windows would read contigs back from them)
+    # (confident_rows speaks about the LAST classification: before the merge stage's)
+    rows = eng.confident_rows() if extractor is None else tuple(np.zeros(0, dt) for dt in (np.uint32, np.uint32, np.uint8, np.int8))
+    if (low, high) == (0.3, 0.7):
+        for mt in pileup_mod.MOD_TYPES:
+            eng.alias_label((mt, "merge"), mt)
+    else:                 # the merge stage always runs at 0.3 / 0.7 (find_motifs_bin.py:569, 1436): a second classification
+        ingest.classify(lambda mt: (mt, "merge"), 0.3, 0.7)
+    log.info(f"pileup: {res['n_kept']:,} rows after the device-side filters ({time.perf_counter() - t0:.1f}s)")
+    part("window_pipeline")
+    ingest.close()
+    part("table_close")
+    lap("upload_filter_s")
+    return FilteredPileup(mine, *rows, res["kept"]), store, extractor
+
+
+def _load_assembly(args, starting, plans, bin_contig, threads, lap):
+    """(engine, assembly with the aliased placements of ``bin_contig``); on an error the engine that came up and the plan go."""
     log.info("Loading assembly")
     # A plain-text assembly is parsed ON THE GPU (nm_fasta_parse_device: the host only moves the file through pinned slabs; the
     # bases never become a host array, the planes are packed from the parser's device buffer); a .gz assembly and
@@ -169,90 +281,81 @@ def find_motifs_bin(args):
     device_fasta = not str(args.assembly).endswith(".gz") and os.environ.get("NANOMOTIF_HOST_FASTA") != "1"
     try:
         if device_fasta:
-            eng = engine()
+            eng = starting.engine()
             lap("engine_start_s")
-            assembly = fasta.DeviceAssembly(eng, args.assembly, threads=max(args.threads, 0) if args.threads > 1 else 0)
+            assembly = fasta.DeviceAssembly(eng, args.assembly, threads=threads)
             TIMINGS["assembly_reading_s"] = assembly.seconds_reading
         else:
             assembly = fasta.load_fasta(args.assembly)
-        fasta.add_alias_sequences(assembly, bin_contig)      # a contig listed under several bins is a member of each
+        fasta.add_alias_sequences(assembly, bin_contig)          # a contig listed under several bins is a member of each
     except BaseException:
-        starter.join()
-        if "eng" in started:
-            started["eng"].close()
-        drop_plan()
+        starting.abandon()
+        plans.drop()
         raise
     lap("assembly_s")
     TIMINGS["assembly_parser"] = "device" if device_fasta else "host"
     if not device_fasta:
-        eng = engine()
+        eng = starting.engine()
         lap("engine_start_s")                    # what the assembly did not hide
-    log.info("Identifying motifs")
-    cfg = ProcessorConfig(assembly=assembly, pileup_path=args.pileup, bin_contig=bin_contig, threads=args.threads,
-                          search_frame_size=args.search_frame_size, methylation_threshold_low=args.methylation_threshold_low,
-                          methylation_threshold_high=args.methylation_threshold_high,
-                          minimum_kl_divergence=args.minimum_kl_divergence, score_threshold=args.min_motif_score,
-                          verbose=args.verbose, log_dir=args.out + "/logs", seed=args.seed, output_dir=args.out)
-    bgzip = cfg.pileup_path.endswith(".gz")
-    if bgzip and not os.path.exists(cfg.pileup_path + ".tbi"):
-        drop_plan()
-        raise FileNotFoundError(f"Tabix index for {cfg.pileup_path} not found.")     # find_motifs_bin.py:383-384
+    return eng, assembly
+
+
+def _open_table(eng, path, names, bin_contig, plans, threads, lap):
+    """The pileup's table for ``names`` (the binned contigs the assembly holds), through the plan made ahead when it is still the right
+    one; logs what was read and records the ``pileup_*`` timings."""
     t0 = time.perf_counter()
-    # native reader, raw rows kept in native memory; a bgzip pileup is read through its tabix index: only the blocks
-    # of the contigs that are in a bin and in the assembly (find_motifs_bin.py:233-246 fetches per bin)
-    wanted = list(dict.fromkeys(fasta.original_name(c) for c in cfg.bin_contig if c in assembly)) if bgzip else None
-    # the pileup is parsed ON THE GPU (nm_bed_parse_device: the host only moves the file through pinned slabs — the BGZF
-    # blocks of a bgzip file are inflated into them by the copy threads, the tabix subset alike; every row equals the host
-    # parser's bit for bit); a gzip stream that is not bgzip, a contig listed under several bins (its rows are needed twice)
-    # and NANOMOTIF_HOST_PARSER=1 take the host parser
-    table = None
-    plan = None
-    if "thread" in plan_box:
-        plan_box.pop("thread").join()
-        plan = plan_box.pop("plan", None)
-        if "error" in plan_box:
-            log.debug(f"the pre-planned indexed parse failed (the regular path reports the cause): {plan_box.pop('error')!r}")
-        if plan is not None and (wanted is None or list(plan.contigs) != list(wanted)):
-            plan.close()                         # the assembly lacks some of the binned contigs: plan again for the ones it holds
-            plan = None
-        if plan is not None:
-            TIMINGS["pileup_plan_s_on_a_thread"] = plan.seconds
-    if os.environ.get("NANOMOTIF_HOST_PARSER") != "1" and not any(fasta.ALIAS_SEP in c for c in cfg.bin_contig):
-        try:
-            try:
-                table = pileup_mod.DevicePileup(eng, cfg.pileup_path, threads=max(args.threads, 0) if args.threads > 1 else 0,
-                                                contigs=wanted, index_path=cfg.pileup_path + ".tbi" if bgzip else None, plan=plan)
-            except BaseException:
-                if plan is not None:             # a final error of the parser: the plan's mapping goes back now
-                    plan.close()
-                    plan = None
-                raise
-            how = (f", tabix-indexed: {table.bytes_inflated / 1e6:.1f} MB inflated for {len(wanted)} contigs" if table.indexed else "")
-            log.info(f"pileup: {len(table):,} rows parsed on the device ({time.perf_counter() - t0:.1f}s, {table.seconds_reading:.1f}s of it "
-                     f"moving the file{how})")
-        except NmScanError as e:
-            if e.code != _lib_codes.NM_EDECLINED:
-                raise
-            log.info(f"pileup: the device parser declined ({e}); using the host parser")
-    if table is None:
-        table = pileup_mod.NativePileup(cfg.pileup_path, contigs=wanted, index_path=cfg.pileup_path + ".tbi" if bgzip else None)
-        how = (f", tabix-indexed: {table.bytes_inflated / 1e6:.1f} MB inflated for {len(wanted)} contigs" if table.indexed else "")
-        log.info(f"pileup: {len(table):,} rows read ({time.perf_counter() - t0:.1f}s{how})")
+    wanted = wanted_contigs(path, names)
+    plan = plans.take(wanted)
     if plan is not None:
-        # (closing the plan unmaps the pileup: 3.5 million page-table entries at 1 Gbp — off the critical path, on a thread of its own)
-        threading.Thread(target=plan.close, name="nm-bed-plan-close", daemon=False).start()
+        TIMINGS["pileup_plan_s_on_a_thread"] = plan.seconds
+    table = open_pileup(eng, path, wanted, bin_contig, threads, plan=plan)
     on_device = isinstance(table, pileup_mod.DevicePileup)
+    how = f", tabix-indexed: {table.bytes_inflated / 1e6:.1f} MB inflated for {len(wanted)} contigs" if table.indexed else ""
+    if on_device:
+        log.info(f"pileup: {len(table):,} rows parsed on the device ({time.perf_counter() - t0:.1f}s, {table.seconds_reading:.1f}s of it "
+                 f"moving the file{how})")
+    else:
+        log.info(f"pileup: {len(table):,} rows read ({time.perf_counter() - t0:.1f}s{how})")
     lap("pileup_parse_s")
     TIMINGS["pileup_parser"] = "device" if on_device else "host"
     if on_device:
         TIMINGS.update(pileup_reading_s=table.seconds_reading, pileup_inflating_s=table.seconds_inflating, pileup_parsing_s=table.seconds_parsing,
                        pileup_in_parser_s=table.seconds)       # (the rest of pileup_parse_s: the tabix index, the walk over the BGZF blocks, the tables)
     TIMINGS["pileup_rows"] = len(table)
+    return table
+
+
+def find_motifs_bin(args):
+    """main.py:46-104."""
+    TIMINGS.clear()
+    lap = _Laps()
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    device = args.device if args.device is not None else int(os.environ.get("LOCAL_RANK", "0"))
+    dist = _start_distributed(device) if world > 1 else None
+    starting = _EngineStart(device)
+    log.info("Starting nanomotif motif finder")
+    bin_contig = fasta.generate_contig_bin(args)
+    if not bin_contig:
+        log.error("No bin contig mapping found")
+        starting.engine().close()
+        return None
+    threads = parser_threads(args)
+    plans = _PlanAhead(str(args.pileup), bin_contig, threads)
+
+    eng, assembly = _load_assembly(args, starting, plans, bin_contig, threads, lap)
+    log.info("Identifying motifs")
+    cfg = ProcessorConfig(assembly=assembly, pileup_path=args.pileup, bin_contig=bin_contig, threads=args.threads,
+                          search_frame_size=args.search_frame_size, methylation_threshold_low=args.methylation_threshold_low,
+                          methylation_threshold_high=args.methylation_threshold_high,
+                          minimum_kl_divergence=args.minimum_kl_divergence, score_threshold=args.min_motif_score,
+                          verbose=args.verbose, log_dir=args.out + "/logs", seed=args.seed, output_dir=args.out)
+    names = [c for c in cfg.bin_contig if c in assembly]             # the binned contigs the assembly holds
+    table = _open_table(eng, cfg.pileup_path, names, cfg.bin_contig, plans, threads, lap)
 
     # engine: this rank's contigs (all contigs that belong to a bin).  Several GPUs: whole bins per GPU when they
     # balance (independent searches, no collective until the rows are gathered), else the contigs of every bin are
     # sharded and the count tables all-reduced every round.
-    names = [c for c in cfg.bin_contig if c in assembly]
     bin_order = list(dict.fromkeys(cfg.bin_contig.values()))         # task order of the reference (:152-171)
     by_bins = None
     if world > 1 and args.shard != "contigs":
@@ -270,140 +373,20 @@ def find_motifs_bin(args):
             return _gather_rows(args, [], rank, gather_world, bin_order)
     else:
         gather_world = 1
-    if world > 1 and dist.get_backend() == "nccl" and os.environ.get("NANOMOTIF_ALLREDUCE", "native") == "native":
-        # the per-round count tables travel through the C ABI's own RCCL communicator (nm_allreduce_counts_host);
-        # torch.distributed only carried the 128-byte id to the ranks.  Every rank must end up on the SAME path.  What is
-        # guaranteed: a rank on which librccl does not load says so BEFORE anybody enters ncclCommInitRank (every rank makes
-        # a unique id as a probe; MIN all-reduce), and a rank whose ncclCommInitRank RETURNS an error says so after it (second
-        # MIN all-reduce) — the run then falls back to torch.distributed as a whole.  What no agreement can cover is a rank
-        # that never arrives inside the collective init (it died, or hangs): the others would wait there for ever, so the
-        # init runs under a watchdog that ends this process with a message (NANOMOTIF_COMM_TIMEOUT seconds, default 300)
-        import threading
-        import torch
-
-        def comm_init_watched():
-            limit = float(os.environ.get("NANOMOTIF_COMM_TIMEOUT", "300"))
-            done = threading.Event()
-
-            def watchdog():
-                if not done.wait(limit):
-                    sys.stderr.write(f"rank {rank}: nm_comm_init did not return within {limit:.0f} s (a rank missing from ncclCommInitRank?): "
-                                     "giving up; NANOMOTIF_ALLREDUCE=torch takes torch.distributed instead\n")
-                    sys.stderr.flush()
-                    os._exit(3)
-            threading.Thread(target=watchdog, name="nm-comm-watchdog", daemon=True).start()
-            try:
-                eng.comm_init(rank, world, uid[0])
-            finally:
-                done.set()
-
-        def agreed(ok_here: int) -> bool:
-            flag = torch.tensor([ok_here], dtype=torch.int32, device=torch.device("cuda", device))
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-            return int(flag[0]) == 1
-
-        ok = 1
-        uid = [None]
-        try:
-            probe = eng.comm_unique_id()            # EVERY rank: proves that librccl loads here before anybody waits in CommInitRank
-            uid = [probe if rank == 0 else None]
-        except NmScanError as e:
-            ok = 0
-            log.warning(f"rank {rank}: nm_comm_unique_id failed ({e})")
-        if agreed(ok):
-            dist.broadcast_object_list(uid, src=0)
-            try:
-                comm_init_watched()
-            except NmScanError as e:
-                ok = 0
-                log.warning(f"rank {rank}: nm_comm_init failed ({e})")
-        else:
-            ok = 0
-        if agreed(ok):
-            use_native_allreduce(eng)
-            log.info(f"rank {rank}: count tables all-reduced by nm_allreduce_counts (RCCL, {eng.comm_info()['world']} ranks)")
-        else:
-            log.warning(f"rank {rank}: the C ABI's communicator is not up on every rank: count tables go through torch.distributed")
+    if world > 1 and dist.get_backend() == "nccl" and os.environ.get("NANOMOTIF_ALLREDUCE", "native") == "native" \
+            and _native_communicator_up(eng, dist, rank, world, device):
+        use_native_allreduce(eng)
     try:
-        parts = assign_contigs([fasta.assembly_length(assembly, c) for c in names], world, bins=[cfg.bin_contig[c] for c in names])
-        mine = [names[i] for i in parts[rank if gather_world == 1 else 0]]
-        all_bins = sorted(set(cfg.bin_contig[c] for c in names))       # bin ids must be identical on every rank
-        if device_fasta:
-            eng.upload_assembly_fasta(assembly, mine, [cfg.bin_contig[c] for c in mine], bin_names=all_bins)
-        else:
-            eng.upload_assembly(mine, [assembly[c] for c in mine], [cfg.bin_contig[c] for c in mine], bin_names=all_bins)
-        t_part = t_phase[0]                      # (the end of the phase before: the pileup parse)
-
-        def part(name):                          # (what upload_filter_s is made of: TIMINGS["filters_<name>_s"])
-            nonlocal t_part
-            now = time.perf_counter()
-            TIMINGS["filters_" + name + "_s"] = TIMINGS.get("filters_" + name + "_s", 0.0) + now - t_part
-            t_part = now
-        part("upload_assembly")
-        # raw rows -> device: the three pre-filters, classification, confident-row list (rows of contigs that are in no
-        # bin or on another rank are ignored: the reference joins with contig -> bin after filtering, find_motifs_bin.py:416)
-        local_id = {c: i for i, c in enumerate(mine)}
-        lut = np.array([local_id.get(n, 0xFFFFFFFF) for n in table.contig_names], dtype=np.uint32)
-        # further placements of a contig listed under several bins: the contig's rows once more per placement
-        file_id = {n: i for i, n in enumerate(table.contig_names)}
-        placements = [(file_id[fasta.original_name(c)], local_id[c]) for c in mine
-                      if fasta.ALIAS_SEP in c and fasta.original_name(c) in file_id]
-        file_contig = table.file_contig_column().copy() if placements else None
-        cols = None if on_device else table.ingest_columns(lut)          # views in the engine's types; refuses positions >= 4 Gbp
-        labels = {i: (mt, MOD_TYPE_TO_CANONICAL[mt]) for i, mt in enumerate(pileup_mod.MOD_TYPES)}
-        t0 = time.perf_counter()
-        low, high = cfg.methylation_threshold_low, cfg.methylation_threshold_high
-        # large pileups go to the device in parts of whole contigs (bounds the memory of the raw rows and filter scratch)
-        part_rows = int(os.environ.get("NANOMOTIF_INGEST_PART_ROWS", 250_000_000))
-        extra = []
-        for fid, local in placements:
-            sel = np.flatnonzero(file_contig == fid)
-            extra.append(dict(contig=np.full(len(sel), local, np.uint32), **{k: cols[k][sel] for k in ("position", "mod_type", "strand", "fraction_mod", "nvalid_cov")}))
-        part("tables")
-        if on_device:
-            res = eng.ingest_device_pileup(table, lut, labels, low=low, high=high, max_part_rows=part_rows)
-        else:
-            res = eng.ingest_pileup(cols["contig"], cols["position"], cols["mod_type"], cols["strand"], cols["fraction_mod"],
-                                    cols["nvalid_cov"], labels, low=low, high=high, want_rows=False, max_part_rows=part_rows, extra_parts=extra)
-        part("ingest")
-        if 2 * cfg.padding + 1 > MAX_DEVICE_WINDOW_WIDTH:
-            # a search frame beyond the device's window planes (default 40; nobody runs such frames): windows are extracted and
-            # filtered on the host (search.HostWindowStore), candidates scored on the device (far-reaching ones by the plain kernel)
-            log.info(f"search frame {cfg.search_frame_size}: windows of {2 * cfg.padding + 1} positions stay on the host")
-            store, extractor = None, None
-        else:
-            store, extractor = device_window_pipeline(eng, {c: fasta.assembly_length(assembly, c) for c in names}, mine, cfg.padding, world)
-        if device_fasta and extractor is not None:
-            assembly.close()                     # the packed bases have served; (host windows would read contigs back from them)
-        rows_part = eng.confident_rows() if extractor is None else tuple(np.zeros(0, dt) for dt in (np.uint32, np.uint32, np.uint8, np.int8))
-        if (low, high) == (0.3, 0.7):
-            for mt in pileup_mod.MOD_TYPES:
-                eng.alias_label((mt, "merge"), mt)
-        elif on_device:   # the merge stage always runs at 0.3 / 0.7 (find_motifs_bin.py:569, 1436): a second classification
-            eng.ingest_device_pileup(table, lut, {i: ((mt, "merge"), MOD_TYPE_TO_CANONICAL[mt]) for i, mt in enumerate(pileup_mod.MOD_TYPES)},
-                                     low=0.3, high=0.7, max_part_rows=part_rows)
-        else:
-            eng.ingest_pileup(cols["contig"], cols["position"], cols["mod_type"], cols["strand"], cols["fraction_mod"],
-                              cols["nvalid_cov"], {i: ((mt, "merge"), MOD_TYPE_TO_CANONICAL[mt]) for i, mt in enumerate(pileup_mod.MOD_TYPES)},
-                              low=0.3, high=0.7, want_rows=False, max_part_rows=part_rows, extra_parts=extra)
-        log.info(f"pileup: {res['n_kept']:,} rows after the device-side filters ({time.perf_counter() - t0:.1f}s)")
-        part("window_pipeline")
-        del cols
-        table.close()
-        part("table_close")
-        lap("upload_filter_s")
-        part = FilteredPileup(mine, *rows_part, res["kept"])
-        if world > 1:
+        filtered, store, extractor = _filter_stage(eng, cfg, assembly, table, names, rank if gather_world == 1 else 0, world, lap)
+        if world > 1:                            # (contigs sharded over the ranks: every rank searches on the rows of all)
             gathered = [None] * world
-            dist.all_gather_object(gathered, part)
+            dist.all_gather_object(gathered, filtered)
             filtered = FilteredPileup.merge(gathered)
-        else:
-            filtered = part
         if filtered.kept.sum() == 0:
             log.info("No pileup data after filtering, skipping")
             return _gather_rows(args, [], rank, gather_world, bin_order) if gather_world > 1 else None
-        scorer = engine_scorer(eng, low, high, use_dist=world > 1)
-        rows, scorer = discover(cfg, filtered, scorer, rank=0 if gather_world > 1 else rank, bgzip_order=bgzip,
+        scorer = engine_scorer(eng, cfg.methylation_threshold_low, cfg.methylation_threshold_high, use_dist=world > 1)
+        rows, scorer = discover(cfg, filtered, scorer, rank=0 if gather_world > 1 else rank, bgzip_order=cfg.pileup_path.endswith(".gz"),
                                 window_store=store, extractor=extractor)
         if getattr(eng, "wide_scored", 0):
             log.info(f"{eng.wide_scored} candidates reaching further than 95 positions from the modified base scored by nm_score_batch_wide")
@@ -415,7 +398,7 @@ def find_motifs_bin(args):
     finally:
         # also on the early returns and on exceptions: the module-global reducer must not outlive its engine
         use_native_allreduce(None)
-        if device_fasta:
+        if isinstance(assembly, fasta.DeviceAssembly):
             assembly.close()
         eng.close()
 
@@ -611,44 +594,17 @@ def main(argv=None):
         if result is None and rank == 0:
             with open(os.path.join(args.out, "bin-motifs.tsv"), "w") as f:     # main.py:317-321
                 f.write(HEADER)
-    elif args.command == "motif_sites":
-        from . import motif_sites
+    elif args.command in ("motif_sites", "motif_coverage", "motif_compare"):
+        import importlib
         if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
-            sys.stderr.write("nanomotif motif_sites runs on one GPU: start it without a multi-rank launcher\n")
+            sys.stderr.write(f"nanomotif {args.command} runs on one GPU: start it without a multi-rank launcher\n")
             sys.exit(2)
+        command = importlib.import_module("." + args.command, __package__)
         shared_setup(args, args.out)
-        status = motif_sites.run(args)
+        status = command.run(args)
         try:
-            with open(os.path.join(args.out, "logs", "timings.motif_sites.json"), "w") as f:
-                json.dump(motif_sites.TIMINGS, f, indent=1)
-        except OSError:
-            pass
-        if status:
-            sys.exit(status)
-    elif args.command == "motif_coverage":
-        from . import motif_coverage
-        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
-            sys.stderr.write("nanomotif motif_coverage runs on one GPU: start it without a multi-rank launcher\n")
-            sys.exit(2)
-        shared_setup(args, args.out)
-        status = motif_coverage.run(args)
-        try:
-            with open(os.path.join(args.out, "logs", "timings.motif_coverage.json"), "w") as f:
-                json.dump(motif_coverage.TIMINGS, f, indent=1)
-        except OSError:
-            pass
-        if status:
-            sys.exit(status)
-    elif args.command == "motif_compare":
-        from . import motif_compare
-        if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
-            sys.stderr.write("nanomotif motif_compare runs on one GPU: start it without a multi-rank launcher\n")
-            sys.exit(2)
-        shared_setup(args, args.out)
-        status = motif_compare.run(args)
-        try:
-            with open(os.path.join(args.out, "logs", "timings.motif_compare.json"), "w") as f:
-                json.dump(motif_compare.TIMINGS, f, indent=1)
+            with open(os.path.join(args.out, "logs", f"timings.{args.command}.json"), "w") as f:
+                json.dump(command.TIMINGS, f, indent=1)
         except OSError:
             pass
         if status:

@@ -7,7 +7,7 @@ pileups are resident on one engine (sample A under the mod types' names, sample 
 motif is classified ONCE by its state in both (``ScanEngine.motif_compare_counts`` / ``motif_compare_sites``, nm_motif_compare_*): the
 joint 3 x 3 table of (mod, nomod, nocall) in A x (mod, nomod, nocall) in B, which two ``motif_sites`` runs only give the marginals of.
 
-Both pileups go through the ingest path of ``motif_discovery`` (``motif_sites.load_engine``: same readers, pre-filters, thresholds), so
+Both pileups go through the ingest path of ``motif_discovery`` (``loading.load_engine``: same readers, pre-filters, thresholds), so
 ``n_mod_a`` / ``n_nomod_a`` are the counts a ``bin-motifs.tsv`` of sample A holds for the motif, and likewise for B.  ``--bin_motifs``
 takes one or more files (typically discovery on A and on B); the candidates are ``candidates_of_bin_motifs`` of each in order,
 complements included, a (bin, motif, mod_type, position) seen before is not repeated.  A mod type is compared when at least one of the
@@ -34,10 +34,11 @@ import time
 
 import numpy as np
 
-from . import _lib, fasta, pileup as pileup_mod
+from . import fasta
 from .engine import SITE_STATES, SWITCHED, TRANSITIONS, ScanEngine
+from .loading import kept_mod_types
 from .motif import MOD_TYPE_TO_CANONICAL, Motif
-from .motif_sites import candidates_of_bin_motifs, format_sites, load_engine
+from .motif_sites import candidates_of_files, open_run, table_text, write_site_batches      # (candidates_of_files: this command's reader of --bin_motifs)
 
 MAIN_NAME = "motif-compare.tsv"
 CONTIGS_NAME = "motif-compare-contigs.tsv"
@@ -102,10 +103,6 @@ def derived_columns(nine) -> list:
     return [str(mod_a), str(nomod_a), str(mod_b), str(nomod_b)] + degrees + ["nan" if math.isnan(p) else "%.6g" % p]
 
 
-def _lines(header, rows) -> str:
-    return "\n".join(["\t".join(header)] + ["\t".join(str(x) for x in r) for r in rows]) + "\n"
-
-
 def _nine(table):
     t = np.asarray(table, dtype=np.int64).reshape(-1, 18).sum(axis=0)
     return [int(x) for x in t[:9] + t[9:]]
@@ -117,7 +114,7 @@ def format_main(cands, tables) -> str:
     for c, t in zip(cands, tables):
         nine = _nine(t)
         rows.append([c.bin, c.motif, c.mod_type, c.mod_position] + nine + derived_columns(nine))
-    return _lines(MAIN_HEADER, rows)
+    return table_text(MAIN_HEADER, rows)
 
 
 def format_contigs(cands, contig_names, tables) -> str:
@@ -127,7 +124,7 @@ def format_contigs(cands, contig_names, tables) -> str:
         t = np.asarray(t, dtype=np.int64).reshape(-1, 18)
         for name, row in zip(names, t):
             rows.append([c.bin, fasta.original_name(name), c.motif, c.mod_type, c.mod_position] + [int(x) for x in row])
-    return _lines(CONTIGS_HEADER, rows)
+    return table_text(CONTIGS_HEADER, rows)
 
 
 def format_bins(keys, tables) -> str:
@@ -136,68 +133,25 @@ def format_bins(keys, tables) -> str:
     for (b, mt), t in zip(keys, tables):
         nine = _nine(t)
         rows.append([b, mt] + nine + derived_columns(nine))
-    return _lines(BINS_HEADER, rows)
-
-
-def compared_mod_types(eng: ScanEngine) -> list:
-    """The mod types of which at least one of the two ingests kept a pileup row on a resident contig, in slot order."""
-    kept = [np.asarray(r["kept"]) for r in eng.pileup_ingests]
-    present = {mt for code, mt in enumerate(pileup_mod.MOD_TYPES) if any(k[:, code].any() for k in kept)}
-    return [mt for mt in sorted((m for m in pileup_mod.MOD_TYPES if m in eng.slot_of_mod), key=eng.slot_of_mod.get) if mt in present]
-
-
-def candidates_of_files(paths) -> list:
-    """The candidates of several bin-motifs.tsv in order; a (bin, motif, mod_type, position) seen before is not repeated."""
-    out, seen = [], set()
-    for path in paths:
-        for c in candidates_of_bin_motifs(path):
-            if c.key not in seen:
-                seen.add(c.key)
-                out.append(c)
-    return out
+    return table_text(BINS_HEADER, rows)
 
 
 def export_switched(eng: ScanEngine, cands: list, transitions, bed_file, max_records=None):
     """Write the records of ``transitions`` of ``cands`` to the open binary file ``bed_file``; returns (records, seconds in the engine,
     seconds in the text writer)."""
-    t_eng = t_text = 0.0
-    n_records = 0
-    t0 = time.perf_counter()
-    for sb in eng.motif_compare_sites([c.engine_candidate() for c in cands], labels_of, transitions=transitions, max_records=max_records):
-        t1 = time.perf_counter()
-        t_eng += t1 - t0
-        group = cands[sb.first_candidate:sb.first_candidate + sb.n_candidates]
-        rec = sb.records
-        if len(rec):
-            seg_begin = np.searchsorted(rec["candidate"], np.arange(sb.first_candidate, sb.first_candidate + sb.n_candidates + 1))
-            bed_file.write(format_sites(rec["contig"], rec["pos"], rec["code"], seg_begin, [c.name for c in group], [c.bin for c in group],
-                                        [fasta.original_name(n) for n in eng.contig_names], symbol="nm_motif_compare_text"))
-            n_records += len(rec)
-        t0 = time.perf_counter()
-        t_text += t0 - t1
-    return n_records, t_eng + time.perf_counter() - t0, t_text
+    batches = eng.motif_compare_sites([c.engine_candidate() for c in cands], labels_of, transitions=transitions, max_records=max_records)
+    return write_site_batches(eng, batches, cands, bed_file, symbol="nm_motif_compare_text")
 
 
 def run(args) -> int:
     """The command.  Returns the process's exit status."""
-    TIMINGS.clear()
-    if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
-        log.error("motif_compare runs on one GPU: start it without a multi-rank launcher (WORLD_SIZE is %s)", os.environ["WORLD_SIZE"])
-        return 2
     transitions = SWITCHED if args.transitions is None else args.transitions if isinstance(args.transitions, tuple) else parse_transitions(args.transitions)
-    files = [args.bin_motifs] if isinstance(args.bin_motifs, str) else list(args.bin_motifs)
-    cands = candidates_of_files(files)
-    log.info(f"{len(cands)} (bin, motif) candidates from {', '.join(files)}")
-    device = args.device if args.device is not None else int(os.environ.get("LOCAL_RANK", "0") or 0)
-    t0 = time.perf_counter()
-    try:
-        eng = load_engine(args, device, pileups=[(args.pileup_a, None), (args.pileup_b, lambda mt: mt + SAMPLE_B_SUFFIX)])
-    except _lib.NmScanError as e:
-        raise RuntimeError(f"nanomotif_amd needs an AMD GPU (MI355X); there is no CPU fallback ({e})") from e
-    TIMINGS["ingest_s"] = time.perf_counter() - t0
+    eng, cands, status = open_run("motif_compare", args, TIMINGS, pileups=[(args.pileup_a, None), (args.pileup_b, lambda mt: mt + SAMPLE_B_SUFFIX)])
+    if eng is None:
+        return status
     TIMINGS["ingest_a_s"], TIMINGS["ingest_b_s"] = (r["seconds"] for r in eng.pileup_ingests)
     try:
-        mod_types = compared_mod_types(eng)
+        mod_types = kept_mod_types(eng)
         known = []
         for c in cands:
             if c.bin not in eng.bin_index:

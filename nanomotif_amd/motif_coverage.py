@@ -7,7 +7,7 @@ stage rewrites the motifs, and never into a file.  This command takes the rows t
 motifs are redundant (every methylated site they hit is also hit by another motif of the bin) and, on request, where the unexplained
 methylated positions are.
 
-Arguments and ingest are those of ``motif_sites`` (``motif_sites.load_engine``, ``candidates_of_bin_motifs``: complements included,
+Arguments and ingest are those of ``motif_sites`` (``loading.load_engine``, ``candidates_of_bin_motifs``: complements included,
 duplicates dropped), so the state planes are the ones ``bin-motifs.tsv`` was scored on.  Every bin with a resident contig x every mod
 type present in the pileup is a SET, also when ``bin-motifs.tsv`` has no motif for it: that row is how a bin with methylation and
 nothing discovered is found.  Sets in the order sorted bin names, mod types in slot order, motifs in file order.
@@ -19,16 +19,16 @@ position, '+' before '-').
 """
 from __future__ import annotations
 
-import ctypes as C
 import logging as log
 import os
 import time
 
 import numpy as np
 
-from . import _lib, fasta, pileup as pileup_mod
+from . import fasta
 from .engine import SITE_MINUS, ScanEngine
-from .motif_sites import candidates_of_bin_motifs, load_engine
+from .loading import kept_mod_types
+from .motif_sites import open_run, table_text
 
 SETS_NAME = "motif-coverage.tsv"
 CONTIGS_NAME = "motif-coverage-contigs.tsv"
@@ -66,19 +66,6 @@ def build_sets(bins, mod_types, cands) -> list:
     return [CoverageSet(b, mt, by_key.get((b, mt), [])) for b in sorted(bins) for mt in mod_types]
 
 
-def mod_types_of_pileup(eng: ScanEngine) -> list:
-    """The mod types of which the ingest kept at least one pileup row on a resident contig, in slot order (``load_engine`` gives every
-    known mod code a slot; a slot no row went into is not a mod type of this pileup)."""
-    kept = np.zeros((max(len(eng.contig_names), 1), 8), dtype=np.uint32)
-    _lib.check(eng.lib.nm_ingest_results(eng.ctx, None, None, None, None, 0, kept.ctypes.data_as(C.POINTER(C.c_uint32))))
-    present = {mt for code, mt in enumerate(pileup_mod.MOD_TYPES) if kept[:, code].any()}
-    return [mt for mt in sorted(eng.slot_of_mod, key=eng.slot_of_mod.get) if mt in present]
-
-
-def _lines(header, rows) -> str:
-    return "\n".join(["\t".join(header)] + ["\t".join(str(x) for x in r) for r in rows]) + "\n"
-
-
 def format_sets(sets, tables) -> str:
     """motif-coverage.tsv: per set the ten columns of its int64[n_contigs, 10] table summed over contigs and strands."""
     rows = []
@@ -87,7 +74,7 @@ def format_sets(sets, tables) -> str:
         n_mod, n_exp = int(t[0] + t[5]), int(t[1] + t[6])
         fraction = "%.6f" % (n_exp / n_mod) if n_mod else "nan"
         rows.append([s.bin, s.mod_type, len(s.candidates), n_mod, n_exp, n_mod - n_exp, fraction, int(t[2] + t[7]), int(t[3] + t[8]), int(t[4] + t[9])])
-    return _lines(SETS_HEADER, rows)
+    return table_text(SETS_HEADER, rows)
 
 
 def format_contigs(sets, contig_names, tables) -> str:
@@ -97,7 +84,7 @@ def format_contigs(sets, contig_names, tables) -> str:
         t = np.asarray(t, dtype=np.int64).reshape(-1, 10)
         for name, row in zip(names, t):
             rows.append([s.bin, fasta.original_name(name), s.mod_type] + [int(x) for x in row])
-    return _lines(CONTIGS_HEADER, rows)
+    return table_text(CONTIGS_HEADER, rows)
 
 
 def format_motifs(sets, site_counts, exclusive) -> str:
@@ -111,7 +98,7 @@ def format_motifs(sets, site_counts, exclusive) -> str:
             four = np.asarray(four, dtype=np.int64).reshape(-1, 4).sum(axis=0)
             rows.append([c.bin, c.motif, c.mod_type, c.mod_position, int(six[0] + six[3]), int(six[1] + six[4]), int(four[0] + four[2]),
                          int(four[1] + four[3])])
-    return _lines(MOTIFS_HEADER, rows)
+    return table_text(MOTIFS_HEADER, rows)
 
 
 def format_unexplained(rec, sets, contig_names) -> str:
@@ -141,21 +128,11 @@ def coverage_tables(eng: ScanEngine, sets: list):
 
 def run(args) -> int:
     """The command.  Returns the process's exit status."""
-    TIMINGS.clear()
-    if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
-        log.error("motif_coverage runs on one GPU: start it without a multi-rank launcher (WORLD_SIZE is %s)", os.environ["WORLD_SIZE"])
-        return 2
-    cands = candidates_of_bin_motifs(args.bin_motifs)
-    log.info(f"{len(cands)} (bin, motif) candidates from {args.bin_motifs}")
-    device = args.device if args.device is not None else int(os.environ.get("LOCAL_RANK", "0") or 0)
-    t0 = time.perf_counter()
+    eng, cands, status = open_run("motif_coverage", args, TIMINGS)
+    if eng is None:
+        return status
     try:
-        eng = load_engine(args, device)
-    except _lib.NmScanError as e:
-        raise RuntimeError(f"nanomotif_amd needs an AMD GPU (MI355X); there is no CPU fallback ({e})") from e
-    TIMINGS["ingest_s"] = time.perf_counter() - t0
-    try:
-        mod_types = mod_types_of_pileup(eng)
+        mod_types = kept_mod_types(eng)
         for c in cands:
             if c.bin not in eng.bin_index:
                 log.warning(f"{c!r}: the bin has no contig in the assembly; skipped")

@@ -99,13 +99,13 @@ def files(tmp, total_bp):
 
 
 def load(tmp):
-    from nanomotif_amd import motif_compare as mc, motif_sites as ms
+    from nanomotif_amd import loading, motif_compare as mc, motif_sites as ms
     args = argparse.Namespace(assembly=os.path.join(tmp, "assembly.fasta"), pileup=None, contig_bin=os.path.join(tmp, "contig_bin.tsv"),
                               files=None, directory=None, extension=".fasta", threads=1, methylation_threshold_low=0.3, methylation_threshold_high=0.7)
     t0 = time.perf_counter()
-    eng = ms.load_engine(args, 0, pileups=[(os.path.join(tmp, "pileup.bed"), None), (os.path.join(tmp, "pileup_b.bed"), lambda mt: mt + mc.SAMPLE_B_SUFFIX)])
+    eng = loading.load_engine(args, 0, pileups=[(os.path.join(tmp, "pileup.bed"), None), (os.path.join(tmp, "pileup_b.bed"), lambda mt: mt + mc.SAMPLE_B_SUFFIX)])
     ingest_s = time.perf_counter() - t0
-    mod_types = mc.compared_mod_types(eng)
+    mod_types = loading.kept_mod_types(eng)
     cands = [c for c in ms.candidates_of_bin_motifs(os.path.join(tmp, "out", "bin-motifs.tsv")) if c.bin in eng.bin_index and c.mod_type in mod_types]
     return eng, cands, ingest_s
 

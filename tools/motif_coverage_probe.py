@@ -60,14 +60,14 @@ def files(tmp, total_bp):
 
 
 def load(tmp):
-    from nanomotif_amd import motif_coverage as mc, motif_sites as ms
+    from nanomotif_amd import loading, motif_coverage as mc, motif_sites as ms
     args = argparse.Namespace(assembly=os.path.join(tmp, "assembly.fasta"), pileup=os.path.join(tmp, "pileup.bed"), contig_bin=os.path.join(tmp, "contig_bin.tsv"),
                               files=None, directory=None, extension=".fasta", threads=1, methylation_threshold_low=0.3, methylation_threshold_high=0.7)
     t0 = time.perf_counter()
-    eng = ms.load_engine(args, 0)
+    eng = loading.load_engine(args, 0)
     ingest_s = time.perf_counter() - t0
     cands = ms.candidates_of_bin_motifs(os.path.join(tmp, "out", "bin-motifs.tsv"))
-    mod_types = mc.mod_types_of_pileup(eng)
+    mod_types = loading.kept_mod_types(eng)
     sets = mc.build_sets([b for b in eng.bin_index if eng.bin_contigs(b)], mod_types, cands)
     return eng, sets, ingest_s
 

@@ -57,11 +57,11 @@ def files(tmp, total_bp):
 
 
 def engine(tmp, with_loop):
-    from nanomotif_amd import motif_sites as ms
+    from nanomotif_amd import loading, motif_sites as ms
     args = argparse.Namespace(assembly=os.path.join(tmp, "assembly.fasta"), pileup=os.path.join(tmp, "pileup.bed"), contig_bin=os.path.join(tmp, "contig_bin.tsv"),
                               files=None, directory=None, extension=".fasta", threads=1, methylation_threshold_low=0.3, methylation_threshold_high=0.7)
     t0 = time.perf_counter()
-    eng = ms.load_engine(args, 0)
+    eng = loading.load_engine(args, 0)
     out = {"mode": "engine" if with_loop else "trace", "ingest_s": time.perf_counter() - t0}
     cands = [c for c in ms.candidates_of_bin_motifs(os.path.join(tmp, "out", "bin-motifs.tsv")) if c.bin in eng.bin_index and c.mod_type in eng.slot_of_mod]
     first_bins = list(dict.fromkeys(c.bin for c in cands))[:8]
