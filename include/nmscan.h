@@ -472,6 +472,55 @@ int nm_motif_compare_text(uint64_t n_records, const uint32_t *site_contig, const
                           uint32_t n_contigs, const char *contig_text, const uint64_t *contig_text_off, char *out,
                           uint64_t capacity, uint64_t *n_bytes);
 
+/* ---- BOTH STRANDS of a motif site: every occurrence of a batch of candidates classified by its own state and its partner's ------
+ * Reference: none; it pairs a motif with its complement by name only (join_motif_complements).  modkit has pileup-hemi for CpG.  Two
+ * nm_motif_sites_count tables (the motif, its reverse complement) are only the MARGINALS of the table below.
+ *
+ * A candidate is a candidate of nm_motif_sites plus a PARTNER OFFSET d = cand_partner_offset[k].  Let the motif (unstripped, L tokens)
+ * have its modified base at i and let the partner's modified base be at j, counted in the REVERSE COMPLEMENT of the motif:
+ * d = L - 1 - i - j.  Stripping leading or trailing '.' from both leaves d unchanged.  An occurrence of the motif on '+' with its
+ * modified base at p has its partner base on '-' at p + d; an occurrence on '-' (the reverse complement on '+') with its modified
+ * base at p has its partner on '+' at p - d.  An OCCURRENCE and the STATE of a (position, strand) are exactly those of nm_motif_sites:
+ * 0 methylated, 1 unmethylated (a position called both ways is methylated), 2 no call.  PAIR t = 3 * own + partner, 0..8; pair_set:
+ * bit t set = pair t is exported (NM_STRANDS_ALL = all nine, NM_STRANDS_HEMI = the two hemimethylated ones, mod-nomod and nomod-mod).
+ * The partner must lie inside the stripped motif (0 <= cand_modpos[k] + d < cand_len[k]): then it lies inside the occurrence's span,
+ * hence inside the contig and inside the reach class of the candidate.  d = 0 is the same position on the other strand.
+ *
+ * nm_motif_strands_count: contig_counts = int64[row_offset[n_cand]][18] in the row layout of nm_motif_compare_count: the nine pair
+ *   counts of the '+' occurrences (index t), then the nine of the '-' occurrences (9 + t); all eighteen whatever pair_set says.
+ *   Summing the '+' nine over the partner state gives the forward three columns of nm_motif_sites_count for the motif, summing them
+ *   over the own state the reverse three of nm_motif_sites_count for (reverse complement, j); mirrored for the '-' nine.  The '-' nine
+ *   of (M, i | j) is the transposed '+' nine of (reverse complement of M, j | i).  cand_total[k] = records of candidate k under pair_set.
+ * nm_motif_strands_sites: count + prefix + fill.  A record = (contig id, contig-local 0-based position of the OWN modified base,
+ *   code = (NM_STRANDS_MINUS on '-') | t).  ORDER, cand_offset, windows by first_record / capacity / *n_written exactly as in
+ *   nm_motif_compare_sites: candidate-major, contigs in nm_bin_contigs order, ascending position, '+' before '-'.
+ * Launches: at most 3 (count, one per reach width) + scan + gather + 3 (fill) whatever the batch holds.
+ * NM_ESTATE without an assembly or without a pileup in a candidate's slot, NM_EINVAL for NULLs / a bad bin / an empty pair_set / bits
+ * above 8 / a partner outside the stripped motif (the message names the candidate), NM_ERANGE for more than 2^32 work items or rows
+ * and for a candidate beyond the reach limit (as nm_motif_sites).  n_cand = 0 is NM_OK. */
+#define NM_STRANDS_MINUS 16u        /* strand bit of a record's code: code = strand bit | pair, pair 0..8 */
+#define NM_STRANDS_ALL 0x1FFu
+#define NM_STRANDS_HEMI ((1u << 1) | (1u << 3))         /* mod-nomod (t = 1), nomod-mod (t = 3) */
+int nm_motif_strands_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot,
+                           const int8_t *cand_partner_offset, const uint8_t *cand_len, const uint8_t *cand_modpos,
+                           const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t pair_set,
+                           const uint64_t *row_offset, uint64_t *cand_total, int64_t *contig_counts);
+int nm_motif_strands_sites(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot,
+                           const int8_t *cand_partner_offset, const uint8_t *cand_len, const uint8_t *cand_modpos,
+                           const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t pair_set,
+                           uint64_t first_record, uint64_t capacity, uint32_t *site_contig, uint32_t *site_pos, uint8_t *site_code,
+                           uint64_t *cand_offset, uint64_t *n_written);
+/* The records of a span as the lines of hemi-sites.bed (host code, no device needed):
+ *   contig \t start \t start + 1 \t name \t 0 \t strand \t own-partner \t bin \t partner position \n
+ * own, partner = mod / nomod / nocall; seg_partner_offset[s] = the partner offset d of run s: the ninth column is start + d on '+',
+ * start - d on '-'.  Runs, names, size query (out == NULL), NM_ERANGE on a short buffer, NM_POST_THREADS and thread-independent bytes
+ * exactly as nm_motif_sites_text; NM_EINVAL for a contig >= n_contigs, a code that is none of the eighteen or a partner position
+ * below 0. */
+int nm_motif_strands_text(uint64_t n_records, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code,
+                          uint32_t n_seg, const uint64_t *seg_begin, const char *seg_text, const uint64_t *seg_text_off,
+                          const int32_t *seg_partner_offset, uint32_t n_contigs, const char *contig_text,
+                          const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes);
+
 /* ---- per-contig READ methylation of motifs: the table binnary starts from -------------------------
  * Reference: nanomotif/main.py:142-193 — `contig_methylation = methylation_pattern(pileup, assembly, motifs,
  * min_valid_read_coverage, min_valid_cov_to_diff_fraction = 0.8, output_type = Median | WeightedMean)` from the

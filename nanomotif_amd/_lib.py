@@ -24,6 +24,7 @@ SYMBOLS = [
     "nm_motif_sites_count", "nm_motif_sites", "nm_motif_sites_text",
     "nm_motif_coverage_count", "nm_motif_coverage_sites",
     "nm_motif_compare_count", "nm_motif_compare_sites", "nm_motif_compare_text",
+    "nm_motif_strands_count", "nm_motif_strands_sites", "nm_motif_strands_text",
 ]
 
 class SearchParams(C.Structure):
@@ -148,6 +149,12 @@ def _load_locked():
     lib.nm_motif_compare_sites.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, u8p, u64p,
                                            u64p]
     lib.nm_motif_compare_text.argtypes = [C.c_uint64, u32p, u32p, u8p, C.c_uint32, u64p, C.c_char_p, u64p, C.c_uint32, C.c_char_p, u64p, p,
+                                          C.c_uint64, u64p]
+    i8p, i32p = C.POINTER(C.c_int8), C.POINTER(C.c_int32)
+    lib.nm_motif_strands_count.argtypes = [p, C.c_uint32, u32p, u8p, i8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, u64p, i64p]
+    lib.nm_motif_strands_sites.argtypes = [p, C.c_uint32, u32p, u8p, i8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, u8p, u64p,
+                                           u64p]
+    lib.nm_motif_strands_text.argtypes = [C.c_uint64, u32p, u32p, u8p, C.c_uint32, u64p, C.c_char_p, u64p, i32p, C.c_uint32, C.c_char_p, u64p, p,
                                           C.c_uint64, u64p]
     lib.nm_motif_sites_text.argtypes = [C.c_uint64, u32p, u32p, u8p, C.c_uint32, u64p, C.c_char_p, u64p, C.c_uint32, C.c_char_p, u64p, p,
                                         C.c_uint64, u64p]

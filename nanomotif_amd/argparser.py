@@ -1,6 +1,6 @@
 """Command line of the MI355X build: the ``motif_discovery`` sub-command with the reference's arguments
 (nanomotif/argparser.py:13-136), plus ``--device`` for the GPU to use, the project's own ``motif_sites`` / ``motif_coverage`` /
-``motif_compare`` on a finished ``bin-motifs.tsv``, and the binnary sub-commands ``detect_contamination`` and
+``motif_compare`` / ``motif_strands`` on a finished ``bin-motifs.tsv``, and the binnary sub-commands ``detect_contamination`` and
 ``include_contigs`` with the reference's flags (argparser.py:139-236).  MTase-linker is out of scope."""
 import argparse
 
@@ -13,7 +13,7 @@ def create_parser():
                                      formatter_class=formatter)
     parser.add_argument("--version", action="version", version="%(prog)s {}".format(__version__))
     sub = parser.add_subparsers(help="-- Command descriptions --", dest="command", title="commands",
-                                metavar="{motif_discovery, motif_sites, motif_coverage, motif_compare, detect_contamination, include_contigs, check_installation}")
+                                metavar="{motif_discovery, motif_sites, motif_coverage, motif_compare, motif_strands, detect_contamination, include_contigs, check_installation}")
     p = sub.add_parser("motif_discovery", help="Finds motifs directly on bin level in provided assembly", add_help=False)
     p.add_argument("assembly", type=str, help="path to the assembly file.")
     p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
@@ -53,6 +53,7 @@ def create_parser():
     add_motif_sites_parser(sub)
     add_motif_coverage_parser(sub)
     add_motif_compare_parser(sub)
+    add_motif_strands_parser(sub)
     add_binnary_parsers(sub)
     sub.add_parser("check_installation", help="Run motif_discovery on a small synthetic data set", add_help=True)
     return parser
@@ -213,3 +214,47 @@ def add_binnary_parsers(sub):
     group.add_argument("--contamination_file", type=str, help="Path to an existing contamination file to include in the analysis")
     group.add_argument("--run_detect_contamination", action="store_true",
                        help="Indicate that the detect_contamination workflow should be run first")
+
+
+def _pairs(text):
+    from .engine import PAIRS
+    asked = [t.strip() for t in text.split(",") if t.strip()]
+    if not asked or any(t not in PAIRS for t in asked):
+        raise argparse.ArgumentTypeError(f"a comma-separated selection of {', '.join(PAIRS)} is expected, got {text!r}")
+    return tuple(t for t in PAIRS if t in asked)
+
+
+def add_motif_strands_parser(sub):
+    """motif_strands: the state of both strands of every motif site — full, hemi, unmethylated (no counterpart on the reference's command
+    line, which pairs a motif with its complement by name only; modkit has pileup-hemi for CpG).  Arguments are those of motif_sites with
+    one or more bin-motifs.tsv: same ingest."""
+    p = sub.add_parser("motif_strands", help="Reports whether both strands of the motif sites of bin-motifs.tsv files are methylated", add_help=False)
+    p.add_argument("assembly", type=str, help="path to the assembly file.")
+    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
+    gm = p.add_argument_group("contig bin arguments, use one of:")
+    g = gm.add_mutually_exclusive_group(required=True)
+    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
+    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
+    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
+    gm.add_argument("--extension", type=str, default=".fasta",
+                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
+    o = p.add_argument_group("Options")
+    o.add_argument("--bin_motifs", type=str, nargs="+", required=True, help="Path(s) to the bin-motifs.tsv whose motif sites are assessed (motif_discovery's output)")
+    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
+    o.add_argument("--hemi_sites", action="store_true",
+                   help="Also write hemi-sites.bed: the occurrences whose own base and partner base differ in state (see --pairs)")
+    o.add_argument("--pairs", type=_pairs, default=("mod-nomod", "nomod-mod"),
+                   help="Comma-separated pairs own-partner written to hemi-sites.bed, each of mod, nomod, nocall on either side. "
+                        "Default: mod-nomod,nomod-mod")
+    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
+                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
+    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
+                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
+    o.add_argument("--threshold_valid_coverage", type=int, default=5,
+                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
+    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
+    gen = p.add_argument_group("general arguments")
+    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
+    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
+    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
+    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")

@@ -22,30 +22,6 @@ struct CompareArgs : ExportArgs {
     unsigned long long *table;           // count pass: [row][18], may be NULL
 };
 
-// the three disjoint states of one strand's word in one slot (a position called both ways is methylated)
-struct States {
-    uint32_t s[3];
-    __device__ __forceinline__ States(uint32_t m, uint32_t u) : s{m, u & ~m, ~(m | u)} {}
-};
-
-// the occurrences of `acc` whose transition is in `set`
-__device__ __forceinline__ uint32_t pick9(uint32_t set, uint32_t acc, const States &a, const States &b) {
-    uint32_t out = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        uint32_t bsel = 0;                                                // states of B selected together with state i of A
-#pragma unroll
-        for (int j = 0; j < 3; ++j) bsel |= (set >> (3 * i + j) & 1u) ? b.s[j] : 0u;
-        out |= a.s[i] & bsel;
-    }
-    return out & acc;
-}
-
-__device__ __forceinline__ uint32_t transition_of(uint32_t bit, const States &a, const States &b) {
-    const uint32_t sa = (a.s[0] & bit) ? 0u : (a.s[1] & bit) ? 1u : 2u, sb = (b.s[0] & bit) ? 0u : (b.s[1] & bit) ? 1u : 2u;
-    return 3u * sa + sb;
-}
-
 template <int G, bool FILL>
 __global__ __launch_bounds__(256) void compare_kernel(CompareArgs a) {
     using K = Variant<G, G, false, 2, false, false>;

@@ -1,4 +1,4 @@
-// The scaffold the three record exports share (nmsites.hip, nmcoverage.hip, nmcompare.hip; included by nothing else).  Each of them
+// The scaffold the four record exports share (nmsites.hip, nmcoverage.hip, nmcompare.hip, nmstrands.hip; included by nothing else).  Each of them
 // hands out one wave per work item = (owner, chunk of the owner's bin) — an owner is a candidate (sites, compare) or a set of
 // candidates (coverage) — and runs the same three steps:
 //   count  the unit's kernel writes the number of records of every work item into the item table (and its own count tables)
@@ -73,6 +73,30 @@ __device__ __forceinline__ StatePlanes slot_planes(const unsigned long long *pl)
     s.MM = reinterpret_cast<const uint32_t *>(pl[2]);
     s.UM = reinterpret_cast<const uint32_t *>(pl[3]);
     return s;
+}
+
+// the three disjoint states of one strand's word in one slot (a position called both ways is methylated)
+struct States {
+    uint32_t s[3];
+    __device__ __forceinline__ States(uint32_t m, uint32_t u) : s{m, u & ~m, ~(m | u)} {}
+};
+
+// the occurrences of `acc` whose transition is in `set`
+__device__ __forceinline__ uint32_t pick9(uint32_t set, uint32_t acc, const States &a, const States &b) {
+    uint32_t out = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        uint32_t bsel = 0;                                                // states of B selected together with state i of A
+#pragma unroll
+        for (int j = 0; j < 3; ++j) bsel |= (set >> (3 * i + j) & 1u) ? b.s[j] : 0u;
+        out |= a.s[i] & bsel;
+    }
+    return out & acc;
+}
+
+__device__ __forceinline__ uint32_t transition_of(uint32_t bit, const States &a, const States &b) {
+    const uint32_t sa = (a.s[0] & bit) ? 0u : (a.s[1] & bit) ? 1u : 2u, sb = (b.s[0] & bit) ? 0u : (b.s[1] & bit) ? 1u : 2u;
+    return 3u * sa + sb;
 }
 
 // The fill pass of a work item.  sel(t, f, r): the positions of the lane's word t that are records, forward and reverse strand;

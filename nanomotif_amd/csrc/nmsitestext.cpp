@@ -1,6 +1,7 @@
 // nm_motif_sites_text — the records of nm_motif_sites as the lines of motif-sites.bed, on a few host threads — and
 // nm_motif_compare_text, the records of nm_motif_compare_sites as the lines of switched-sites.bed: the same line with the
-// transition "a>b" in the state column.
+// transition "a>b" in the state column — and nm_motif_strands_text, the records of nm_motif_strands_sites as the lines of hemi-sites.bed:
+// the pair "own-partner" in the state column and the partner's position in a ninth.
 // The reference keeps the four position arrays of motif_model_contig(save_motif_positions=True) in memory
 // (find_motifs_bin.py:1322-1329) and writes no per-site file; the line format is this project's (README.md).
 // Two passes over the span: every thread sizes its share of the records exactly, the shares' offsets are a prefix sum, then every
@@ -44,6 +45,9 @@ const char *const TRANSITION_TEXT[9] = {"mod>mod", "mod>nomod", "mod>nocall", "n
                                         "nocall>nocall"};
 const unsigned TRANSITION_LEN[9] = {7, 9, 10, 9, 11, 12, 10, 12, 13};
 const Labels TRANSITION_LABELS{TRANSITION_TEXT, TRANSITION_LEN, 9, 15u, NM_COMPARE_MINUS};
+const char *const PAIR_TEXT[9] = {"mod-mod", "mod-nomod", "mod-nocall", "nomod-mod", "nomod-nomod", "nomod-nocall", "nocall-mod", "nocall-nomod",
+                                  "nocall-nocall"};
+const Labels PAIR_LABELS{PAIR_TEXT, TRANSITION_LEN, 9, 15u, NM_STRANDS_MINUS};
 
 struct Span {
     const uint32_t *contig, *pos;
@@ -52,6 +56,9 @@ struct Span {
     const uint64_t *seg_begin, *seg_text_off, *contig_text_off;
     const char *seg_text, *contig_text;
     Labels lab;
+    const int32_t *seg_partner;                                          // per run the partner offset d (a ninth column), or NULL
+    // position of the partner of record i of run seg: pos + d on '+', pos - d on '-'
+    int64_t partner(uint64_t i, uint32_t seg) const { return (int64_t)pos[i] + ((code[i] & lab.minus) ? -(int64_t)seg_partner[seg] : (int64_t)seg_partner[seg]); }
     // segment that holds record i (the last one whose begin is <= i; empty segments are passed over)
     uint32_t seg_of(uint64_t i) const { return (uint32_t)(std::upper_bound(seg_begin, seg_begin + n_seg + 1, i) - seg_begin) - 1; }
 };
@@ -66,6 +73,7 @@ uint64_t size_range(const Span &s, uint64_t lo, uint64_t hi) {
         const uint32_t c = s.contig[i];
         const uint64_t p = s.pos[i];
         bytes += (s.contig_text_off[c + 1] - s.contig_text_off[c]) + digits(p) + digits(p + 1) + 1 + s.lab.len[s.code[i] & s.lab.mask] + fixed;
+        if (s.seg_partner) bytes += 1 + digits((uint64_t)s.partner(i, seg));
     }
     return bytes;
 }
@@ -98,6 +106,10 @@ char *write_range(const Span &s, uint64_t lo, uint64_t hi, char *out) {
         const uint64_t bl = s.seg_text_off[2 * seg + 2] - s.seg_text_off[2 * seg + 1];
         memcpy(out, s.seg_text + s.seg_text_off[2 * seg + 1], bl);
         out += bl;
+        if (s.seg_partner) {
+            *out++ = '\t';
+            out = put_u64(out, (uint64_t)s.partner(i, seg));
+        }
         *out++ = '\n';
     }
     return out;
@@ -105,11 +117,12 @@ char *write_range(const Span &s, uint64_t lo, uint64_t hi, char *out) {
 
 int records_text(const Labels &lab, uint64_t n, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code, uint32_t n_seg,
                  const uint64_t *seg_begin, const char *seg_text, const uint64_t *seg_text_off, uint32_t n_contigs, const char *contig_text,
-                 const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes) {
+                 const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes, const int32_t *seg_partner = nullptr,
+                 bool with_partner = false) {
     if (!n_bytes) return nm_set_error(NM_EINVAL, "NULL argument");
     *n_bytes = 0;
     if (n == 0) return NM_OK;
-    if (!site_contig || !site_pos || !site_code || !seg_begin || !seg_text || !seg_text_off || !contig_text || !contig_text_off)
+    if (!site_contig || !site_pos || !site_code || !seg_begin || !seg_text || !seg_text_off || !contig_text || !contig_text_off || (with_partner && !seg_partner))
         return nm_set_error(NM_EINVAL, "NULL argument");
     if (n_seg == 0 || seg_begin[0] != 0 || seg_begin[n_seg] != n) return nm_set_error(NM_EINVAL, "the runs must cover the %llu records exactly", (unsigned long long)n);
     for (uint32_t s = 0; s < n_seg; ++s)
@@ -117,7 +130,7 @@ int records_text(const Labels &lab, uint64_t n, const uint32_t *site_contig, con
     unsigned n_thr = std::max(1u, std::min(16u, std::thread::hardware_concurrency() / 2));
     if (const char *e = getenv("NM_POST_THREADS")) n_thr = (unsigned)std::max(1, std::min(16, atoi(e)));
     n_thr = (unsigned)std::min<uint64_t>(n_thr, (n + 255) / 256);        // (a thread is not worth starting for less)
-    const Span sp{site_contig, site_pos, site_code, n_seg, seg_begin, seg_text_off, contig_text_off, seg_text, contig_text, lab};
+    const Span sp{site_contig, site_pos, site_code, n_seg, seg_begin, seg_text_off, contig_text_off, seg_text, contig_text, lab, seg_partner};
     auto lo_of = [&](unsigned t) { return n * t / n_thr; };
     std::vector<uint64_t> bytes(n_thr + 1, 0);
     std::vector<int> bad(n_thr, 0);
@@ -131,8 +144,17 @@ int records_text(const Labels &lab, uint64_t n, const uint32_t *site_contig, con
         const uint64_t lo = lo_of(t), hi = lo_of(t + 1);
         for (uint64_t i = lo; i < hi; ++i)
             if (site_contig[i] >= n_contigs || (site_code[i] & lab.mask) >= lab.n || (site_code[i] & ~(lab.mask | lab.minus))) { bad[t] = 1; return; }
+        if (seg_partner) {
+            uint32_t seg = lo < hi ? sp.seg_of(lo) : 0;
+            for (uint64_t i = lo; i < hi; ++i) {
+                while (i >= seg_begin[seg + 1]) ++seg;
+                if (sp.partner(i, seg) < 0) { bad[t] = 2; return; }
+            }
+        }
         bytes[t + 1] = size_range(sp, lo, hi);
     });
+    for (unsigned t = 0; t < n_thr; ++t)
+        if (bad[t] == 2) return nm_set_error(NM_EINVAL, "a record's partner lies before the start of its contig");
     for (unsigned t = 0; t < n_thr; ++t)
         if (bad[t]) return nm_set_error(NM_EINVAL, "a record names a contig >= %u or carries a code that is none of the %u", n_contigs, 2 * lab.n);
     for (unsigned t = 0; t < n_thr; ++t) bytes[t + 1] += bytes[t];
@@ -157,4 +179,12 @@ extern "C" int nm_motif_compare_text(uint64_t n, const uint32_t *site_contig, co
                                      const char *contig_text, const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes) {
     return records_text(TRANSITION_LABELS, n, site_contig, site_pos, site_code, n_seg, seg_begin, seg_text, seg_text_off, n_contigs, contig_text,
                         contig_text_off, out, capacity, n_bytes);
+}
+
+extern "C" int nm_motif_strands_text(uint64_t n, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code, uint32_t n_seg,
+                                     const uint64_t *seg_begin, const char *seg_text, const uint64_t *seg_text_off, const int32_t *seg_partner_offset,
+                                     uint32_t n_contigs, const char *contig_text, const uint64_t *contig_text_off, char *out, uint64_t capacity,
+                                     uint64_t *n_bytes) {
+    return records_text(PAIR_LABELS, n, site_contig, site_pos, site_code, n_seg, seg_begin, seg_text, seg_text_off, n_contigs, contig_text,
+                        contig_text_off, out, capacity, n_bytes, seg_partner_offset, true);
 }

@@ -29,6 +29,9 @@ SITE_DTYPE = np.dtype([("candidate", np.uint32), ("contig", np.uint32), ("pos", 
 COMPARE_MINUS = 16                             # NM_COMPARE_MINUS: the strand bit of a record of nm_motif_compare_sites; the rest is the transition
 TRANSITIONS = tuple(f"{a}>{b}" for a in SITE_STATES for b in SITE_STATES)      # transition t = 3 * state in sample A + state in sample B
 SWITCHED = ("mod>nomod", "nomod>mod")          # NM_COMPARE_SWITCHED: the two discordant called transitions
+STRANDS_MINUS = 16                             # NM_STRANDS_MINUS: the strand bit of a record of nm_motif_strands_sites; the rest is the pair
+PAIRS = tuple(f"{a}-{b}" for a in SITE_STATES for b in SITE_STATES)            # pair t = 3 * state of the own base + state of the partner's
+HEMI = ("mod-nomod", "nomod-mod")              # NM_STRANDS_HEMI: the two hemimethylated pairs
 UNEXPLAINED_DTYPE = np.dtype([("set", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])   # ScanEngine.unexplained_sites
 
 
@@ -48,6 +51,21 @@ def transition_set(transitions) -> int:
     if bad or not transitions:
         raise ValueError(f"transitions must be a non-empty selection of {TRANSITIONS}, got {transitions!r}")
     return sum(1 << TRANSITIONS.index(t) for t in set(transitions))
+
+
+def pair_set(pairs) -> int:
+    """("mod-nomod", "nomod-mod") -> the pair_set bits of nm_motif_strands_*."""
+    pairs = tuple(pairs)
+    bad = [t for t in pairs if t not in PAIRS]
+    if bad or not pairs:
+        raise ValueError(f"pairs must be a non-empty selection of {PAIRS}, got {pairs!r}")
+    return sum(1 << PAIRS.index(t) for t in set(pairs))
+
+
+def partner_offset(motif: Motif, partner_position: int) -> int:
+    """d = L - 1 - i - j of include/nmscan.h: ``motif`` (L tokens, unstripped) has its modified base at i, its partner's modified base
+    is at ``partner_position`` = j of the motif's reverse complement.  Stripping dots from both ends of both leaves d unchanged."""
+    return len(motif.tokens) - 1 - int(motif.mod_position) - int(partner_position)
 
 
 class SiteBatch:
@@ -839,7 +857,7 @@ class ScanEngine:
 
     def _count_table(self, call, args, b: CandidateBatch, selection: int, width: int):
         """(contig names per bin, row prefix, totals under ``selection``, int64[rows, width]) of one count call of the per-candidate
-        exports (nm_motif_sites_count, nm_motif_compare_count); ``args``: the call's candidate arguments."""
+        exports (nm_motif_sites_count, nm_motif_compare_count, nm_motif_strands_count); ``args``: the call's candidate arguments."""
         names, rows = self._site_rows(b)
         table = np.zeros((max(int(rows[-1]), 1), width), dtype=np.int64)
         totals = np.zeros(max(len(b), 1), dtype=np.uint64)
@@ -855,7 +873,7 @@ class ScanEngine:
         return limit
 
     def _record_windows(self, call, group_args, totals, limit: int, dtype, owner: str, unit: str):
-        """The window loop of the three record exports: consecutive owners (candidates, sets) are grouped while their ``totals`` fit
+        """The window loop of the four record exports: consecutive owners (candidates, sets) are grouped while their ``totals`` fit
         ``limit``, and every group is fetched in windows of at most ``limit`` records — one, unless a single owner exceeds the limit.
         ``call``: the library's *_sites function; ``group_args(k, e)``: its arguments before first_record for the owners [k, e);
         ``dtype``: the records' type, whose ``owner`` field is filled in here; ``unit``: what the library's message calls a group.
@@ -975,6 +993,50 @@ class ScanEngine:
             sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
             return (self.ctx, *self._compare_args(sub, np.ascontiguousarray(slots_b[k:e])), tset)
         windows = self._record_windows(self.lib.nm_motif_compare_sites, group_args, totals, limit, SITE_DTYPE, "candidate", "batch")
+        yield from self._site_batches(windows, b, names, rows, table)
+
+    # ------------------------------------------------------------------ both strands of a site (nm_motif_strands_*)
+    def _strands_batch(self, candidates):
+        """(CandidateBatch, int8 partner offsets) of ``candidates`` = sequence of (Motif, mod_type, bin, partner_position).  An offset
+        beyond int8 is clipped: it lies outside every motif within the reach limit, and the library refuses it by name."""
+        candidates = list(candidates)
+        b = self.make_batch([c[:3] for c in candidates])
+        d = np.fromiter((max(-128, min(127, partner_offset(c[0], c[3]))) for c in candidates), dtype=np.int8, count=len(candidates))
+        return b, d
+
+    @staticmethod
+    def _strands_args(b: CandidateBatch, d):
+        return (len(b), _ptr(b.bins, C.c_uint32), _ptr(b.slots, C.c_uint8), _ptr(d, C.c_int8), _ptr(b.lens, C.c_uint8), _ptr(b.modpos, C.c_uint8),
+                _ptr(b.offsets, C.c_uint32), _ptr(b.masks, C.c_uint8))
+
+    def _strands_counts(self, b: CandidateBatch, d, pset: int):
+        return self._count_table(self.lib.nm_motif_strands_count, self._strands_args(b, d), b, pset, 18)
+
+    def motif_strand_counts(self, candidates):
+        """Per (candidate, contig) the eighteen pair counts of every resident contig of the candidate's bin (nm_motif_strands_count):
+        column 3 * own state + partner state of the occurrences on '+', then 9 + that of the occurrences on '-'; states 0 mod, 1 nomod,
+        2 nocall.  ``candidates``: sequence of (Motif, mod_type, bin, partner_position) — the partner's modified base is at
+        ``partner_position`` of the motif's reverse complement, on the opposite strand (``partner_offset``).  Returns a list, per
+        candidate, of (contig names, int64[n_contigs, 18])."""
+        b, d = self._strands_batch(candidates)
+        names, rows, _, table = self._strands_counts(b, d, 0x1FF)
+        return [(names[int(b.bins[k])], table[int(rows[k]):int(rows[k + 1])]) for k in range(len(b))]
+
+    def motif_strand_sites(self, candidates, pairs=HEMI, max_records=None):
+        """Generator over the occurrences of ``candidates`` whose (own, partner) pair is one of ``pairs`` (``PAIRS`` spellings; default
+        the two hemimethylated ones).  Yields ``SiteBatch`` objects as ``motif_sites`` does (``counts``: the int64[n_contigs, 18]
+        tables); a record's position is that of the OWN base, its code = 16 for an occurrence on '-' | pair 0..8.  Order: candidate,
+        contig (``bin_contigs`` order), position, '+' before '-'.  No batch holds more than ``max_records`` records; the concatenation
+        does not depend on ``max_records``."""
+        b, d = self._strands_batch(candidates)
+        pset = pair_set(pairs)
+        limit = self._record_limit(max_records)
+        names, rows, totals, table = self._strands_counts(b, d, pset)
+
+        def group_args(k, e):
+            sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
+            return (self.ctx, *self._strands_args(sub, np.ascontiguousarray(d[k:e])), pset)
+        windows = self._record_windows(self.lib.nm_motif_strands_sites, group_args, totals, limit, SITE_DTYPE, "candidate", "batch")
         yield from self._site_batches(windows, b, names, rows, table)
 
     # ------------------------------------------------------------------ coverage of a set of motifs (nm_motif_coverage_*)

@@ -90,10 +90,11 @@ def candidates_of_bin_motifs(path) -> list:
     return out
 
 
-def format_sites(contig, pos, code, seg_begin, seg_names, seg_bins, contig_names, symbol="nm_motif_sites_text") -> bytes:
+def format_sites(contig, pos, code, seg_begin, seg_names, seg_bins, contig_names, symbol="nm_motif_sites_text", seg_partner_offsets=None) -> bytes:
     """The lines of motif-sites.bed for records (contig, pos, code) cut into runs [seg_begin[s], seg_begin[s + 1]) that share a name
     and a bin (nm_motif_sites_text: native, on up to NM_POST_THREADS threads).  ``symbol``: the writer, nm_motif_compare_text for the
-    records of ``ScanEngine.motif_compare_sites`` (switched-sites.bed)."""
+    records of ``ScanEngine.motif_compare_sites`` (switched-sites.bed), nm_motif_strands_text with the runs' ``seg_partner_offsets`` for
+    those of ``ScanEngine.motif_strand_sites`` (hemi-sites.bed)."""
     lib = _lib.load()
     text = getattr(lib, symbol)
     n = len(contig)
@@ -110,8 +111,12 @@ def format_sites(contig, pos, code, seg_begin, seg_names, seg_bins, contig_names
     c_off = np.zeros(len(cparts) + 1, dtype=np.uint64)
     np.cumsum([len(x) for x in cparts], out=c_off[1:])
     p = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+    extra = ()
+    if seg_partner_offsets is not None:
+        seg_partner_offsets = np.ascontiguousarray(seg_partner_offsets, dtype=np.int32)
+        extra = (p(seg_partner_offsets, C.c_int32),)
     args = (n, p(contig, C.c_uint32), p(pos, C.c_uint32), p(code, C.c_uint8), len(seg_names), p(seg_begin, C.c_uint64), b"".join(parts),
-            p(seg_off, C.c_uint64), len(cparts), b"".join(cparts), p(c_off, C.c_uint64))
+            p(seg_off, C.c_uint64), *extra, len(cparts), b"".join(cparts), p(c_off, C.c_uint64))
     size = C.c_uint64(0)
     _lib.check(text(*args, None, 0, C.byref(size)))
     buf = np.empty(size.value, dtype=np.uint8)
@@ -119,9 +124,10 @@ def format_sites(contig, pos, code, seg_begin, seg_names, seg_bins, contig_names
     return buf.tobytes()
 
 
-def write_site_batches(eng: ScanEngine, batches, cands: list, bed_file, symbol="nm_motif_sites_text", summary=None):
+def write_site_batches(eng: ScanEngine, batches, cands: list, bed_file, symbol="nm_motif_sites_text", summary=None, partner_offsets=None):
     """The batch-to-BED loop of the per-site exports: ``batches`` (a generator of the engine over ``cands``: ``motif_sites``,
-    ``motif_compare_sites``) are written to the open binary file ``bed_file`` by the native writer ``symbol`` as they arrive.
+    ``motif_compare_sites``, ``motif_strand_sites``) are written to the open binary file ``bed_file`` by the native writer ``symbol`` as
+    they arrive.  ``partner_offsets``: per candidate the partner offset nm_motif_strands_text takes.
     ``summary``: a list that takes the rows (candidate, contig name, its row of the table) of the batches' ``counts`` in candidate,
     contig order.  Returns (records written, seconds spent in the engine, seconds spent on text)."""
     t_eng = t_text = 0.0
@@ -139,7 +145,8 @@ def write_site_batches(eng: ScanEngine, batches, cands: list, bed_file, symbol="
         if len(rec):
             seg_begin = np.searchsorted(rec["candidate"], np.arange(sb.first_candidate, sb.first_candidate + sb.n_candidates + 1))
             bed_file.write(format_sites(rec["contig"], rec["pos"], rec["code"], seg_begin, [c.name for c in group], [c.bin for c in group],
-                                        contig_names, symbol=symbol))
+                                        contig_names, symbol=symbol,
+                                        seg_partner_offsets=None if partner_offsets is None else partner_offsets[sb.first_candidate:sb.first_candidate + sb.n_candidates]))
             n_records += len(rec)
         t0 = time.perf_counter()
         t_text += t0 - t1
@@ -180,7 +187,7 @@ def candidates_of_files(paths) -> list:
 
 
 def open_run(command: str, args, timings: dict, pileups=None):
-    """How the three export commands open: the refusal of a multi-rank launch, the candidates of ``--bin_motifs`` (one file or
+    """How the four export commands open: the refusal of a multi-rank launch, the candidates of ``--bin_motifs`` (one file or
     several), the loaded engine (``loading.load_engine`` with ``pileups``) and ``timings["ingest_s"]``.  Returns (engine, candidates,
     0), or (None, None, the exit status) when the command does not run."""
     timings.clear()
