@@ -521,6 +521,34 @@ int nm_motif_strands_text(uint64_t n_records, const uint32_t *site_contig, const
                           const int32_t *seg_partner_offset, uint32_t n_contigs, const char *contig_text,
                           const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes);
 
+/* ---- METHYLATION PROFILE around a motif's sites: every position within `radius` of the modified base, both strands, every target ----
+ * Reference: none.  The four exports above read the modified base only; this call reads its neighbours, under any resident
+ * classification: is mod_position the right one, is the call bleed from the next base, is the site another mod type's.
+ *
+ * A candidate is (bin, stripped motif, mod_position) as for nm_motif_sites; its own mod slot is NOT an argument (occurrences depend on
+ * the sequence only).  An occurrence has its modified base at '+' coordinate p on occurrence strand s (0 '+', 1 '-').  For an offset o
+ * in the motif's reading direction, -radius <= o <= radius, and a relative strand r (0 the occurrence's strand, 1 the opposite one) the
+ * probe is the position q = p + o (s = 0) or p - o (s = 1) on strand s ^ r.  Under target t = mod slot target_slot[t] with canonical
+ * base B, a probe is
+ *   0 mod     (q, strand) is in the slot's methylated plane (a position called both ways is methylated),
+ *   1 nomod   in the unmethylated plane and not the methylated one,
+ *   2 nocall  neither, q inside the contig and the contig's letter at q read on that strand (complemented on '-') is B,
+ *   other     everything else (another letter, N, outside the contig): not counted here, = occurrences - the three above.
+ * cand_sites[2k + s] = occurrences of candidate k on strand s, summed over the contigs of its bin;
+ * counts = int64[n_cand][n_targets][2 radius + 1][2 (s)][2 (r)][3 (class)], offset o at index o + radius.
+ * With a candidate's own slot as target, (o = 0, r = 0) is its row of nm_motif_sites_count summed over contigs, and (o = d, r = 1) gives
+ * the partner marginals of nm_motif_strands_count for the partner offset d (those two have one no-call state: it is nocall + other here,
+ * and other is empty wherever the motif fixes the probed letter to the canonical base).  A slot may be named more than once.
+ * Launches: at most 3 (one per reach width) whatever the batch, the targets and the radius.
+ * NM_EINVAL for NULLs, radius > NM_PROFILE_MAX_RADIUS, n_targets 0 or above NM_MAX_MOD_SLOTS and a bad bin — each checked before any
+ * device is touched, in that order, the message names the argument; NM_ESTATE without an assembly or for a target slot without an
+ * uploaded pileup (per-strand planes); NM_ERANGE for a motif beyond NM_MAX_MOTIF_LEN / the reach limit and for more than 2^32 work
+ * items.  n_cand = 0 is NM_OK. */
+#define NM_PROFILE_MAX_RADIUS 31
+int nm_motif_profile_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_len, const uint8_t *cand_modpos,
+                           const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t n_targets, const uint8_t *target_slot,
+                           uint32_t radius, uint64_t *cand_sites, int64_t *counts);
+
 /* ---- per-contig READ methylation of motifs: the table binnary starts from -------------------------
  * Reference: nanomotif/main.py:142-193 — `contig_methylation = methylation_pattern(pileup, assembly, motifs,
  * min_valid_read_coverage, min_valid_cov_to_diff_fraction = 0.8, output_type = Median | WeightedMean)` from the

@@ -32,6 +32,8 @@ SWITCHED = ("mod>nomod", "nomod>mod")          # NM_COMPARE_SWITCHED: the two di
 STRANDS_MINUS = 16                             # NM_STRANDS_MINUS: the strand bit of a record of nm_motif_strands_sites; the rest is the pair
 PAIRS = tuple(f"{a}-{b}" for a in SITE_STATES for b in SITE_STATES)            # pair t = 3 * state of the own base + state of the partner's
 HEMI = ("mod-nomod", "nomod-mod")              # NM_STRANDS_HEMI: the two hemimethylated pairs
+PROFILE_MAX_RADIUS = 31                        # NM_PROFILE_MAX_RADIUS: offsets a profile reaches either side of the modified base
+PROFILE_CLASSES = ("mod", "nomod", "nocall", "other")                           # the last axis of ScanEngine.motif_profile's table
 UNEXPLAINED_DTYPE = np.dtype([("set", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])   # ScanEngine.unexplained_sites
 
 
@@ -1038,6 +1040,62 @@ class ScanEngine:
             return (self.ctx, *self._strands_args(sub, np.ascontiguousarray(d[k:e])), pset)
         windows = self._record_windows(self.lib.nm_motif_strands_sites, group_args, totals, limit, SITE_DTYPE, "candidate", "batch")
         yield from self._site_batches(windows, b, names, rows, table)
+
+    # ------------------------------------------------------------------ profile around a motif's sites (nm_motif_profile_count)
+    def _profile_targets(self, targets):
+        """(labels, uint8 slots) of ``targets`` = labels or slot numbers; None: every resident classification in slot order (a slot that
+        several labels name appears once, under the label that came first)."""
+        so = self.slot_of_mod
+        if targets is None:
+            first = {}
+            for label, slot in so.items():
+                first.setdefault(int(slot), label)
+            targets = [first[s] for s in sorted(first)]
+        targets = list(targets)
+        if not targets:
+            raise ValueError("motif_profile needs at least one target classification")
+        label_of_slot = {}
+        for label, slot in so.items():
+            label_of_slot.setdefault(int(slot), label)
+        labels, slots = [], []
+        for t in targets:
+            if isinstance(t, str):
+                if t not in so:
+                    raise ValueError(f"target {t!r} is not a resident classification ({', '.join(map(str, so)) or 'none'})")
+                labels.append(t)
+                slots.append(int(so[t]))
+            else:
+                labels.append(label_of_slot.get(int(t), str(int(t))))
+                slots.append(int(t))
+        return labels, np.asarray(slots, dtype=np.uint8)
+
+    def motif_profile(self, candidates, targets=None, radius=10):
+        """The methylation of every position around the sites of ``candidates`` (sequence of (Motif, mod_type, bin), or a
+        CandidateBatch; a candidate's mod type plays no part: occurrences depend on the sequence only) under the classifications
+        ``targets`` (labels or slot numbers; default every resident one in slot order), nm_motif_profile_count.  An occurrence has its
+        modified base at p on occurrence strand s (0 '+', 1 '-'); offset o counts in the motif's reading direction, relative strand r is
+        0 for the occurrence's strand and 1 for the opposite one; the probe is (p + o, s ^ r) for s = 0 and (p - o, s ^ r) for s = 1.
+        Returns (target labels, sites int64[n, 2] = occurrences per occurrence strand, table int64[n, n_targets, 2 radius + 1, 2 (s),
+        2 (r), 4]) with the classes mod, nomod, nocall (no call, and the letter read on the probed strand is the target's canonical
+        base) and other (the rest); offset o is at index o + radius; the four classes sum to ``sites[:, s]``.  Counts are summed over
+        the contigs of the candidate's bin."""
+        radius = int(radius)
+        if not 0 <= radius <= PROFILE_MAX_RADIUS:
+            raise ValueError(f"radius {radius} outside 0..{PROFILE_MAX_RADIUS}")
+        labels, slots = self._profile_targets(targets)
+        b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(list(candidates), slot_of=lambda mt: 0)
+        n, nt, width = len(b), len(slots), 2 * radius + 1
+        sites = np.zeros((n, 2), dtype=np.uint64)
+        three = np.zeros((n, nt, width, 2, 2, 3), dtype=np.int64)
+        if n:
+            _lib.check(self.lib.nm_motif_profile_count(self.ctx, n, _ptr(b.bins, C.c_uint32), _ptr(b.lens, C.c_uint8), _ptr(b.modpos, C.c_uint8),
+                                                       _ptr(b.offsets, C.c_uint32), _ptr(b.masks, C.c_uint8), nt, _ptr(slots, C.c_uint8), radius,
+                                                       _ptr(sites, C.c_uint64), _ptr(three, C.c_int64)))
+        sites = sites.astype(np.int64)
+        table = np.empty((n, nt, width, 2, 2, 4), dtype=np.int64)
+        table[..., :3] = three
+        table[..., 3] = sites[:, None, None, :, None] - three.sum(axis=-1)
+        return labels, sites, table
 
     # ------------------------------------------------------------------ coverage of a set of motifs (nm_motif_coverage_*)
     def _coverage_args(self, sets):
