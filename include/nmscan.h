@@ -549,6 +549,38 @@ int nm_motif_profile_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bi
                            const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t n_targets, const uint8_t *target_slot,
                            uint32_t radius, uint64_t *cand_sites, int64_t *counts);
 
+/* ---- METHYLATION TRACKS: a motif's site counts per WINDOW along the contigs of its bin ------------------------------------------------
+ * Reference: none (motif_model_contig, find_motifs_bin.py:1285-1331, sums over the contig).  The exports above give one row per contig
+ * or per bin; this call keeps the counts apart by position: a chimeric contig is a step function, an island an unmethylated stretch,
+ * a coverage dropout a stretch of nocall.
+ *
+ * WINDOW.  window_bp = W is a multiple of NM_TRACKS_MIN_WINDOW (128 = one lane's span of a wave-chunk, so every lane belongs to
+ *   exactly one window) in [128, NM_TRACKS_MAX_WINDOW = 2^30].  A contig of length L has n_windows = max(1, ceil(L / W)); window i
+ *   covers [i W, min((i + 1) W, L)).
+ * OCCURRENCES and STATES are nm_motif_sites': the stripped motif on '+', its reverse complement on '-'; 0 mod, 1 nomod, 2 nocall; a
+ *   position called both ways is mod.  An occurrence belongs to the window that holds its MODIFIED base (contig-local '+' coordinate
+ *   p, window p / W), on either strand.
+ * ROW = (fwd mod, fwd nomod, fwd nocall, rev mod, rev nomod, rev nocall) as uint32 (a window holds at most W positions per strand).
+ * ROW LAYOUT (part of the contract): candidate-major; within a candidate the contigs in nm_bin_contigs order; within a contig the
+ *   windows ascending.  Summing a contig's rows gives its row of nm_motif_sites_count.
+ *
+ * nm_tracks_windows: THE definition of the layout — contig_win_offset[n + 1] = prefix of the window counts over the n resident
+ *   contigs of `bin` in nm_bin_contigs order (contig_win_offset[n] = windows of the bin).  Host code.  contig_win_offset == NULL: only
+ *   *n_contigs; else `capacity` says how many contigs the array holds (+ 1 entries), NM_ERANGE when that is fewer than n.
+ * nm_motif_tracks_count: candidates as for nm_motif_sites_count.  row_offset[n_cand + 1], row_offset[0] == 0; every candidate gets at
+ *   least as many rows as its bin has windows, the rows it has beyond that stay zero.  window_counts = uint32[row_offset[n_cand]][6].
+ * Launches: at most 3 (one per reach width) whatever the batch holds and whatever W is.
+ * NM_EINVAL for NULLs, a window_bp that is no multiple of 128 or out of range (both checked before any device is touched, the
+ * message names the argument), a bad bin and too few rows; NM_ESTATE without an assembly or without a pileup in a candidate's slot;
+ * NM_ERANGE for 2^32 rows or work items and for a motif beyond NM_MAX_MOTIF_LEN / the reach limit as in nm_motif_sites.  n_cand = 0
+ * is NM_OK. */
+#define NM_TRACKS_MIN_WINDOW 128
+#define NM_TRACKS_MAX_WINDOW (1 << 30)
+int nm_tracks_windows(nm_ctx *ctx, uint32_t bin, uint32_t window_bp, uint64_t *contig_win_offset, uint32_t capacity, uint32_t *n_contigs);
+int nm_motif_tracks_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot, const uint8_t *cand_len,
+                          const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t window_bp,
+                          const uint64_t *row_offset, uint32_t *window_counts);
+
 /* ---- per-contig READ methylation of motifs: the table binnary starts from -------------------------
  * Reference: nanomotif/main.py:142-193 — `contig_methylation = methylation_pattern(pileup, assembly, motifs,
  * min_valid_read_coverage, min_valid_cov_to_diff_fraction = 0.8, output_type = Median | WeightedMean)` from the

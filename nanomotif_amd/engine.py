@@ -34,7 +34,11 @@ PAIRS = tuple(f"{a}-{b}" for a in SITE_STATES for b in SITE_STATES)            #
 HEMI = ("mod-nomod", "nomod-mod")              # NM_STRANDS_HEMI: the two hemimethylated pairs
 PROFILE_MAX_RADIUS = 31                        # NM_PROFILE_MAX_RADIUS: offsets a profile reaches either side of the modified base
 PROFILE_CLASSES = ("mod", "nomod", "nocall", "other")                           # the last axis of ScanEngine.motif_profile's table
-UNEXPLAINED_DTYPE = np.dtype([("set", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])   # ScanEngine.unexplained_sites
+TRACKS_MIN_WINDOW = 128                        # NM_TRACKS_MIN_WINDOW: one lane's span of a wave-chunk; a window is a multiple of it ...
+TRACKS_MAX_WINDOW = 1 << 30                    # ... up to NM_TRACKS_MAX_WINDOW
+TRACK_ROW_BYTES = 24                           # a row of ScanEngine.motif_tracks on the device: six uint32
+TRACK_BUDGET_BYTES = 256 << 20                 # default size of the tables of one library call of ScanEngine.motif_tracks
+UNEXPLAINED_DTYPE =np.dtype([("set", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])   # ScanEngine.unexplained_sites
 
 
 def site_state_set(states) -> int:
@@ -62,6 +66,23 @@ def pair_set(pairs) -> int:
     if bad or not pairs:
         raise ValueError(f"pairs must be a non-empty selection of {PAIRS}, got {pairs!r}")
     return sum(1 << PAIRS.index(t) for t in set(pairs))
+
+
+def track_window(window) -> int:
+    """A window size of ``ScanEngine.motif_tracks``: a multiple of 128 in [128, 2^30]; ValueError otherwise."""
+    w = int(window)
+    if not TRACKS_MIN_WINDOW <= w <= TRACKS_MAX_WINDOW or w % TRACKS_MIN_WINDOW:
+        raise ValueError(f"window {window!r}: a multiple of {TRACKS_MIN_WINDOW} in [{TRACKS_MIN_WINDOW}, 2^30]")
+    return w
+
+
+def window_prefix(lengths, window) -> np.ndarray:
+    """int64[n + 1]: the prefix of the window counts max(1, ceil(L / window)) of contigs of the given lengths — the layout of
+    nm_tracks_windows restated on the host (``ScanEngine.track_windows`` asks the library)."""
+    w = track_window(window)
+    out = np.zeros(len(lengths) + 1, dtype=np.int64)
+    np.cumsum([max(1, -(-int(n) // w)) for n in lengths], out=out[1:])
+    return out
 
 
 def partner_offset(motif: Motif, partner_position: int) -> int:
@@ -1096,6 +1117,53 @@ class ScanEngine:
         table[..., :3] = three
         table[..., 3] = sites[:, None, None, :, None] - three.sum(axis=-1)
         return labels, sites, table
+
+    # ------------------------------------------------------------------ methylation along contigs (nm_tracks_windows, nm_motif_tracks_count)
+    def track_windows(self, bin, window) -> np.ndarray:
+        """int64[n_contigs + 1]: the prefix of the window counts over the resident contigs of ``bin`` in ``bin_contigs`` order at window
+        size ``window`` (nm_tracks_windows, the one definition of the row layout of ``motif_tracks``): a contig of length L has
+        max(1, ceil(L / window)) windows, window i covers [i window, min((i + 1) window, L))."""
+        w = track_window(window)
+        b = self.bin_index[bin] if isinstance(bin, str) else int(bin)
+        n = C.c_uint32(0)
+        _lib.check(self.lib.nm_tracks_windows(self.ctx, b, w, None, 0, C.byref(n)))
+        off = np.zeros(n.value + 1, dtype=np.uint64)
+        _lib.check(self.lib.nm_tracks_windows(self.ctx, b, w, _ptr(off, C.c_uint64), n.value, C.byref(n)))
+        return off.astype(np.int64)
+
+    def motif_tracks(self, candidates, window=4096, max_bytes=None):
+        """Generator over the methylation of ``candidates`` (sequence of (Motif, mod_type, bin), or a CandidateBatch) ALONG the contigs of
+        their bins (nm_motif_tracks_count).  Yields one item per candidate, in candidate order: (contig names in ``bin_contigs`` order,
+        the window prefix int64[n_contigs + 1] of ``track_windows``, uint32[n_windows, 6]) — per window the six counts of
+        ``motif_site_counts`` (fwd mod, fwd nomod, fwd nocall, rev mod, rev nomod, rev nocall) of the occurrences whose modified base
+        lies in it, contigs in order, windows ascending.  ``window``: a multiple of 128 in [128, 2^30].  Consecutive candidates share
+        one library call while their tables fit ``max_bytes`` (default ``TRACK_BUDGET_BYTES`` = 256 MiB at 24 bytes a row); a group
+        always holds at least one candidate.  What is yielded does not depend on ``max_bytes``."""
+        w = track_window(window)
+        limit = TRACK_BUDGET_BYTES if max_bytes is None else int(max_bytes)
+        if limit < 1:
+            raise ValueError("max_bytes must be at least 1")
+        b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(list(candidates))
+        return self._track_groups(b, w, limit)
+
+    def _track_groups(self, b: CandidateBatch, w: int, limit: int):
+        bins = [int(x) for x in b.bins]
+        names = {bid: self.bin_contigs(bid) for bid in sorted(set(bins))}
+        prefix = {bid: self.track_windows(bid, w) for bid in names}
+        n, k = len(b), 0
+        while k < n:
+            e, held = k + 1, int(prefix[bins[k]][-1]) * TRACK_ROW_BYTES
+            while e < n and held + int(prefix[bins[e]][-1]) * TRACK_ROW_BYTES <= limit:
+                held += int(prefix[bins[e]][-1]) * TRACK_ROW_BYTES
+                e += 1
+            rows = np.zeros(e - k + 1, dtype=np.uint64)
+            np.cumsum([int(prefix[bins[j]][-1]) for j in range(k, e)], out=rows[1:])
+            table = np.zeros((max(int(rows[-1]), 1), 6), dtype=np.uint32)
+            sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
+            _lib.check(self.lib.nm_motif_tracks_count(self.ctx, *self._batch_args(sub), w, _ptr(rows, C.c_uint64), _ptr(table, C.c_uint32)))
+            for j in range(k, e):
+                yield names[bins[j]], prefix[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
+            k = e
 
     # ------------------------------------------------------------------ coverage of a set of motifs (nm_motif_coverage_*)
     def _coverage_args(self, sets):
