@@ -601,7 +601,9 @@ int nm_motif_tracks_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin
  *     median         median of the per-site read fractions n_modified / n_valid_cov (mean of the two middle ones for an
  *                    even count) — MethylationOutput.Median,
  *     weighted_mean  sum(n_modified) / sum(n_valid_cov) — MethylationOutput.WeightedMean.
- *   Host arrays of n_motifs * n_contigs entries each. */
+ *   Host arrays of n_motifs * n_contigs entries each.  Motifs run in batches of up to 32 per (slot, reach width); a batch whose
+ *   sites with records exceed the key budget (2^30; NM_METH_MAX_KEYS=<positive integer> in the environment, read at every call,
+ *   lowers it) is halved and run again, a single motif proceeds below 2^32 - 1 sites (NM_ERANGE from there): the table is the same. */
 int nm_readstats_upload(nm_ctx *ctx, uint32_t slot, uint64_t n_rows, const uint32_t *contig_id, const uint32_t *position,
                         const uint8_t *strand, const int32_t *n_valid_cov, const int32_t *n_modified, const int32_t *n_diff,
                         int32_t min_valid_read_coverage, double min_valid_cov_to_diff_fraction, int rows_on_device, uint64_t *n_kept);

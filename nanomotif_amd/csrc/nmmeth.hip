@@ -16,6 +16,7 @@
 // segment reads the middle.
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <cstring>
 
 #include <rocprim/device/device_scan.hpp>
@@ -432,6 +433,12 @@ int nm_contig_methylation(nm_ctx *c, uint32_t n_motifs, const uint8_t *motif_slo
     // batches: motifs of one mod code, at most MB of them, all of one reach class (32 / 64 / 96 positions either side)
     constexpr uint32_t MB = 32;
     constexpr uint64_t MAX_KEYS = 1ull << 30;                          // 8 GB of keys (+ as much for the sorted copy) per batch
+    uint64_t max_keys = MAX_KEYS;                                      // NM_METH_MAX_KEYS=<positive integer>: a smaller budget, read per call
+    if (const char *e = getenv("NM_METH_MAX_KEYS")) {                  // (A/B and tests: the only way to the halving below 2^30 sites)
+        char *end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        if (e[0] >= '0' && e[0] <= '9' && end != e && *end == 0 && v > 0) max_keys = std::min<uint64_t>(v, MAX_KEYS);
+    }
     std::vector<std::vector<uint32_t>> batches;
     for (uint32_t slot = 0; slot < NM_MAX_MOD_SLOTS; ++slot)
         for (int wide = 0; wide < 3; ++wide) {
@@ -521,9 +528,9 @@ int nm_contig_methylation(nm_ctx *c, uint32_t n_motifs, const uint8_t *motif_slo
         unsigned long long total = 0;
         HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (total > MAX_KEYS && nb == 1 && total >= 0xFFFFFFFFull)
+        if (total > max_keys && nb == 1 && total >= 0xFFFFFFFFull)
             return fail(NM_ERANGE, "motif %u has %llu sites with records: more than one sort can hold", batch[0], total);
-        if (total > MAX_KEYS && nb > 1) {                              // too many sites at once: halve the batch
+        if (total > max_keys && nb > 1) {                              // too many sites at once: halve the batch
             std::vector<uint32_t> lo(batch.begin(), batch.begin() + nb / 2), hi(batch.begin() + nb / 2, batch.end());
             batches[bi] = lo;
             batches.insert(batches.begin() + bi + 1, hi);

@@ -1,6 +1,7 @@
 """Fuzz of binnary's read-methylation table (nm_readstats_upload + nm_contig_methylation, csrc/nmmeth.hip) ON THE GPU BOX against
 oracle/contig_methylation.read_methylation: random IUPAC motifs (gaps, degenerate letters, lengths 1..14 and a few that reach
-more than 31 / 63 positions from the modified base), both output types, random read filters, a contig-sharded engine.
+more than 31 / 63 positions from the modified base), both output types, random read filters, a contig-sharded engine; half the seeds
+upload their rows in a shuffled order, and coverages reach 0.
 usage: python3 tools/meth_fuzz.py [first_seed [n_seeds]]"""
 import sys
 import time
@@ -50,6 +51,15 @@ def one(seed):
                            seed=int(rng.integers(0, 1 << 30)), min_contig_bp=5_000, fixed_motifs=(("GATC", 1, "a"), ("CCWGG", 1, "m")))
     mg = synth.make_metagenome(spec)
     rec = T._records(mg, rng)
+    for r in rec.values():                                    # coverages down to 0 (dropped whatever min_cov is) on ~4 % of the records
+        low = rng.random(len(r["n_valid"])) < 0.04
+        r["n_valid"] = np.where(low, rng.integers(0, 3, len(low)), r["n_valid"])
+        r["n_mod"] = np.minimum(r["n_mod"], r["n_valid"])
+    if rng.random() < 0.5:                                    # rows in any order: the fill looks them up by position
+        for r in rec.values():
+            perm = rng.permutation(len(r["position"]))
+            for k in r:
+                r[k] = r[k][perm]
     motifs = sorted({random_motif(rng) for _ in range(int(rng.integers(4, 40)))})
     min_cov, min_frac = int(rng.choice([1, 3, 3, 8])), float(rng.choice([0.8, 0.8, 0.5, 0.95]))
     eng = ScanEngine(0)
