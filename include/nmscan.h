@@ -581,6 +581,32 @@ int nm_motif_tracks_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin
                           const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t window_bp,
                           const uint64_t *row_offset, uint32_t *window_counts);
 
+/* ---- READ-FRACTION HISTOGRAMS at motif sites: how n_modified / n_valid_cov is distributed over a motif's sites ------------------------
+ * Reference: none.  The exports above read the thresholded state planes; this call reads the READ STATISTICS (nm_readstats_upload[_bedcols],
+ * below) and tells a mixture of fully methylated and unmethylated sites from sites that are all partially methylated.
+ *
+ * CANDIDATES are spelled as for nm_motif_sites_count, but cand_rs_slot names a READ-STATISTICS slot (filled by nm_readstats_upload or
+ *   nm_readstats_upload_bedcols), not an ingest slot.
+ * OCCURRENCES: strand 0 = the stripped motif on '+', read against '+' records at the modified base; strand 1 = its reverse complement
+ *   on '-', read against '-' records (nm_contig_methylation's semantics).  A SITE is an occurrence whose modified base carries a kept
+ *   record (one that passed the filters of the upload).
+ * BIN of a site: min(n_bins - 1, (uint64) n_modified * n_bins / n_valid_cov), integer division: bin k is [k / B, (k + 1) / B), fraction
+ *   1 falls in the last bin; no floating point takes part.  NM_FRACTIONS_MIN_BINS <= n_bins <= NM_FRACTIONS_MAX_BINS.
+ * ROW = (candidate, contig of its bin): candidate-major, contigs in nm_bin_contigs order — the row numbering of nm_motif_sites_count
+ *   with row_offset = the prefix of the bins' contig counts.  counts = uint64[rows][2 (strand)][n_bins + NM_FRACTIONS_EXTRA]: per strand
+ *   hist[0 .. n_bins), then occurrences (every occurrence of the strand, with or without a record), sum_valid and sum_mod (the sums of
+ *   n_valid_cov and n_modified over the sites).  The caller's table need not be zeroed.
+ * Launches: at most 3 (one per reach width) whatever the batch holds.
+ * NM_EINVAL for NULLs, n_bins out of range and a bad bin; NM_ESTATE without an assembly or for a slot without read statistics;
+ * NM_ERANGE for 2^32 rows or work items and for a motif beyond NM_MAX_MOTIF_LEN / the reach limit as in nm_motif_sites.  n_cand = 0
+ * is NM_OK.  A refusal leaves the ctx usable. */
+#define NM_FRACTIONS_MIN_BINS 2
+#define NM_FRACTIONS_MAX_BINS 64
+#define NM_FRACTIONS_EXTRA 3
+int nm_motif_fractions_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_rs_slot, const uint8_t *cand_len,
+                             const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t n_bins,
+                             uint64_t *counts);
+
 /* ---- per-contig READ methylation of motifs: the table binnary starts from -------------------------
  * Reference: nanomotif/main.py:142-193 — `contig_methylation = methylation_pattern(pileup, assembly, motifs,
  * min_valid_read_coverage, min_valid_cov_to_diff_fraction = 0.8, output_type = Median | WeightedMean)` from the

@@ -59,6 +59,7 @@ def upload_read_statistics(engine, mod_type, contig_local, position, strand, n_v
     kept = C.c_uint64(0)
     _lib.check(engine.lib.nm_readstats_upload(engine.ctx, slot, n, vp(cid), vp(pos), vp(st), vp(nv), vp(nm), vp(nd),
                                               int(min_valid_read_coverage), float(min_valid_cov_to_diff_fraction), 0, C.byref(kept)))
+    engine.readstats_mods.add(mod_type)
     return int(kept.value)
 
 
@@ -138,8 +139,8 @@ def methylation_pattern(pileup, assembly, motifs, threads=1, min_valid_read_cove
         done = False
         if not host_only:
             try:
-                _read_statistics_device(eng, lib, pileup, nthreads, local, wanted, allow_assembly_pileup_mismatch,
-                                        min_valid_read_coverage, min_valid_cov_to_diff_fraction)
+                read_statistics_device(eng, lib, pileup, nthreads, local, wanted, allow_assembly_pileup_mismatch,
+                                       min_valid_read_coverage, min_valid_cov_to_diff_fraction)
                 done = True
                 log.info("pileup: read statistics from the device parser's columns")
             except _lib.NmScanError as e:
@@ -147,8 +148,8 @@ def methylation_pattern(pileup, assembly, motifs, threads=1, min_valid_read_cove
                     raise
                 log.info(f"pileup: the device parser declined ({e}); using the host parser")
         if not done:
-            _read_statistics_host(eng, lib, pileup, threads, local, wanted, allow_assembly_pileup_mismatch,
-                                  min_valid_read_coverage, min_valid_cov_to_diff_fraction)
+            read_statistics_host(eng, lib, pileup, threads, local, wanted, allow_assembly_pileup_mismatch,
+                                 min_valid_read_coverage, min_valid_cov_to_diff_fraction)
             log.info("pileup: read statistics from the host parser's rows")
         rows = read_methylation_table(eng, motifs, output_type)
     finally:
@@ -170,11 +171,13 @@ def _check_mod_code(mt):
         raise ValueError(f"unknown modification type '{mt}' (constants.py:28-37 knows m, a, 21839)")
 
 
-def _read_statistics_device(eng, lib, pileup, threads, local, wanted, allow_assembly_pileup_mismatch, min_valid_read_coverage,
-                            min_valid_cov_to_diff_fraction):
+def read_statistics_device(eng, lib, pileup, threads, local, wanted, allow_assembly_pileup_mismatch, min_valid_read_coverage,
+                           min_valid_cov_to_diff_fraction):
     """The pileup parsed on the device with its count columns -> one read-statistics slot per wanted mod code, straight from the
-    device columns (rows of the other codes are skipped in place)."""
+    device columns (rows of the other codes are skipped in place).  ``local``: contig name -> engine contig index.  Returns
+    {mod code: records kept}."""
     h = C.c_void_p()
+    n_kept = {}
     try:
         _lib.check(lib.nm_bed_parse_device_counts(eng.ctx, os.fsencode(str(pileup)), int(threads), C.byref(h)))
         n, nc = C.c_uint64(0), C.c_uint32(0)
@@ -192,15 +195,19 @@ def _read_statistics_device(eng, lib, pileup, threads, local, wanted, allow_asse
             kept = C.c_uint64(0)
             _lib.check(lib.nm_readstats_upload_bedcols(eng.ctx, h, slot, slot, int(min_valid_read_coverage),
                                                        float(min_valid_cov_to_diff_fraction), C.byref(kept)))
+            eng.readstats_mods.add(mt)
+            n_kept[mt] = int(kept.value)
     finally:
         if h:
             lib.nm_bedcols_close(h)
+    return n_kept
 
 
-def _read_statistics_host(eng, lib, pileup, threads, local, wanted, allow_assembly_pileup_mismatch, min_valid_read_coverage,
-                          min_valid_cov_to_diff_fraction):
+def read_statistics_host(eng, lib, pileup, threads, local, wanted, allow_assembly_pileup_mismatch, min_valid_read_coverage,
+                         min_valid_cov_to_diff_fraction):
     """The same from the host reader's rows (nm_bed_open_counts), uploaded per mod code."""
     h = C.c_void_p()
+    n_kept = {}
     try:
         _lib.check(lib.nm_bed_open_counts(os.fsencode(str(pileup)), int(threads), C.byref(h)))
         n, nc = C.c_uint64(0), C.c_uint32(0)
@@ -222,11 +229,12 @@ def _read_statistics_host(eng, lib, pileup, threads, local, wanted, allow_assemb
         for mt in sorted(wanted):
             _check_mod_code(mt)
             sel = np.flatnonzero(mod == MOD_CODES.index(mt))
-            upload_read_statistics(eng, mt, lut[contig[sel]], position[sel], strand[sel], np.clip(nvalid[sel], -1, 2**31 - 1), nmod[sel],
-                                   ndiff[sel], min_valid_read_coverage, min_valid_cov_to_diff_fraction)
+            n_kept[mt] = upload_read_statistics(eng, mt, lut[contig[sel]], position[sel], strand[sel], np.clip(nvalid[sel], -1, 2**31 - 1), nmod[sel],
+                                                ndiff[sel], min_valid_read_coverage, min_valid_cov_to_diff_fraction)
     finally:
         if h:
             lib.nm_bed_close(h)
+    return n_kept
 
 
 def write_tsv(rows, path, columns=COLUMNS):

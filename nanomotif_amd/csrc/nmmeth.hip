@@ -22,7 +22,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
-#include "nmscan_device.h"
+#include "nmreadstats_device.h"
 
 using namespace nmdetail;
 
@@ -140,19 +140,11 @@ __global__ __launch_bounds__(256) void cm_scan_kernel(CmArgs a) {
     raw.load(a.seq, stp, chunk, lane);
     Tile<K> tile;
     tile.expand(raw);
-    // value index of the first record of this lane's words, per strand: contig base + block rank + the records of the
-    // lanes before it in its 16-word block (a lane owns 4 words)
+    // value index of the first record of this lane's words, per strand (nmreadstats_device.h)
     uint64_t first[2];
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        const uint32_t (&pw)[T_WORDS] = raw.s[0][s * 2];
-        const uint32_t mine = __popc(pw[0]) + __popc(pw[1]) + __popc(pw[2]) + __popc(pw[3]);
-        const uint32_t a1 = __shfl_up(mine, 1), a2 = __shfl_up(mine, 2), a3 = __shfl_up(mine, 3);
-        const int q = lane & 3;
-        const uint32_t before = (q >= 1 ? a1 : 0u) + (q >= 2 ? a2 : 0u) + (q >= 3 ? a3 : 0u);
-        const uint32_t blk = chunk * RANK_PER_CHUNK + (uint32_t)(lane >> 2);
-        first[s] = (s == 0 ? a.base_p : a.base_m)[contig] + (s == 0 ? a.rank_p : a.rank_m)[blk] + before;
-    }
+    for (int s = 0; s < 2; ++s)
+        first[s] = first_record_index(raw.s[0][s * 2], s == 0 ? a.base_p : a.base_m, s == 0 ? a.rank_p : a.rank_m, contig, chunk, lane);
     for (uint32_t m = 0; m < a.n_motifs; ++m) {
         cu32p prog = (cu32p)(a.programs + (size_t)m * (2 * K::PDW));
         uint32_t sites[2][T_WORDS];
@@ -187,21 +179,10 @@ __global__ __launch_bounds__(256) void cm_scan_kernel(CmArgs a) {
         }
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const uint2 *val = s == 0 ? a.val_p : a.val_m;
-            uint64_t idx = first[s];
-#pragma unroll
-            for (int t = 0; t < T_WORDS; ++t) {
-                const uint32_t pw = raw.s[0][s * 2][t];
-                uint32_t x = sites[s][t];
-                while (x) {
-                    const uint32_t b = (uint32_t)__builtin_ctz(x);
-                    x &= x - 1;
-                    const uint2 v = val[idx + __popc(pw & ((1u << b) - 1u))];
-                    if (EMIT) *dst++ = (unsigned long long)__double_as_longlong((double)v.y / (double)v.x);
-                    else { sum_valid += v.x; sum_mod += v.y; }
-                }
-                idx += __popc(pw);
-            }
+            for_each_site_value(raw.s[0][s * 2], sites[s], s == 0 ? a.val_p : a.val_m, first[s], [&](const uint2 v) {
+                if (EMIT) *dst++ = (unsigned long long)__double_as_longlong((double)v.y / (double)v.x);
+                else { sum_valid += v.x; sum_mod += v.y; }
+            });
         }
         if (!EMIT) {
             uint32_t n = n_lane;

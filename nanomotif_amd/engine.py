@@ -38,6 +38,9 @@ TRACKS_MIN_WINDOW = 128                        # NM_TRACKS_MIN_WINDOW: one lane'
 TRACKS_MAX_WINDOW = 1 << 30                    # ... up to NM_TRACKS_MAX_WINDOW
 TRACK_ROW_BYTES = 24                           # a row of ScanEngine.motif_tracks on the device: six uint32
 TRACK_BUDGET_BYTES = 256 << 20                 # default size of the tables of one library call of ScanEngine.motif_tracks
+FRACTIONS_MIN_BINS, FRACTIONS_MAX_BINS = 2, 64 # NM_FRACTIONS_MIN_BINS / NM_FRACTIONS_MAX_BINS: histogram bins of ScanEngine.motif_fractions
+FRACTIONS_EXTRA = 3                            # NM_FRACTIONS_EXTRA: occurrences, sum_valid, sum_mod behind a strand's histogram
+FRACTIONS_BUDGET_BYTES = 256 << 20             # default size of the table of one library call of ScanEngine.motif_fractions
 UNEXPLAINED_DTYPE =np.dtype([("set", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])   # ScanEngine.unexplained_sites
 
 
@@ -485,6 +488,7 @@ class ScanEngine:
         self.bin_index = {}
         self.bin_names = []
         self.slot_of_mod = {}
+        self.readstats_mods = set()      # mod codes whose read statistics are resident (contig_methylation.upload_read_statistics)
         self.comm_world = 0
 
     def close(self):
@@ -535,6 +539,7 @@ class ScanEngine:
         self.contig_lengths = lengths.astype(np.int64)
         self.contig_bin = bin_ids
         self.slot_of_mod = {}
+        self.readstats_mods = set()      # mod codes whose read statistics are resident (contig_methylation.upload_read_statistics)
 
     def upload_assembly_device(self, names, lengths, bin_of_contig, device_ptr: int, bin_names=None):
         """``upload_assembly`` for sequences that are already in device memory: ``device_ptr`` addresses the contigs'
@@ -554,6 +559,7 @@ class ScanEngine:
         self.contig_lengths = lengths.astype(np.int64)
         self.contig_bin = bin_ids
         self.slot_of_mod = {}
+        self.readstats_mods = set()      # mod codes whose read statistics are resident (contig_methylation.upload_read_statistics)
 
     def upload_assembly_fasta(self, assembly, names, bin_of_contig, bin_names=None):
         """``upload_assembly`` for a ``fasta.DeviceAssembly`` (the FASTA was parsed on this device): contig ``names[i]`` is the
@@ -570,6 +576,7 @@ class ScanEngine:
         self.contig_lengths = np.array([assembly.length(n) for n in names], dtype=np.int64)
         self.contig_bin = bin_ids
         self.slot_of_mod = {}
+        self.readstats_mods = set()      # mod codes whose read statistics are resident (contig_methylation.upload_read_statistics)
 
     def contig_base_counts(self, base: str, padding: int) -> np.ndarray:
         """Per resident contig: positions p in [padding, len - padding) whose base is ``base`` — the number of valid
@@ -1163,6 +1170,51 @@ class ScanEngine:
             _lib.check(self.lib.nm_motif_tracks_count(self.ctx, *self._batch_args(sub), w, _ptr(rows, C.c_uint64), _ptr(table, C.c_uint32)))
             for j in range(k, e):
                 yield names[bins[j]], prefix[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
+            k = e
+
+    # ------------------------------------------------------------------ read-fraction histograms at motif sites (nm_motif_fractions_count)
+    def motif_fractions(self, candidates, bins=20, max_bytes=None):
+        """Generator over the read-fraction histograms of ``candidates`` (sequence of (Motif, mod_type, bin)) on the contigs of their
+        bins, read against the READ STATISTICS of the candidate's mod code (``contig_methylation.upload_read_statistics`` /
+        ``read_statistics_device``), nm_motif_fractions_count.  Yields one item per candidate, in call order: (the candidate, contig names
+        in ``bin_contigs`` order, uint64[n_contigs, 2, bins + 3]) — per strand (0: the motif on '+' against '+' records, 1: its reverse
+        complement on '-' against '-' records) the histogram of the sites' n_modified / n_valid_cov over ``bins`` equal bins (a site's bin
+        is min(bins - 1, n_modified * bins // n_valid_cov)), then the occurrences (with or without a record), the sum of n_valid_cov and
+        the sum of n_modified over the sites.  ``bins``: 2..64.  A candidate of a mod code without resident read statistics is a
+        ValueError.  Consecutive candidates share one library call while their table fits ``max_bytes`` (default
+        ``FRACTIONS_BUDGET_BYTES``); a group always holds at least one candidate.  What is yielded does not depend on ``max_bytes``."""
+        from .contig_methylation import MOD_CODES
+        bins = int(bins)
+        if not FRACTIONS_MIN_BINS <= bins <= FRACTIONS_MAX_BINS:
+            raise ValueError(f"bins {bins} outside {FRACTIONS_MIN_BINS}..{FRACTIONS_MAX_BINS}")
+        limit = FRACTIONS_BUDGET_BYTES if max_bytes is None else int(max_bytes)
+        if limit < 1:
+            raise ValueError("max_bytes must be at least 1")
+        candidates = list(candidates)
+        missing = sorted({str(c[1]) for c in candidates if c[1] not in self.readstats_mods})
+        if missing:
+            raise ValueError(f"no read statistics are resident for mod type(s) {', '.join(missing)} (resident: {', '.join(sorted(self.readstats_mods)) or 'none'})")
+        b = self.make_batch(candidates, slot_of=lambda mt: MOD_CODES.index(mt))
+        return self._fraction_groups(candidates, b, bins, limit)
+
+    def _fraction_groups(self, candidates, b: CandidateBatch, nb: int, limit: int):
+        bins = [int(x) for x in b.bins]
+        names = {bid: self.bin_contigs(bid) for bid in sorted(set(bins))}
+        width = nb + FRACTIONS_EXTRA
+        row_bytes = 2 * width * 8
+        n, k = len(b), 0
+        while k < n:
+            e, held = k + 1, len(names[bins[k]]) * row_bytes
+            while e < n and held + len(names[bins[e]]) * row_bytes <= limit:
+                held += len(names[bins[e]]) * row_bytes
+                e += 1
+            rows = np.zeros(e - k + 1, dtype=np.int64)
+            np.cumsum([len(names[bins[j]]) for j in range(k, e)], out=rows[1:])
+            table = np.zeros((max(int(rows[-1]), 1), 2, width), dtype=np.uint64)
+            sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
+            _lib.check(self.lib.nm_motif_fractions_count(self.ctx, *self._batch_args(sub), nb, _ptr(table, C.c_uint64)))
+            for j in range(k, e):
+                yield candidates[j], names[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
             k = e
 
     # ------------------------------------------------------------------ coverage of a set of motifs (nm_motif_coverage_*)

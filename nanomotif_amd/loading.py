@@ -109,6 +109,24 @@ def upload_assembly(eng: ScanEngine, assembly, names: list, bins: list, bin_name
         eng.upload_assembly(names, [assembly[c] for c in names], bins, bin_names=bin_names)
 
 
+def open_assembly(eng: ScanEngine, args, bin_contig: dict, threads: int):
+    """The assembly of the command line, read by the device FASTA parser (a gzip file and NANOMOTIF_HOST_FASTA=1: the host reader), with
+    the aliased placements of ``bin_contig`` added.  Returns (assembly, the entries of ``bin_contig`` whose contig the assembly holds);
+    the assembly is the caller's to close when it has a ``close``."""
+    device_fasta = not str(args.assembly).endswith(".gz") and os.environ.get("NANOMOTIF_HOST_FASTA") != "1"
+    assembly = fasta.DeviceAssembly(eng, args.assembly, threads=threads) if device_fasta else fasta.load_fasta(args.assembly)
+    try:
+        fasta.add_alias_sequences(assembly, bin_contig)
+        bin_contig = {c: b for c, b in bin_contig.items() if c in assembly}
+        if not bin_contig:
+            raise ValueError("No contigs remain in bin_contig after filtering against the assembly")
+    except BaseException:
+        if hasattr(assembly, "close"):
+            assembly.close()
+        raise
+    return assembly, bin_contig
+
+
 def load_engine(args, device: int, pileups=None) -> ScanEngine:
     """Assembly and pileup of the command line -> an engine whose state planes are ``motif_discovery``'s on one GPU: the readers
     (device-side FASTA and bedMethyl parsers, the host readers where those decline; a bgzip pileup through its tabix index for the
@@ -124,12 +142,7 @@ def load_engine(args, device: int, pileups=None) -> ScanEngine:
     eng = ScanEngine(device)
     assembly = None
     try:
-        device_fasta = not str(args.assembly).endswith(".gz") and os.environ.get("NANOMOTIF_HOST_FASTA") != "1"
-        assembly = fasta.DeviceAssembly(eng, args.assembly, threads=threads) if device_fasta else fasta.load_fasta(args.assembly)
-        fasta.add_alias_sequences(assembly, bin_contig)
-        bin_contig = {c: b for c, b in bin_contig.items() if c in assembly}
-        if not bin_contig:
-            raise ValueError("No contigs remain in bin_contig after filtering against the assembly")
+        assembly, bin_contig = open_assembly(eng, args, bin_contig, threads)
         names = list(bin_contig)
         eng.pileup_ingests = []
         for path, label_of in pileups:
@@ -161,3 +174,59 @@ def kept_mod_types(eng: ScanEngine) -> list:
     kept = [np.asarray(r["kept"]) for r in eng.pileup_ingests]
     present = {mt for code, mt in enumerate(pileup_mod.MOD_TYPES) if any(k[:, code].any() for k in kept)}
     return [mt for mt in sorted((m for m in pileup_mod.MOD_TYPES if m in eng.slot_of_mod), key=eng.slot_of_mod.get) if mt in present]
+
+
+class AliasedContigs(ValueError):
+    """A contig is listed under several bins where the command cannot serve that (``load_readstats_engine``)."""
+
+
+def load_readstats_engine(args, device: int, mod_types) -> ScanEngine:
+    """Assembly and pileup of the command line -> an engine that holds the BINNED assembly exactly as ``load_engine`` puts it (same
+    readers, the binned contigs the assembly holds, the run's bins) and the READ STATISTICS of ``mod_types`` (the mod codes wanted) in
+    place of the state planes: every pileup record with ``n_valid_cov >= args.min_valid_read_coverage`` and ``n_valid_cov / (n_valid_cov
+    + n_diff) >= args.min_valid_cov_to_diff_fraction`` keeps its (n_valid_cov, n_modified).  The pileup goes through
+    ``contig_methylation.read_statistics_device`` (parsed on the device, one upload per mod code from the parser's columns), or
+    ``read_statistics_host`` when the device parser declines or NANOMOTIF_HOST_PARSER=1; pileup contigs outside the bins are ignored.
+    ``eng.readstats_kept``: mod code -> records kept.  A contig listed under several bins would need its rows twice in one upload:
+    ``AliasedContigs`` names it before any device is touched."""
+    from . import contig_methylation as cm
+    bin_contig = fasta.generate_contig_bin(args)
+    if not bin_contig:
+        raise ValueError("No bin contig mapping found")
+    aliased = sorted({fasta.original_name(c) for c in bin_contig if fasta.ALIAS_SEP in c})
+    if aliased:
+        raise AliasedContigs(f"{len(aliased)} contig(s) are listed under several bins (e.g. {aliased[0]}): the read statistics hold a pileup row once, "
+                             "so a contig cannot be read in two bins of one run; list it under one bin")
+    threads = parser_threads(args)
+    eng = ScanEngine(device)
+    assembly = None
+    try:
+        assembly, bin_contig = open_assembly(eng, args, bin_contig, threads)
+        names = list(bin_contig)
+        upload_assembly(eng, assembly, names, [bin_contig[c] for c in names], sorted(set(bin_contig.values())))
+        if hasattr(assembly, "close"):
+            assembly.close()
+        assembly = None
+        local = {c: i for i, c in enumerate(names)}
+        wanted = set(mod_types)
+        filters = (int(args.min_valid_read_coverage), float(args.min_valid_cov_to_diff_fraction))
+        kept = None
+        if os.environ.get("NANOMOTIF_HOST_PARSER") != "1":
+            try:
+                kept = cm.read_statistics_device(eng, eng.lib, args.pileup, threads, local, wanted, True, *filters)
+                log.info("pileup: read statistics from the device parser's columns")
+            except _lib.NmScanError as e:
+                if e.code != _lib.NM_EDECLINED:
+                    raise
+                log.info(f"pileup: the device parser declined ({e}); using the host parser")
+        if kept is None:
+            kept = cm.read_statistics_host(eng, eng.lib, args.pileup, getattr(args, "threads", 1), local, wanted, True, *filters)
+            log.info("pileup: read statistics from the host parser's rows")
+        eng.readstats_kept = kept
+        return eng
+    except BaseException:
+        eng.close()
+        raise
+    finally:
+        if assembly is not None and hasattr(assembly, "close"):
+            assembly.close()

@@ -186,10 +186,10 @@ def candidates_of_files(paths) -> list:
     return out
 
 
-def open_run(command: str, args, timings: dict, pileups=None):
-    """How the four export commands open: the refusal of a multi-rank launch, the candidates of ``--bin_motifs`` (one file or
-    several), the loaded engine (``loading.load_engine`` with ``pileups``) and ``timings["ingest_s"]``.  Returns (engine, candidates,
-    0), or (None, None, the exit status) when the command does not run."""
+def open_candidates(command: str, args, timings: dict):
+    """How every export command opens, before anything is loaded: the refusal of a multi-rank launch and the candidates of
+    ``--bin_motifs`` (one file or several).  Returns (candidates, the GPU to use, 0), or (None, None, the exit status) when the command
+    does not run."""
     timings.clear()
     if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
         log.error("%s runs on one GPU: start it without a multi-rank launcher (WORLD_SIZE is %s)", command, os.environ["WORLD_SIZE"])
@@ -198,6 +198,16 @@ def open_run(command: str, args, timings: dict, pileups=None):
     cands = candidates_of_files(files)
     log.info(f"{len(cands)} (bin, motif) candidates from {', '.join(files)}")
     device = args.device if args.device is not None else int(os.environ.get("LOCAL_RANK", "0") or 0)
+    return cands, device, 0
+
+
+def open_run(command: str, args, timings: dict, pileups=None):
+    """How the export commands that read the state planes open: ``open_candidates``, the loaded engine (``loading.load_engine`` with
+    ``pileups``) and ``timings["ingest_s"]``.  Returns (engine, candidates, 0), or (None, None, the exit status) when the command does
+    not run."""
+    cands, device, status = open_candidates(command, args, timings)
+    if cands is None:
+        return None, None, status
     t0 = time.perf_counter()
     try:
         eng = load_engine(args, device, pileups)
