@@ -10,7 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
-SRC_HIP = [os.path.join(_CSRC, f) for f in ("nmscan.hip", "nmingest.hip", "nmwindows.hip", "nmmeth.hip", "nmbedgpu.hip", "nmfasta.hip", "nmsites.hip",
+SRC_HIP = [os.path.join(_CSRC, f) for f in ("nmscan.hip", "nmscore_classes.hip", "nmingest.hip", "nmwindows.hip", "nmmeth.hip", "nmbedgpu.hip", "nmfasta.hip", "nmsites.hip",
                                                   "nmcoverage.hip", "nmcompare.hip", "nmstrands.hip", "nmprofile.hip", "nmtracks.hip", "nmfractions.hip")]
 SRC_HOST = [os.path.join(_CSRC, f) for f in ("nmbed.cpp", "nmhost.cpp", "nmcomm.cpp", "nmsearch.cpp", "nmpost.cpp", "nmpool.cpp", "nmsitestext.cpp")]
 OUT = os.path.join(_HERE, "libnmscan.so")
@@ -20,6 +20,18 @@ SYNTH_SRC = os.path.join(_CSRC, "bench", "nmsynth.cpp")
 SYNTH_OUT = os.path.join(_HERE, "libnmsynth.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "nmscan.h")
 OBJ_DIR = os.path.join(_CSRC, "_build")
+
+
+def unit_flags() -> dict:
+    """Flags of single translation units, declared beside the kernels they are for: lines ``// NM_UNIT_FLAGS <file>: <flags>``
+    of csrc/nmscan_device.h."""
+    out = {}
+    with open(os.path.join(_CSRC, "nmscan_device.h")) as f:
+        for line in f:
+            if line.startswith("// NM_UNIT_FLAGS "):
+                name, _, flags = line[len("// NM_UNIT_FLAGS "):].partition(":")
+                out[name.strip()] = flags.split()
+    return out
 
 
 def _headers():
@@ -51,11 +63,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
     common = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=off"] + extra
     jobs = []
     objs = []
+    per_unit = unit_flags()
     for s in srcs:
         o = os.path.join(OBJ_DIR, os.path.basename(s) + ".o")
         objs.append(o)
         if force or not os.path.exists(o) or os.path.getmtime(o) < max(os.path.getmtime(s), hdr_time):
-            jobs.append(common + ["-c", s, "-o", o])
+            jobs.append(common + per_unit.get(os.path.basename(s), []) + ["-c", s, "-o", o])
     if not jobs and os.path.exists(OUT) and all(os.path.getmtime(OUT) >= os.path.getmtime(o) for o in objs):
         return OUT
 

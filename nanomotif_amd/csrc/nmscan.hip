@@ -17,6 +17,7 @@
 //     complement base), so they are OR-ed and counted with two popcounts against M and U.
 //   * Per-lane counts go to LDS with ds_add, are reduced once per workgroup segment and leave the CU as one
 //     64-bit atomic per counter.
+#define NM_SCORE_KERNEL_SOURCE
 #include "nmscan_device.h"
 
 using namespace nmdetail;
@@ -28,24 +29,6 @@ thread_local std::string g_err;
 // ------------------------------------------------------------------------------------------------------
 // device code
 // ------------------------------------------------------------------------------------------------------
-struct ScoreArgs {
-    Planes seq;
-    StatePlanes st[NM_MAX_MOD_SLOTS];
-    const uint4 *segments;      // {first chunk, n chunks, bin, 0}
-    uint32_t n_segments;
-    uint32_t split_log2;        // every segment is cut into 1 << split_log2 pieces
-    uint32_t pieces_per_run, j_big, fine_log2;   // per run of pieces: the first j_big go whole, the rest in 1 << fine_log2 parts
-    uint32_t n_bins;
-    const uint4 *cand_range;    // [active_slot_index][bin] -> {begin, count, common program or ~0, -} into programs
-    const uint32_t *programs;   // [n_prog][2 * (GN + GP) * 8], sorted by (slot, bin)
-    const uint32_t *orig_index; // [n_cand] sorted -> caller order
-    unsigned long long *out;    // [n_cand][2]; per-contig mode: [rows][2], row = row_base[candidate] + rank of the contig in its bin
-    const uint32_t *chunk_rank; // per chunk: rank of its contig within its bin (per-contig mode)
-    const uint64_t *row_base;   // [n_prog] sorted order (per-contig mode)
-    uint32_t active_slot[NM_MAX_MOD_SLOTS];
-    uint32_t slot_is_c[NM_MAX_MOD_SLOTS];   // canonical base of the slot is C (else A)
-};
-
 // Pack: one workgroup per chunk, 64 positions per wave per step, wave ballot builds the plane words.
 __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ ascii,
                                                    const uint64_t *__restrict__ contig_src,
@@ -129,330 +112,14 @@ __global__ void state_kernel(uint64_t n_rows, const uint32_t *__restrict__ conti
     if (v && h == want_h && l == can_l) atomicOr((meth ? M : U) + w, bit);
 }
 
-// acc = base & (the ONE constraint `desc` = (mask index << 5) | r of a strand): the residual of a sibling child once the
-// parent's constraints are in `base`.  The mask index selects registers, so it is dispatched through a switch.
-template <class K, int I = 0>
-__device__ __forceinline__ void apply_single(uint32_t idx, uint32_t r, const Tile<K> &tile, const uint32_t (&base)[T_WORDS],
-                                             uint32_t (&acc)[T_WORDS]) {
-    if constexpr (I < K::PDW) {
-        if (idx == I) {
-            constexpr int g = I / K::NP, p = I % K::NP;
-#pragma unroll
-            for (int t = 0; t < T_WORDS; ++t) acc[t] = base[t] & alignbit(tile.w[p][t + g + 1], tile.w[p][t + g], r);
-        } else {
-            apply_single<K, I + 1>(idx, r, tile, base, acc);
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < T_WORDS; ++t) acc[t] = base[t];      // idx == PDW: no constraint left on this strand
-    }
-}
-
-// Candidate k's two counters of this wave: one (candidate, contig) row of the count table (PC), or the lane's LDS slots.
-template <class K>
-__device__ __forceinline__ void emit_counts(const ScoreArgs &a, uint32_t n_mod, uint32_t n_non, uint32_t k0, uint32_t k,
-                                            uint32_t *lds_acc, uint32_t lds_row0, int lane, uint32_t contig_rank) {
-    if (K::PC) {
-        // per-contig counters (motif_model_contig per contig, find_motifs_bin.py:1285-1331): a chunk lies inside ONE
-        // contig, so the wave's sum goes straight to that (candidate, contig) row
-#pragma unroll
-        for (int o = 32; o; o >>= 1) {
-            n_mod += __shfl_xor(n_mod, o);
-            n_non += __shfl_xor(n_non, o);
-        }
-        if (lane == 0 && (n_mod | n_non)) {
-            unsigned long long *row = a.out + (a.row_base[k0 + k] + contig_rank) * 2;
-            if (n_mod) atomicAdd(row, (unsigned long long)n_mod);
-            if (n_non) atomicAdd(row + 1, (unsigned long long)n_non);
-        }
-        return;
-    }
-    atomicAdd(&lds_acc[((k * K::NS + lds_row0) * 2 + 0) * 64 + lane], n_mod);
-    atomicAdd(&lds_acc[((k * K::NS + lds_row0) * 2 + 1) * 64 + lane], n_non);
-}
-
-// Heavy batches (the non-CF variants): both strands of a candidate from its forward masks (JointWalk, nmscan_device.h), one
-// s_load_dwordx16 per candidate.
-template <class K, int CAN>
-__device__ __forceinline__ void score_heavy(const ScoreArgs &a, const Tile<K> &tile, const uint32_t (&sw)[K::NST][T_WORDS],
-                                            uint32_t k0, uint32_t nb, uint32_t *lds_acc, uint32_t lds_row0, int lane,
-                                            uint32_t contig_rank) {
-    constexpr int PF = CAN == 0 ? 0 : 1;   // plane of the canonical base: A or C
-    constexpr int PR = CAN == 0 ? 3 : 2;   // plane of its complement:     T or G
-    uint32_t basef[T_WORDS], baser[T_WORDS];
-#pragma unroll
-    for (int t = 0; t < T_WORDS; ++t) {
-        // compact batches: the canonical literal at the modified position is left out of the program, the plane is the
-        // walk's base
-        basef[t] = K::COMPACT ? tile.w[PF][t + K::GN] : 0xFFFFFFFFu;
-        baser[t] = K::COMPACT ? tile.w[PR][t + K::GN] : 0xFFFFFFFFu;
-    }
-    JointWalk<K> jw;
-    for (uint32_t k = 0; k < nb; ++k) {
-        cu32p prog = (cu32p)(a.programs + (size_t)(k0 + k) * (2 * K::PDW));
-        uint32_t m[K::PDW];
-#pragma unroll
-        for (int i = 0; i < K::PDW; ++i) m[i] = prog[i];
-        jw.walk(m, tile, basef, baser);
-        uint32_t n_mod = 0, n_non = 0;
-#pragma unroll
-        for (int t = 0; t < T_WORDS; ++t) {
-            if (K::COMPACT) {
-                const uint32_t sites = jw.accf[t] | jw.accr[t];  // forward sites sit on the canonical base, reverse on its complement
-                n_mod += __popc(sites & sw[0][t]);
-                n_non += __popc(sites & sw[1][t]);
-            } else {
-                n_mod += __popc(jw.accf[t] & sw[0][t]) + __popc(jw.accr[t] & sw[K::COMPACT ? 0 : 2][t]);
-                n_non += __popc(jw.accf[t] & sw[1][t]) + __popc(jw.accr[t] & sw[K::COMPACT ? 1 : 3][t]);
-            }
-        }
-        emit_counts<K>(a, n_mod, n_non, k0, k, lds_acc, lds_row0, lane, contig_rank);
-    }
-}
-
-// One slot's candidates [k0, k0 + nb) against the tile this wave holds: match masks, site counts, per-lane counts into
-// LDS rows k * NS + lds_row0 (lds_row0 = the slot's index in the workgroup).  CAN: canonical base of the slot, 0 = A (reverse-strand sites sit on T), 1 = C (reverse on G).
-// common != ~0u: program index of the constraints shared by all nb candidates (their own programs hold the rest).
-template <class K, int CAN>
-__device__ __forceinline__ void score_candidates(const ScoreArgs &a, const Tile<K> &tile, const uint32_t (&sw)[K::NST][T_WORDS],
-                                                 uint32_t k0, uint32_t nb, uint32_t common, bool siblings, uint32_t *lds_acc,
-                                                 uint32_t lds_row0, int lane, uint32_t contig_rank = 0) {
-    if constexpr (!K::CF) {
-        score_heavy<K, CAN>(a, tile, sw, k0, nb, lds_acc, lds_row0, lane, contig_rank);
-        return;
-    }
-    constexpr int PF = CAN == 0 ? 0 : 1;   // plane of the canonical base: A or C
-    constexpr int PR = CAN == 0 ? 3 : 2;   // plane of its complement:     T or G
-    uint32_t basef[T_WORDS], baser[T_WORDS];
-#pragma unroll
-    for (int t = 0; t < T_WORDS; ++t) {
-        // compact batches: every candidate has the canonical literal at its modified position, the compiler leaves
-        // that constraint out of the program and it becomes the accumulator's initial value
-        basef[t] = K::COMPACT ? tile.w[PF][t + K::GN] : 0xFFFFFFFFu;
-        baser[t] = K::COMPACT ? tile.w[PR][t + K::GN] : 0xFFFFFFFFu;
-    }
-    if (common != 0xFFFFFFFFu) {                                             // wave-uniform
-        cu32p prog = (cu32p)(a.programs + (size_t)common * (2 * K::PDW));
-        eval_strand<K>(prog, tile, basef);
-        eval_strand<K>(prog + K::PDW, tile, baser);
-    }
-    // Scalar loads of the masks are software-pipelined at strand granularity: the reverse masks of candidate k are
-    // requested before its forward strand is evaluated, the forward masks of candidate k + 1 before its reverse strand —
-    // two sets of SGPRs like before, but a load's latency hides behind ~40 vector instructions instead of standing in
-    // front of every strand.
-    uint32_t mf[K::PDW], mr[K::PDW];
-    if (!siblings) {
-        cu32p prog = (cu32p)(a.programs + (size_t)k0 * (2 * K::PDW));
-#pragma unroll
-        for (int i = 0; i < K::PDW; ++i) mf[i] = prog[i];
-    }
-    for (uint32_t k = 0; k < nb; ++k) {
-        cu32p prog = (cu32p)(a.programs + (size_t)(k0 + k) * (2 * K::PDW));
-        uint32_t accf[T_WORDS], accr[T_WORDS];
-        if (siblings) {                                                      // wave-uniform: one constraint per strand left
-            const uint32_t df = prog[0], dr = prog[1];
-            apply_single<K>(df >> 5, df & 31u, tile, basef, accf);
-            apply_single<K>(dr >> 5, dr & 31u, tile, baser, accr);
-        } else {
-#pragma unroll
-            for (int i = 0; i < K::PDW; ++i) mr[i] = prog[K::PDW + i];
-#pragma unroll
-            for (int t = 0; t < T_WORDS; ++t) accf[t] = basef[t];
-            eval_masks<K>(mf, tile, accf);
-            cu32p next = (cu32p)(a.programs + (size_t)(k0 + min(k + 1, nb - 1)) * (2 * K::PDW));
-#pragma unroll
-            for (int i = 0; i < K::PDW; ++i) mf[i] = next[i];
-#pragma unroll
-            for (int t = 0; t < T_WORDS; ++t) accr[t] = baser[t];
-            eval_masks<K>(mr, tile, accr);
-        }
-        uint32_t n_mod = 0, n_non = 0;
-#pragma unroll
-        for (int t = 0; t < T_WORDS; ++t) {
-            if (K::COMPACT) {
-                const uint32_t sites = accf[t] | accr[t];       // forward sites sit on the canonical base, reverse on its complement
-                n_mod += __popc(sites & sw[0][t]);
-                n_non += __popc(sites & sw[1][t]);
-            } else {
-                n_mod += __popc(accf[t] & sw[0][t]) + __popc(accr[t] & sw[K::COMPACT ? 0 : 2][t]);
-                n_non += __popc(accf[t] & sw[1][t]) + __popc(accr[t] & sw[K::COMPACT ? 1 : 3][t]);
-            }
-        }
-        emit_counts<K>(a, n_mod, n_non, k0, k, lds_acc, lds_row0, lane, contig_rank);
-    }
-}
-
-// With NS > 1 a tile's sequence planes are loaded and expanded once and serve the candidates of all NS slots (each slot
-// brings its own state planes); with NS = 1 the slot comes from blockIdx.y.  A pass handles up to BMAX / NS candidates
-// per slot; LDS rows are [candidate k][slot j].
-// One PIECE of work: the chunks [sg.x, sg.x + sg.y) of bin sg.z, all candidates of the workgroup's slot column(s), counters
-// accumulated in LDS and flushed to the count table at the end.  Called once per workgroup by score_kernel (piece = a
-// segment or a part of one).
-template <class K>
-__device__ __forceinline__ void score_piece(const ScoreArgs &a, const uint4 sg, const StatePlanes (&stp)[K::NS], const bool (&is_c)[K::NS],
-                                            uint32_t *lds_acc, const int lane, const uint32_t wave) {
-    constexpr int NS = K::NS;
-    constexpr uint32_t H = BMAX / NS;
-    // the wave's first chunk is requested before anything else of the segment is looked at (candidate ranges, LDS
-    // clearing, the barrier): a workgroup lives for four chunks per wave, its start-up chain would otherwise sit
-    // in front of every fourth memory round trip
-    constexpr bool EARLY = K::CF && K::LIT;          // (the 8-plane light tiles would drop from 5 to 4 waves per SIMD)
-    RawChunk<K> first;
-    if (EARLY && wave < sg.y) first.load(a.seq, stp, sg.x + wave, lane);
-    uint4 range[NS];                                // {first program, candidates, common program or ~0, siblings}
-    uint32_t most = 0;
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-        const uint32_t slot_i = NS == 1 ? blockIdx.y : (uint32_t)j;
-        range[j] = a.cand_range[(size_t)slot_i * a.n_bins + sg.z];
-        range[j].x = __builtin_amdgcn_readfirstlane(range[j].x);
-        range[j].y = __builtin_amdgcn_readfirstlane(range[j].y);
-        range[j].z = __builtin_amdgcn_readfirstlane(range[j].z);
-        range[j].w = __builtin_amdgcn_readfirstlane(range[j].w);
-        most = max(most, range[j].y);
-    }
-    if (most == 0) return;
-
-    // one chunk of one pass: tile, then every slot's candidates of this pass
-    auto score_chunk = [&](const RawChunk<K> &cur, uint32_t pass0, uint32_t chunk) {
-        Tile<K> tile;
-        tile.expand(cur);
-        const uint32_t rank = K::PC ? ((cu32p)a.chunk_rank)[chunk] : 0u;
-        // one slot at a time with the slot index a compile-time constant: left to `#pragma unroll`, the optimizer gave up on
-        // the NS = 2 non-literal bodies ("loop not unrolled") and indexed cur.s[j] / range[j] / is_c[j] through private
-        // memory — 192-288 bytes of scratch per lane in five variants (round-3 review)
-        auto one_slot = [&](auto jc) {
-            constexpr int j = decltype(jc)::value;
-            if (range[j].y <= pass0) return;                         // wave-uniform
-            const uint32_t nbj = min(H, range[j].y - pass0);
-            if (K::COMPACT && is_c[j])
-                score_candidates<K, 1>(a, tile, cur.s[j], range[j].x + pass0, nbj, range[j].z, range[j].w != 0, lds_acc, j, lane, rank);
-            else
-                score_candidates<K, 0>(a, tile, cur.s[j], range[j].x + pass0, nbj, range[j].z, range[j].w != 0, lds_acc, j, lane, rank);
-        };
-        one_slot(std::integral_constant<int, 0>{});
-        if constexpr (NS > 1) one_slot(std::integral_constant<int, 1>{});
-        static_assert(NS <= 2, "slot fusion is written for one or two slots");
-    };
-    auto clear_rows = [&](uint32_t rows_hi) {
-        if (K::PC) return;
-        for (uint32_t i = threadIdx.x; i < rows_hi * 128; i += 256) lds_acc[i] = 0;
-        __syncthreads();
-    };
-    // 4 threads per counter, 16 lane-slots each, then a 4-lane butterfly; one 64-bit atomic per counter
-    auto flush_rows = [&](uint32_t rows_hi, uint32_t pass0) {
-        if (K::PC) return;
-        __syncthreads();
-        for (uint32_t idx = threadIdx.x; idx < rows_hi * 8; idx += 256) {
-            const uint32_t i = idx >> 2, q = idx & 3;               // i = counter row: (k * NS + j) * 2 + which
-            const uint32_t j = (i >> 1) % NS, k = (i >> 1) / NS;
-            uint32_t s = 0;
-#pragma unroll 4
-            for (int jj = 0; jj < 16; ++jj) s += lds_acc[i * 64 + q * 16 + jj];
-            s += __shfl_xor(s, 1);
-            s += __shfl_xor(s, 2);
-            if (q == 0 && s) {
-                uint4 rj = range[0];
-#pragma unroll
-                for (int t = 1; t < NS; ++t)
-                    if (j == (uint32_t)t) rj = range[t];
-                if (pass0 + k < rj.y) {
-                    const uint32_t orig = a.orig_index[rj.x + pass0 + k];
-                    atomicAdd(a.out + (size_t)orig * 2 + (i & 1), (unsigned long long)s);
-                }
-            }
-        }
-        __syncthreads();
-    };
-    // LDS rows in use in a pass: row = k * NS + j for candidate k of slot j
-    uint32_t pass0 = 0;
-    if (EARLY) {                                                     // pass 0 with the chunk already under way
-        const uint32_t rows_hi = NS * min(H, most);
-        clear_rows(rows_hi);
-        if (wave < sg.y) score_chunk(first, 0, sg.x + wave);
-        for (uint32_t ck = wave + 4; ck < sg.y; ck += 4) {
-            RawChunk<K> cur;
-            cur.load(a.seq, stp, sg.x + ck, lane);
-            score_chunk(cur, 0, sg.x + ck);
-        }
-        flush_rows(rows_hi, 0);
-        pass0 = H;
-    }
-    for (; pass0 < most; pass0 += H) {
-        const uint32_t rows_hi = NS * min(H, most - pass0);
-        clear_rows(rows_hi);
-        for (uint32_t ck = wave; ck < sg.y; ck += 4) {
-            RawChunk<K> cur;
-            cur.load(a.seq, stp, sg.x + ck, lane);
-            score_chunk(cur, pass0, sg.x + ck);
-        }
-        flush_rows(rows_hi, pass0);
-    }
-}
-
-#define NM_SCORE_BOUNDS __launch_bounds__(256, (K::GN + K::GP > 2 ? 2 : (K::LIT ? NM_LIT_WAVES : 4)))
-
-// per-slot facts are read from the kernel arguments once per workgroup
-#define NM_SLOT_SETUP                                                                                               \
-    const int lane = threadIdx.x & 63;                                                                              \
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); /* provably uniform: chunk indices stay scalar */ \
-    StatePlanes stp[K::NS];                                                                                         \
-    bool is_c[K::NS];                                                                                               \
-    _Pragma("unroll") for (int j = 0; j < K::NS; ++j) {                                                             \
-        const uint32_t slot = a.active_slot[K::NS == 1 ? blockIdx.y : (uint32_t)j];                                 \
-        stp[j] = a.st[slot];                                                                                        \
-        is_c[j] = a.slot_is_c[slot] != 0;                                                                           \
-    }
-
-template <class K>
-__global__ NM_SCORE_BOUNDS void score_kernel(ScoreArgs a) {
-    __shared__ uint32_t lds_acc[BMAX * 2 * 64];
-    // XCD-aware remap: blocks b and b+8 share an XCD (round-robin dispatch), give every XCD a contiguous run
-    // of segments so candidate programs and counters of one bin stay in one L2.
-    // (a light batch streams: there the remap costs 3 % of the read rate, tools/stream_pattern.hip)
-    const uint32_t lanes_x = K::CF ? 1u : 8u;                  // runs of pieces: one per XCD, or a single one
-    const uint32_t x = K::CF ? 0u : blockIdx.x % 8, j = K::CF ? blockIdx.x : blockIdx.x / 8;
-    // Pieces: a segment (16 chunks), or a half / quarter of one for assemblies that fill the device for less than two
-    // rounds of workgroups (split_log2).  The workgroups dispatched LAST (j >= j_big in every run) take pieces cut
-    // finer still (fine_log2): the last, partly filled round of workgroups then lasts a quarter as long.
-    uint32_t piece, sub = 0, n_sub = 1;
-    if (j < a.j_big) piece = x * a.pieces_per_run + j;
-    else {
-        const uint32_t k = j - a.j_big;
-        piece = x * a.pieces_per_run + a.j_big + (k >> a.fine_log2);
-        sub = k & ((1u << a.fine_log2) - 1);
-        n_sub = 1u << a.fine_log2;
-        if (a.j_big + (k >> a.fine_log2) >= a.pieces_per_run) return;
-    }
-    (void)lanes_x;
-    const uint32_t seg = piece >> a.split_log2;
-    if (seg >= a.n_segments) return;
-    uint4 sg = a.segments[seg];
-    sg.x = __builtin_amdgcn_readfirstlane(sg.x);   // everything below is wave-uniform: keep it in SGPRs
-    sg.y = __builtin_amdgcn_readfirstlane(sg.y);
-    sg.z = __builtin_amdgcn_readfirstlane(sg.z);
-    if (a.split_log2) {
-        const uint32_t len = (sg.y + (1u << a.split_log2) - 1) >> a.split_log2;
-        const uint32_t at = (piece & ((1u << a.split_log2) - 1)) * len;
-        if (at >= sg.y) return;
-        sg.x += at;
-        sg.y = min(len, sg.y - at);
-    }
-    if (n_sub > 1) {
-        const uint32_t len = (sg.y + n_sub - 1) / n_sub;
-        const uint32_t at = sub * len;
-        if (at >= sg.y) return;
-        sg.x += at;
-        sg.y = min(len, sg.y - at);
-    }
-    NM_SLOT_SETUP
-    score_piece<K>(a, sg, stp, is_c, lds_acc, lane, wave);
-}
-
 __global__ void compile_kernel(uint32_t n_prog, const CandRec *__restrict__ rec, const uint8_t *__restrict__ masks,
-                               uint32_t *__restrict__ programs, int wide, int np, int fold_modpos) {
+                               uint32_t *__restrict__ programs, int wide, int np, int fold_modpos, int classes, uint32_t c_slots) {
+    // classes: write the class layout of the CLS variants (nmscan_device.h; wide, np and fold_modpos do not apply);
+    // c_slots: bit s = mod slot s has canonical base C (a class program carries its base)
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < n_prog) compile_one(k, rec, masks, programs, wide, np, fold_modpos);
+    if (k >= n_prog) return;
+    if (classes) compile_one_classes(k, rec, masks, programs, c_slots);
+    else compile_one(k, rec, masks, programs, wide, np, fold_modpos);
 }
 
 __global__ void common_kernel(uint32_t n_entries, uint4 *__restrict__ range, uint32_t *__restrict__ programs, uint32_t pdw,
@@ -793,6 +460,7 @@ struct LaunchShape {
     bool compact, lit, light;
     uint32_t n_active;
     bool per_contig = false;
+    bool classes = false;     // narrow compact non-literal heavy batch: the class-plane variants and their program layout
 };
 
 template <class K>
@@ -812,6 +480,7 @@ void launch_score(const ScoreArgs &a, uint32_t gx, const LaunchShape &sh, hipStr
         const uint32_t gy = std::max(sh.n_active, 1u);
         if (sh.wide == 2 && sh.compact) launch_variant<Variant<3, 3, true, 1, false, false, true>>(a, gx, gy, s);
         else if (sh.wide == 2) launch_variant<Variant<3, 3, false, 1, false, false, true>>(a, gx, gy, s);
+        else if (!sh.wide && sh.compact && sh.classes) launch_score_classes(a, gx, gy, true, s);
         else if (!sh.wide && sh.compact) launch_variant<Variant<1, 1, true, 1, false, false, true>>(a, gx, gy, s);
         else if (!sh.wide) launch_variant<Variant<1, 1, false, 1, false, false, true>>(a, gx, gy, s);
         else if (sh.compact) launch_variant<Variant<2, 2, true, 1, false, false, true>>(a, gx, gy, s);
@@ -822,7 +491,8 @@ void launch_score(const ScoreArgs &a, uint32_t gx, const LaunchShape &sh, hipStr
         if (sh.compact) launch_by_load<3, true, false>(a, gx, sh, s);
         else launch_by_load<3, false, false>(a, gx, sh, s);
     } else if (!sh.wide && sh.compact) {
-        if (sh.lit) launch_by_load<1, true, true>(a, gx, sh, s);
+        if (sh.classes) launch_score_classes(a, gx, std::max(sh.n_active, 1u), false, s);
+        else if (sh.lit) launch_by_load<1, true, true>(a, gx, sh, s);
         else launch_by_load<1, true, false>(a, gx, sh, s);
     } else if (!sh.wide) launch_by_load<1, false, false>(a, gx, sh, s);
     else if (sh.compact) launch_by_load<2, true, false>(a, gx, sh, s);
@@ -1013,6 +683,15 @@ int score_impl(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, const uint8
     // measured crossover (profiles/): up to ~6 candidates per (slot, bin) group the launch is HBM-bound
     const bool light = (uint64_t)n_prog <= 6ull * n_groups && !per_contig;
     const bool cf = light && !c->opt_no_cf;
+    // IUPAC classes: exactly the batches that launch Variant<1, 1, true, 1, false, false, PC> take the class-plane twin of
+    // that variant and the class program layout (the same 32 dwords per program).  NM_SCORE_CLASSES=0, read at every call,
+    // keeps them on the 8-plane path (same-process A/B, tests/test_gpu_iupac_classes.py).
+    const char *cls_env = getenv("NM_SCORE_CLASSES");
+    const bool classes = !spec && !lit && !any_wide && all_compact && !cf && !(cls_env && atoi(cls_env) == 0);
+    static_assert(nmdetail::CLS_PROG_DW == 32, "a class program takes the room of a narrow 8-plane one");
+    static_assert(NM_MAX_MOD_SLOTS <= 32, "one bit per mod slot");
+    uint32_t c_slots = 0;
+    for (int sl = 0; sl < NM_MAX_MOD_SLOTS; ++sl) c_slots |= (c->slots[sl].canonical == 'C' ? 1u : 0u) << sl;
     // device-side program buffer: one part per staging pair, so that compiling the next batches (on the copy stream)
     // overlaps the scoring kernel of batch k; reuse of a part is gated like its staging pair (ensure_stage).  A light
     // batch appends one common program per (slot, bin) entry.
@@ -1093,7 +772,7 @@ int score_impl(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, const uint8
         } else {
             hipLaunchKernelGGL(compile_kernel, dim3((n_prog + 255) / 256), dim3(256), 0, pst, n_prog,
                                reinterpret_cast<const CandRec *>(ds), ds + off_masks, d_prog, any_wide, (int)np,
-                               all_compact ? 1 : 0);
+                               all_compact ? 1 : 0, classes ? 1 : 0, c_slots);
             HIP_TRY(hipGetLastError());
             if (cf) {
                 hipLaunchKernelGGL(common_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, pst, n_entries,
@@ -1156,7 +835,7 @@ int score_impl(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, const uint8
     if (a.fine_log2 == 0) tail_pieces = 0;
     a.j_big = a.pieces_per_run - tail_pieces;
     const uint32_t gx = (a.j_big + (tail_pieces << a.fine_log2)) * runs;
-    const LaunchShape shape{any_wide, all_compact, lit, light && !c->opt_no_cf, n_active, per_contig};
+    const LaunchShape shape{any_wide, all_compact, lit, light && !c->opt_no_cf, n_active, per_contig, classes};
     const bool fuse = n_active == 2 && shape.light && lit;
 
     if (timed_launch && !spec) HIP_TRY(hipEventRecord(e0, sst));

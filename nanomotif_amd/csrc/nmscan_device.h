@@ -34,10 +34,14 @@ typedef const uint8_t __attribute__((address_space(4))) *cu8p;
 #define NM_LIT_WAVES 4      // minimum waves per SIMD the literal-only variants are compiled for
 #endif
 
-template <int GN_, int GP_, bool COMPACT_, int NS_, bool LIT_, bool CF_, bool PC_ = false>
+// CLS (narrow, compact, non-literal heavy batches only): every IUPAC set is ONE constraint on the class planes
+// (ClassTile / ClassWalk below); the program is the 32-dword class layout, of which PDW and NP say nothing.
+template <int GN_, int GP_, bool COMPACT_, int NS_, bool LIT_, bool CF_, bool PC_ = false, bool CLS_ = false>
 struct Variant {
     static constexpr int GN = GN_, GP = GP_, NS = NS_;
     static constexpr bool COMPACT = COMPACT_, LIT = LIT_, CF = CF_, PC = PC_;   // PC: counters keyed by (candidate, contig)
+    static constexpr bool CLS = CLS_;
+    static_assert(!CLS || (GN == 1 && GP == 1 && COMPACT && NS == 1 && !LIT && !CF), "class planes: narrow compact heavy variants only");
     static constexpr int NW = T_WORDS + GN + GP;
     static constexpr int NP = LIT ? 4 : 8;                 // planes per tile
     static constexpr int NST = COMPACT ? 2 : 4;            // state planes per slot
@@ -80,7 +84,7 @@ struct RawChunk {
             for (int j = 0; j < GN; ++j) v[j] = seq.V[base - GN + j];
 #pragma unroll
             for (int j = 0; j < GP; ++j) v[GN + T_WORDS + j] = seq.V[base + T_WORDS + j];
-        } else {
+        } else if constexpr (!K::CLS) {                    // (a CLS variant never looks at V in an all-valid chunk)
 #pragma unroll
             for (int j = 0; j < K::NW; ++j) v[j] = 0xFFFFFFFFu;
         }
@@ -177,6 +181,128 @@ struct JointWalk {
                 and_in<I>(tile, r);
             }
             walk<I + 1>(m, tile, bf, br);
+        }
+    }
+};
+
+// ---- IUPAC classes: every set of 1, 2 or 3 bases as ONE constraint (score_candidates, the CLS variants) ---------------
+// On the stored 2-bit code (A = 00, C = 01, G = 11, T = 10 as H, L) every 2-set is a bit function of H, L and
+// X = H ^ L — [GT] = H, [AC] = ~H, [CG] = L, [AT] = ~L, [CT] = X, [AG] = ~X — and every 3-set is the complement of a
+// literal plane.  A constraint is a plane and a sense: positive (acc &= plane) or negative (acc &= ~plane).
+// Class word p of a word-group (bit r = shift r, as everywhere):
+//     0..3   A+ C+ G+ T+                  the literals
+//     4..7   A- C- G- T-                  the 3-sets [CGT] [AGT] [ACT] [ACG]
+//     8, 9   H+ H-    10, 11   L+ L-    12, 13   X+ X-
+// The reverse strand takes the complemented set: A <-> T, C <-> G, and complementing flips H (so H+ <-> H-, X+ <-> X-)
+// and leaves L alone.  One program is CLS_PROG_DW dwords, forward half only:
+//     [0..7] literal words of word-groups 0, 1   [8] summary   [9..28] words 4..13 of word-groups 0, 1   [29] base mask   [30..31] zero
+// summary: bit 10 g + (p - 4) is set iff word p >= 4 of word-group g is not empty.  The walk fetches a program as two
+// s_load_dwordx16: the first holds everything a candidate of literals needs (and the first seven class words).
+// base mask: all ones when the candidate's canonical base is C, zero when it is A.  The walk starts from
+// (mask & is-C) | (~mask & is-A) at the modified position (reverse: is-G / is-T): one v_bfi_b32 with a scalar operand per
+// accumulator word where the 8-plane walk has a v_mov_b32, no scalar instruction, one body for both mod types and no
+// start words held in registers (a body per base ends in scratch: four bodies share and copy tile words).
+constexpr int CLS_PROG_DW = 32, CLS_SUMMARY_DW = 8, CLS_WORDS_DW = 9, CLS_BASE_DW = 29;
+constexpr int cls_plane(int p) { return p < 4 ? p : p < 8 ? p - 4 : 4 + (p - 8) / 2; }         // planes of ClassTile
+constexpr bool cls_neg(int p) { return p >= 4 && (p < 8 || ((p - 8) & 1)); }
+constexpr int cls_mirror(int p) { return p < 4 ? 3 - p : p < 8 ? 11 - p : (p == 10 || p == 11) ? p : (p ^ 1); }
+constexpr int cls_dword(int g, int p) { return p < 4 ? 4 * g + p : CLS_WORDS_DW + 10 * g + (p - 4); }
+// class word of a base set (bit 0..3 = A C G T) of one, two or three bases
+constexpr int cls_word_of_set(uint32_t set) {
+    return set == 1 ? 0 : set == 2 ? 1 : set == 4 ? 2 : set == 8 ? 3 :
+           set == 14 ? 4 : set == 13 ? 5 : set == 11 ? 6 : set == 7 ? 7 :
+           set == 12 ? 8 : set == 3 ? 9 : set == 6 ? 10 : set == 9 ? 11 : set == 10 ? 12 : 13 /* set == 5 */;
+}
+
+// Planes is-A / C / G / T, H, L, X (and V when BV).  pack_kernel writes H and L as zero at invalid positions, so C, G,
+// T, H, L and X are zero there on their own; is-A (~H & ~L) is masked with V.
+// BV = false: an all-valid chunk (needs_v == 0: the chunk and the halo are valid) — no V anywhere, a negative
+// constraint is acc & ~shift(P).  BV = true: a boundary chunk — a negative constraint is acc & ~shift(P) & shift(V):
+// nothing but V keeps an invalid position out of a negative class.  There V takes X's place in the tile and an X
+// constraint shifts H and L (shift(X) = shift(H) ^ shift(L)): with V as an eighth plane the body needs 48 plane words
+// plus eight temporaries per negative constraint — 91 VGPRs, or 80 and scratch.  A boundary chunk is a contig's first
+// or last one, and one constraint in six is on X.
+template <class K, bool BV>
+struct ClassTile {
+    static constexpr bool HAS_V = BV;
+    static constexpr int VP = 6;                           // (BV) where V sits
+    uint32_t w[7][K::NW];
+
+    __device__ __forceinline__ void expand(const RawChunk<K> &r) {
+#pragma unroll
+        for (int j = 0; j < K::NW; ++j) {
+            const uint32_t hh = r.h[j], ll = r.l[j];
+            w[0][j] = BV ? r.v[j] & ~(hh | ll) : ~(hh | ll);
+            w[1][j] = ll & ~hh;
+            w[2][j] = hh & ll;
+            w[3][j] = hh & ~ll;
+            w[4][j] = hh;
+            w[5][j] = ll;
+            w[6][j] = BV ? r.v[j] : hh ^ ll;
+        }
+    }
+};
+
+// JointWalk over a class program: one scalar walk drives both strands, the reverse twin of class word p is word
+// cls_mirror(p) at word-group 2 GN - 1 - g, shift 32 - r (r = 0: word-group 2 GN - g, unshifted).  The class words are
+// looked at only behind the summary: not at all for a candidate of literals, in groups of four otherwise.
+template <class K, class TileT>
+struct ClassWalk {
+    uint32_t accf[T_WORDS], accr[T_WORDS];
+
+    template <int G, int P>
+    __device__ __forceinline__ void and_one(const TileT &tile, uint32_t (&acc)[T_WORDS], uint32_t r) {
+        constexpr int PL = cls_plane(P);
+#pragma unroll
+        for (int t = 0; t < T_WORDS; ++t) {
+            uint32_t s;
+            if constexpr (TileT::HAS_V && PL == 6) s = alignbit(tile.w[4][t + G + 1], tile.w[4][t + G], r) ^ alignbit(tile.w[5][t + G + 1], tile.w[5][t + G], r);
+            else s = alignbit(tile.w[PL][t + G + 1], tile.w[PL][t + G], r);
+            if constexpr (!cls_neg(P)) acc[t] &= s;
+            else if constexpr (!TileT::HAS_V) acc[t] &= ~s;
+            else acc[t] = acc[t] & ~s & alignbit(tile.w[TileT::VP][t + G + 1], tile.w[TileT::VP][t + G], r);
+        }
+    }
+    template <int G, int P, bool R0 = false>
+    __device__ __forceinline__ void and_in(const TileT &tile, uint32_t r) {
+        constexpr int GR = R0 ? 2 * K::GN - G : 2 * K::GN - 1 - G;
+        and_one<G, P>(tile, accf, r);
+        and_one<GR, cls_mirror(P)>(tile, accr, R0 ? 0u : 32u - r);
+    }
+    template <int G, int P>
+    __device__ __forceinline__ void word(uint32_t mm, const TileT &tile) {
+        if (JointWalk<K>::template r0_possible<G>() && (mm & 1u)) {     // wave-uniform
+            mm &= ~1u;
+            and_in<G, P, true>(tile, 0u);
+        }
+        while (mm) {                                                    // wave-uniform
+            const uint32_t r = __builtin_ctz(mm);
+            mm &= mm - 1;
+            and_in<G, P>(tile, r);
+        }
+    }
+    // the four class words behind summary bits 4 Q .. 4 Q + 3
+    template <int Q>
+    __device__ __forceinline__ void quad(const uint32_t (&m)[CLS_PROG_DW], const TileT &tile) {
+        if (m[CLS_SUMMARY_DW] & (0xFu << (4 * Q))) {                    // wave-uniform
+            word<(4 * Q + 0) / 10, 4 + (4 * Q + 0) % 10>(m[CLS_WORDS_DW + 4 * Q + 0], tile);
+            word<(4 * Q + 1) / 10, 4 + (4 * Q + 1) % 10>(m[CLS_WORDS_DW + 4 * Q + 1], tile);
+            word<(4 * Q + 2) / 10, 4 + (4 * Q + 2) % 10>(m[CLS_WORDS_DW + 4 * Q + 2], tile);
+            word<(4 * Q + 3) / 10, 4 + (4 * Q + 3) % 10>(m[CLS_WORDS_DW + 4 * Q + 3], tile);
+        }
+    }
+    __device__ __forceinline__ void walk(const uint32_t (&m)[CLS_PROG_DW], const TileT &tile, const uint32_t (&)[T_WORDS],
+                                         const uint32_t (&)[T_WORDS]) {
+        const uint32_t cm = m[CLS_BASE_DW];                             // wave-uniform
+#pragma unroll
+        for (int t = 0; t < T_WORDS; ++t) {
+            accf[t] = (cm & tile.w[1][t + K::GN]) | (~cm & tile.w[0][t + K::GN]);
+            accr[t] = (cm & tile.w[2][t + K::GN]) | (~cm & tile.w[3][t + K::GN]);
+        }
+        word<0, 0>(m[0], tile); word<0, 1>(m[1], tile); word<0, 2>(m[2], tile); word<0, 3>(m[3], tile);
+        word<1, 0>(m[4], tile); word<1, 1>(m[5], tile); word<1, 2>(m[6], tile); word<1, 3>(m[7], tile);
+        if (m[CLS_SUMMARY_DW]) {                                        // wave-uniform: 20 class words skipped at once
+            quad<0>(m, tile); quad<1>(m, tile); quad<2>(m, tile); quad<3>(m, tile); quad<4>(m, tile);
         }
     }
 };
@@ -278,6 +404,27 @@ __device__ __forceinline__ void compile_one(uint32_t k, const CandRec *__restric
     }
 }
 
+// The class layout (CLS variants: narrow, compact, so the modified position is folded and offsets lie in [-31, 31]): the
+// forward half only, one constraint per set of one, two or three bases, and the summary dword (layout: ClassWalk).
+__device__ __forceinline__ void compile_one_classes(uint32_t k, const CandRec *__restrict__ rec, const uint8_t *__restrict__ masks,
+                                                    uint32_t *__restrict__ programs, uint32_t c_slots) {
+    uint32_t *prog = programs + (size_t)k * CLS_PROG_DW;
+    for (int i = 0; i < CLS_PROG_DW; ++i) prog[i] = 0;
+    const CandRec c = rec[k];
+    const uint8_t *m = masks + c.mask_off;
+    prog[CLS_BASE_DW] = ((c_slots >> c.slot) & 1u) ? 0xFFFFFFFFu : 0u;      // c_slots: bit s = mod slot s has canonical base C
+    for (int j = 0; j < c.len; ++j) {
+        const uint32_t set = m[j] & 15u;
+        if (set == 15u || j == c.modpos) continue;
+        const int d = j - (int)c.modpos;
+        const int g = (d >> 5) + 1;
+        if (g < 0 || g > 1) continue;                   // (the host sends no such offset to a narrow variant)
+        const int p = cls_word_of_set(set);
+        prog[cls_dword(g, p)] |= 1u << ((uint32_t)d & 31u);
+        if (p >= 4) prog[CLS_SUMMARY_DW] |= 1u << (10 * g + p - 4);
+    }
+}
+
 // Light batches (a round of the greedy search): the constraints shared by ALL candidates of a (slot, bin) group — the
 // parent of sibling children (find_motifs_bin.py:1116-1135), the motif under its parents in a pruning round
 // (:1408-1432) — become the group's COMMON program (index n_prog + group), evaluated once per tile; the candidates keep
@@ -334,3 +481,412 @@ __device__ __forceinline__ void common_one(uint32_t g, uint4 *__restrict__ range
 
 
 }  // namespace nmdetail
+
+// ---- the scoring kernel ------------------------------------------------------------------------------------------------
+// score_kernel and what it is made of, for the two translation units that instantiate it (they define
+// NM_SCORE_KERNEL_SOURCE before including this header): nmscan.hip — every variant but the class-plane ones — and
+// nmscore_classes.hip, which is nothing but this header with NM_SCORE_CLASSES_UNIT defined and exists because of one
+// compiler flag.  The flag is declared HERE, in the line below that build.py reads, so that the kernel's source and what
+// decides its register count stay in one file:
+//
+// NM_UNIT_FLAGS nmscore_classes.hip: -fno-slp-vectorize
+//
+// The SLP vectorizer pairs the eight accumulator words of the class walk and, through them, the words of the tile into
+// <2 x i32> values; those want aligned register pairs, the halo words get copied into place (v_pk_mov_b32, v_mov_b32), and
+// the class variants end at 86 - 94 VGPRs (5 waves per SIMD), or at 80 with scratch when held to 6 waves.  Without that
+// pass: 80 VGPRs, no scratch, 6 waves, no copy of a plane word.  The pass cannot be switched off per function.  Every other
+// variant keeps the flags and the code it had.
+#ifdef NM_SCORE_KERNEL_SOURCE
+
+namespace nmdetail {
+
+struct ScoreArgs {
+    Planes seq;
+    StatePlanes st[NM_MAX_MOD_SLOTS];
+    const uint4 *segments;      // {first chunk, n chunks, bin, 0}
+    uint32_t n_segments;
+    uint32_t split_log2;        // every segment is cut into 1 << split_log2 pieces
+    uint32_t pieces_per_run, j_big, fine_log2;   // per run of pieces: the first j_big go whole, the rest in 1 << fine_log2 parts
+    uint32_t n_bins;
+    const uint4 *cand_range;    // [active_slot_index][bin] -> {begin, count, common program or ~0, -} into programs
+    const uint32_t *programs;   // [n_prog][2 * (GN + GP) * NP], sorted by (slot, bin); CLS variants: [n_prog][CLS_PROG_DW], the class layout
+    const uint32_t *orig_index; // [n_cand] sorted -> caller order
+    unsigned long long *out;    // [n_cand][2]; per-contig mode: [rows][2], row = row_base[candidate] + rank of the contig in its bin
+    const uint32_t *chunk_rank; // per chunk: rank of its contig within its bin (per-contig mode)
+    const uint64_t *row_base;   // [n_prog] sorted order (per-contig mode)
+    uint32_t active_slot[NM_MAX_MOD_SLOTS];
+    uint32_t slot_is_c[NM_MAX_MOD_SLOTS];   // canonical base of the slot is C (else A)
+};
+
+// the CLS variants (Variant<1, 1, true, 1, false, false, PC, true>): instantiated by nmscore_classes.hip
+void launch_score_classes(const ScoreArgs &a, uint32_t gx, uint32_t gy, bool per_contig, hipStream_t s);
+
+}  // namespace nmdetail
+
+namespace {      // (a kernel has internal linkage in the translation unit that instantiates it)
+
+using namespace nmdetail;
+
+// acc = base & (the ONE constraint `desc` = (mask index << 5) | r of a strand): the residual of a sibling child once the
+// parent's constraints are in `base`.  The mask index selects registers, so it is dispatched through a switch.
+template <class K, int I = 0>
+__device__ __forceinline__ void apply_single(uint32_t idx, uint32_t r, const Tile<K> &tile, const uint32_t (&base)[T_WORDS],
+                                             uint32_t (&acc)[T_WORDS]) {
+    if constexpr (I < K::PDW) {
+        if (idx == I) {
+            constexpr int g = I / K::NP, p = I % K::NP;
+#pragma unroll
+            for (int t = 0; t < T_WORDS; ++t) acc[t] = base[t] & alignbit(tile.w[p][t + g + 1], tile.w[p][t + g], r);
+        } else {
+            apply_single<K, I + 1>(idx, r, tile, base, acc);
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < T_WORDS; ++t) acc[t] = base[t];      // idx == PDW: no constraint left on this strand
+    }
+}
+
+// Candidate k's two counters of this wave: one (candidate, contig) row of the count table (PC), or the lane's LDS slots.
+template <class K>
+__device__ __forceinline__ void emit_counts(const ScoreArgs &a, uint32_t n_mod, uint32_t n_non, uint32_t k0, uint32_t k,
+                                            uint32_t *lds_acc, uint32_t lds_row0, int lane, uint32_t contig_rank) {
+    if (K::PC) {
+        // per-contig counters (motif_model_contig per contig, find_motifs_bin.py:1285-1331): a chunk lies inside ONE
+        // contig, so the wave's sum goes straight to that (candidate, contig) row
+#pragma unroll
+        for (int o = 32; o; o >>= 1) {
+            n_mod += __shfl_xor(n_mod, o);
+            n_non += __shfl_xor(n_non, o);
+        }
+        if (lane == 0 && (n_mod | n_non)) {
+            unsigned long long *row = a.out + (a.row_base[k0 + k] + contig_rank) * 2;
+            if (n_mod) atomicAdd(row, (unsigned long long)n_mod);
+            if (n_non) atomicAdd(row + 1, (unsigned long long)n_non);
+        }
+        return;
+    }
+    atomicAdd(&lds_acc[((k * K::NS + lds_row0) * 2 + 0) * 64 + lane], n_mod);
+    atomicAdd(&lds_acc[((k * K::NS + lds_row0) * 2 + 1) * 64 + lane], n_non);
+}
+
+// Heavy batches (the non-CF variants): both strands of a candidate from its forward masks (JointWalk, nmscan_device.h), one
+// s_load_dwordx16 per candidate.
+template <class K, int CAN, class TileT>
+__device__ __forceinline__ void score_heavy(const ScoreArgs &a, const TileT &tile, const uint32_t (&sw)[K::NST][T_WORDS],
+                                            uint32_t k0, uint32_t nb, uint32_t *lds_acc, uint32_t lds_row0, int lane,
+                                            uint32_t contig_rank) {
+    constexpr int PF = CAN == 0 ? 0 : 1;   // plane of the canonical base: A or C
+    constexpr int PR = CAN == 0 ? 3 : 2;   // plane of its complement:     T or G
+    uint32_t basef[T_WORDS], baser[T_WORDS];
+#pragma unroll
+    for (int t = 0; t < T_WORDS; ++t) {
+        // compact batches: the canonical literal at the modified position is left out of the program, the plane is the
+        // walk's base
+        basef[t] = K::COMPACT ? tile.w[PF][t + K::GN] : 0xFFFFFFFFu;
+        baser[t] = K::COMPACT ? tile.w[PR][t + K::GN] : 0xFFFFFFFFu;
+    }
+    // CLS: the class program (forward half, 32 dwords: two s_load_dwordx16) and its walk over the class planes
+    constexpr int MDW = K::CLS ? CLS_PROG_DW : K::PDW;
+    static_assert(!K::CLS || CLS_PROG_DW == 2 * K::PDW, "a class program takes the room of both halves of a plain one");
+    std::conditional_t<K::CLS, ClassWalk<K, TileT>, JointWalk<K>> jw;
+    for (uint32_t k = 0; k < nb; ++k) {
+        cu32p prog = (cu32p)(a.programs + (size_t)(k0 + k) * (2 * K::PDW));
+        uint32_t m[MDW];
+        if constexpr (K::CLS) {            // two loads of 16 dwords each, whatever the walk looks at first
+            typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+            typedef const u32x16 __attribute__((address_space(4))) *cu32x16p;
+            const u32x16 lo = ((cu32x16p)prog)[0], hi = ((cu32x16p)prog)[1];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) { m[i] = lo[i]; m[16 + i] = hi[i]; }
+        } else {
+#pragma unroll
+            for (int i = 0; i < MDW; ++i) m[i] = prog[i];
+        }
+        jw.walk(m, tile, basef, baser);
+        uint32_t n_mod = 0, n_non = 0;
+#pragma unroll
+        for (int t = 0; t < T_WORDS; ++t) {
+            if (K::COMPACT) {
+                const uint32_t sites = jw.accf[t] | jw.accr[t];  // forward sites sit on the canonical base, reverse on its complement
+                n_mod += __popc(sites & sw[0][t]);
+                n_non += __popc(sites & sw[1][t]);
+            } else {
+                n_mod += __popc(jw.accf[t] & sw[0][t]) + __popc(jw.accr[t] & sw[K::COMPACT ? 0 : 2][t]);
+                n_non += __popc(jw.accf[t] & sw[1][t]) + __popc(jw.accr[t] & sw[K::COMPACT ? 1 : 3][t]);
+            }
+        }
+        emit_counts<K>(a, n_mod, n_non, k0, k, lds_acc, lds_row0, lane, contig_rank);
+    }
+}
+
+// One slot's candidates [k0, k0 + nb) against the tile this wave holds: match masks, site counts, per-lane counts into
+// LDS rows k * NS + lds_row0 (lds_row0 = the slot's index in the workgroup).  CAN: canonical base of the slot, 0 = A (reverse-strand sites sit on T), 1 = C (reverse on G).
+// common != ~0u: program index of the constraints shared by all nb candidates (their own programs hold the rest).
+template <class K, int CAN, class TileT>
+__device__ __forceinline__ void score_candidates(const ScoreArgs &a, const TileT &tile, const uint32_t (&sw)[K::NST][T_WORDS],
+                                                 uint32_t k0, uint32_t nb, uint32_t common, bool siblings, uint32_t *lds_acc,
+                                                 uint32_t lds_row0, int lane, uint32_t contig_rank = 0) {
+    if constexpr (!K::CF) {
+        score_heavy<K, CAN>(a, tile, sw, k0, nb, lds_acc, lds_row0, lane, contig_rank);
+        return;
+    } else {
+    constexpr int PF = CAN == 0 ? 0 : 1;   // plane of the canonical base: A or C
+    constexpr int PR = CAN == 0 ? 3 : 2;   // plane of its complement:     T or G
+    uint32_t basef[T_WORDS], baser[T_WORDS];
+#pragma unroll
+    for (int t = 0; t < T_WORDS; ++t) {
+        // compact batches: every candidate has the canonical literal at its modified position, the compiler leaves
+        // that constraint out of the program and it becomes the accumulator's initial value
+        basef[t] = K::COMPACT ? tile.w[PF][t + K::GN] : 0xFFFFFFFFu;
+        baser[t] = K::COMPACT ? tile.w[PR][t + K::GN] : 0xFFFFFFFFu;
+    }
+    if (common != 0xFFFFFFFFu) {                                             // wave-uniform
+        cu32p prog = (cu32p)(a.programs + (size_t)common * (2 * K::PDW));
+        eval_strand<K>(prog, tile, basef);
+        eval_strand<K>(prog + K::PDW, tile, baser);
+    }
+    // Scalar loads of the masks are software-pipelined at strand granularity: the reverse masks of candidate k are
+    // requested before its forward strand is evaluated, the forward masks of candidate k + 1 before its reverse strand —
+    // two sets of SGPRs like before, but a load's latency hides behind ~40 vector instructions instead of standing in
+    // front of every strand.
+    uint32_t mf[K::PDW], mr[K::PDW];
+    if (!siblings) {
+        cu32p prog = (cu32p)(a.programs + (size_t)k0 * (2 * K::PDW));
+#pragma unroll
+        for (int i = 0; i < K::PDW; ++i) mf[i] = prog[i];
+    }
+    for (uint32_t k = 0; k < nb; ++k) {
+        cu32p prog = (cu32p)(a.programs + (size_t)(k0 + k) * (2 * K::PDW));
+        uint32_t accf[T_WORDS], accr[T_WORDS];
+        if (siblings) {                                                      // wave-uniform: one constraint per strand left
+            const uint32_t df = prog[0], dr = prog[1];
+            apply_single<K>(df >> 5, df & 31u, tile, basef, accf);
+            apply_single<K>(dr >> 5, dr & 31u, tile, baser, accr);
+        } else {
+#pragma unroll
+            for (int i = 0; i < K::PDW; ++i) mr[i] = prog[K::PDW + i];
+#pragma unroll
+            for (int t = 0; t < T_WORDS; ++t) accf[t] = basef[t];
+            eval_masks<K>(mf, tile, accf);
+            cu32p next = (cu32p)(a.programs + (size_t)(k0 + min(k + 1, nb - 1)) * (2 * K::PDW));
+#pragma unroll
+            for (int i = 0; i < K::PDW; ++i) mf[i] = next[i];
+#pragma unroll
+            for (int t = 0; t < T_WORDS; ++t) accr[t] = baser[t];
+            eval_masks<K>(mr, tile, accr);
+        }
+        uint32_t n_mod = 0, n_non = 0;
+#pragma unroll
+        for (int t = 0; t < T_WORDS; ++t) {
+            if (K::COMPACT) {
+                const uint32_t sites = accf[t] | accr[t];       // forward sites sit on the canonical base, reverse on its complement
+                n_mod += __popc(sites & sw[0][t]);
+                n_non += __popc(sites & sw[1][t]);
+            } else {
+                n_mod += __popc(accf[t] & sw[0][t]) + __popc(accr[t] & sw[K::COMPACT ? 0 : 2][t]);
+                n_non += __popc(accf[t] & sw[1][t]) + __popc(accr[t] & sw[K::COMPACT ? 1 : 3][t]);
+            }
+        }
+        emit_counts<K>(a, n_mod, n_non, k0, k, lds_acc, lds_row0, lane, contig_rank);
+    }
+    }
+}
+
+template <class T>
+struct TileTag { using type = T; };
+
+// With NS > 1 a tile's sequence planes are loaded and expanded once and serve the candidates of all NS slots (each slot
+// brings its own state planes); with NS = 1 the slot comes from blockIdx.y.  A pass handles up to BMAX / NS candidates
+// per slot; LDS rows are [candidate k][slot j].
+// One PIECE of work: the chunks [sg.x, sg.x + sg.y) of bin sg.z, all candidates of the workgroup's slot column(s), counters
+// accumulated in LDS and flushed to the count table at the end.  Called once per workgroup by score_kernel (piece = a
+// segment or a part of one).
+template <class K>
+__device__ __forceinline__ void score_piece(const ScoreArgs &a, const uint4 sg, const StatePlanes (&stp)[K::NS], const bool (&is_c)[K::NS],
+                                            uint32_t *lds_acc, const int lane, const uint32_t wave) {
+    constexpr int NS = K::NS;
+    constexpr uint32_t H = BMAX / NS;
+    // the wave's first chunk is requested before anything else of the segment is looked at (candidate ranges, LDS
+    // clearing, the barrier): a workgroup lives for four chunks per wave, its start-up chain would otherwise sit
+    // in front of every fourth memory round trip
+    constexpr bool EARLY = K::CF && K::LIT;          // (the 8-plane light tiles would drop from 5 to 4 waves per SIMD)
+    RawChunk<K> first;
+    if (EARLY && wave < sg.y) first.load(a.seq, stp, sg.x + wave, lane);
+    uint4 range[NS];                                // {first program, candidates, common program or ~0, siblings}
+    uint32_t most = 0;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        const uint32_t slot_i = NS == 1 ? blockIdx.y : (uint32_t)j;
+        range[j] = a.cand_range[(size_t)slot_i * a.n_bins + sg.z];
+        range[j].x = __builtin_amdgcn_readfirstlane(range[j].x);
+        range[j].y = __builtin_amdgcn_readfirstlane(range[j].y);
+        range[j].z = __builtin_amdgcn_readfirstlane(range[j].z);
+        range[j].w = __builtin_amdgcn_readfirstlane(range[j].w);
+        most = max(most, range[j].y);
+    }
+    if (most == 0) return;
+
+    // one chunk of one pass: tile, then every slot's candidates of this pass
+    auto score_tile = [&](auto tile_tag, const RawChunk<K> &cur, uint32_t pass0, uint32_t chunk) {
+        typename decltype(tile_tag)::type tile;
+        tile.expand(cur);
+        const uint32_t rank = K::PC ? ((cu32p)a.chunk_rank)[chunk] : 0u;
+        // one slot at a time with the slot index a compile-time constant: left to `#pragma unroll`, the optimizer gave up on
+        // the NS = 2 non-literal bodies ("loop not unrolled") and indexed cur.s[j] / range[j] / is_c[j] through private
+        // memory — 192-288 bytes of scratch per lane in five variants (round-3 review)
+        auto one_slot = [&](auto jc) {
+            constexpr int j = decltype(jc)::value;
+            if (range[j].y <= pass0) return;                         // wave-uniform
+            const uint32_t nbj = min(H, range[j].y - pass0);
+            if constexpr (K::CLS)          // (one body: a class program carries its canonical base as a mask)
+                score_candidates<K, 0>(a, tile, cur.s[j], range[j].x + pass0, nbj, range[j].z, range[j].w != 0, lds_acc, j, lane, rank);
+            else if (K::COMPACT && is_c[j])
+                score_candidates<K, 1>(a, tile, cur.s[j], range[j].x + pass0, nbj, range[j].z, range[j].w != 0, lds_acc, j, lane, rank);
+            else
+                score_candidates<K, 0>(a, tile, cur.s[j], range[j].x + pass0, nbj, range[j].z, range[j].w != 0, lds_acc, j, lane, rank);
+        };
+        one_slot(std::integral_constant<int, 0>{});
+        if constexpr (NS > 1) one_slot(std::integral_constant<int, 1>{});
+        static_assert(NS <= 2, "slot fusion is written for one or two slots");
+    };
+    // CLS: two bodies, chosen per chunk by the wave-uniform needs_v byte the load already read — the all-valid chunk
+    // never looks at V, the boundary chunk (a contig's first and last) holds V where the other holds X
+    auto score_chunk = [&](const RawChunk<K> &cur, uint32_t pass0, uint32_t chunk) {
+        if constexpr (K::CLS) {
+            if (cur.need_v) score_tile(TileTag<ClassTile<K, true>>{}, cur, pass0, chunk);
+            else score_tile(TileTag<ClassTile<K, false>>{}, cur, pass0, chunk);
+        } else {
+            score_tile(TileTag<Tile<K>>{}, cur, pass0, chunk);
+        }
+    };
+    auto clear_rows = [&](uint32_t rows_hi) {
+        if (K::PC) return;
+        for (uint32_t i = threadIdx.x; i < rows_hi * 128; i += 256) lds_acc[i] = 0;
+        __syncthreads();
+    };
+    // 4 threads per counter, 16 lane-slots each, then a 4-lane butterfly; one 64-bit atomic per counter
+    auto flush_rows = [&](uint32_t rows_hi, uint32_t pass0) {
+        if (K::PC) return;
+        __syncthreads();
+        for (uint32_t idx = threadIdx.x; idx < rows_hi * 8; idx += 256) {
+            const uint32_t i = idx >> 2, q = idx & 3;               // i = counter row: (k * NS + j) * 2 + which
+            const uint32_t j = (i >> 1) % NS, k = (i >> 1) / NS;
+            uint32_t s = 0;
+#pragma unroll 4
+            for (int jj = 0; jj < 16; ++jj) s += lds_acc[i * 64 + q * 16 + jj];
+            s += __shfl_xor(s, 1);
+            s += __shfl_xor(s, 2);
+            if (q == 0 && s) {
+                uint4 rj = range[0];
+#pragma unroll
+                for (int t = 1; t < NS; ++t)
+                    if (j == (uint32_t)t) rj = range[t];
+                if (pass0 + k < rj.y) {
+                    const uint32_t orig = a.orig_index[rj.x + pass0 + k];
+                    atomicAdd(a.out + (size_t)orig * 2 + (i & 1), (unsigned long long)s);
+                }
+            }
+        }
+        __syncthreads();
+    };
+    // LDS rows in use in a pass: row = k * NS + j for candidate k of slot j
+    uint32_t pass0 = 0;
+    if (EARLY) {                                                     // pass 0 with the chunk already under way
+        const uint32_t rows_hi = NS * min(H, most);
+        clear_rows(rows_hi);
+        if (wave < sg.y) score_chunk(first, 0, sg.x + wave);
+        for (uint32_t ck = wave + 4; ck < sg.y; ck += 4) {
+            RawChunk<K> cur;
+            cur.load(a.seq, stp, sg.x + ck, lane);
+            score_chunk(cur, 0, sg.x + ck);
+        }
+        flush_rows(rows_hi, 0);
+        pass0 = H;
+    }
+    for (; pass0 < most; pass0 += H) {
+        const uint32_t rows_hi = NS * min(H, most - pass0);
+        clear_rows(rows_hi);
+        for (uint32_t ck = wave; ck < sg.y; ck += 4) {
+            RawChunk<K> cur;
+            cur.load(a.seq, stp, sg.x + ck, lane);
+            score_chunk(cur, pass0, sg.x + ck);
+        }
+        flush_rows(rows_hi, pass0);
+    }
+}
+
+// (CLS: a negative constraint of the boundary-chunk body shifts two planes; asked for 6 waves the scheduler keeps its
+// temporaries inside the 80 VGPRs of the 8-plane variant, without scratch)
+#define NM_SCORE_BOUNDS __launch_bounds__(256, (K::GN + K::GP > 2 ? 2 : (K::LIT ? NM_LIT_WAVES : (K::CLS ? 6 : 4))))
+
+// per-slot facts are read from the kernel arguments once per workgroup
+#define NM_SLOT_SETUP                                                                                               \
+    const int lane = threadIdx.x & 63;                                                                              \
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); /* provably uniform: chunk indices stay scalar */ \
+    StatePlanes stp[K::NS];                                                                                         \
+    bool is_c[K::NS];                                                                                               \
+    _Pragma("unroll") for (int j = 0; j < K::NS; ++j) {                                                             \
+        const uint32_t slot = a.active_slot[K::NS == 1 ? blockIdx.y : (uint32_t)j];                                 \
+        stp[j] = a.st[slot];                                                                                        \
+        is_c[j] = a.slot_is_c[slot] != 0;                                                                           \
+    }
+
+template <class K>
+__global__ NM_SCORE_BOUNDS void score_kernel(ScoreArgs a) {
+    __shared__ uint32_t lds_acc[BMAX * 2 * 64];
+    // XCD-aware remap: blocks b and b+8 share an XCD (round-robin dispatch), give every XCD a contiguous run
+    // of segments so candidate programs and counters of one bin stay in one L2.
+    // (a light batch streams: there the remap costs 3 % of the read rate, tools/stream_pattern.hip)
+    const uint32_t lanes_x = K::CF ? 1u : 8u;                  // runs of pieces: one per XCD, or a single one
+    const uint32_t x = K::CF ? 0u : blockIdx.x % 8, j = K::CF ? blockIdx.x : blockIdx.x / 8;
+    // Pieces: a segment (16 chunks), or a half / quarter of one for assemblies that fill the device for less than two
+    // rounds of workgroups (split_log2).  The workgroups dispatched LAST (j >= j_big in every run) take pieces cut
+    // finer still (fine_log2): the last, partly filled round of workgroups then lasts a quarter as long.
+    uint32_t piece, sub = 0, n_sub = 1;
+    if (j < a.j_big) piece = x * a.pieces_per_run + j;
+    else {
+        const uint32_t k = j - a.j_big;
+        piece = x * a.pieces_per_run + a.j_big + (k >> a.fine_log2);
+        sub = k & ((1u << a.fine_log2) - 1);
+        n_sub = 1u << a.fine_log2;
+        if (a.j_big + (k >> a.fine_log2) >= a.pieces_per_run) return;
+    }
+    (void)lanes_x;
+    const uint32_t seg = piece >> a.split_log2;
+    if (seg >= a.n_segments) return;
+    uint4 sg = a.segments[seg];
+    sg.x = __builtin_amdgcn_readfirstlane(sg.x);   // everything below is wave-uniform: keep it in SGPRs
+    sg.y = __builtin_amdgcn_readfirstlane(sg.y);
+    sg.z = __builtin_amdgcn_readfirstlane(sg.z);
+    if (a.split_log2) {
+        const uint32_t len = (sg.y + (1u << a.split_log2) - 1) >> a.split_log2;
+        const uint32_t at = (piece & ((1u << a.split_log2) - 1)) * len;
+        if (at >= sg.y) return;
+        sg.x += at;
+        sg.y = min(len, sg.y - at);
+    }
+    if (n_sub > 1) {
+        const uint32_t len = (sg.y + n_sub - 1) / n_sub;
+        const uint32_t at = sub * len;
+        if (at >= sg.y) return;
+        sg.x += at;
+        sg.y = min(len, sg.y - at);
+    }
+    NM_SLOT_SETUP
+    score_piece<K>(a, sg, stp, is_c, lds_acc, lane, wave);
+}
+
+}  // namespace
+
+#ifdef NM_SCORE_CLASSES_UNIT
+namespace nmdetail {
+
+void launch_score_classes(const ScoreArgs &a, uint32_t gx, uint32_t gy, bool per_contig, hipStream_t s) {
+    if (per_contig) hipLaunchKernelGGL((score_kernel<Variant<1, 1, true, 1, false, false, true, true>>), dim3(gx, gy), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((score_kernel<Variant<1, 1, true, 1, false, false, false, true>>), dim3(gx, gy), dim3(256), 0, s, a);
+}
+
+}  // namespace nmdetail
+#endif  // NM_SCORE_CLASSES_UNIT
+
+#endif  // NM_SCORE_KERNEL_SOURCE
