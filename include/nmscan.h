@@ -549,6 +549,32 @@ int nm_motif_profile_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bi
                            const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t n_targets, const uint8_t *target_slot,
                            uint32_t radius, uint64_t *cand_sites, int64_t *counts);
 
+/* ---- SEQUENCE CONTEXT of a motif's sites by methylation state: the letter at every offset around the modified base ------------------
+ * Reference: none (the search of find_motifs_bin.py scores one expansion at a time and keeps nothing of it).  The exports above accept
+ * a motif as given; this call answers whether it is under-specified: which position and which letters around its sites separate the
+ * methylated occurrences from the unmethylated ones.
+ *
+ * A candidate is (bin, mod slot, stripped motif, mod_position) as for nm_motif_sites, and OCCURRENCES and STATES are nm_motif_sites':
+ * the stripped motif on '+', its reverse complement on '-', wholly inside the contig; an occurrence has its modified base at '+'
+ * coordinate p on occurrence strand s (0 '+', 1 '-') and is, in slot cand_mod_slot[k] on strand s at p, 0 mod (a position called both
+ * ways is mod), 1 nomod or 2 nocall (everything else, including a modified base the motif leaves open that is not the canonical
+ * letter).  For an offset o in the motif's reading direction, -radius <= o <= radius, the probe is the position q = p + o (s = 0) or
+ * p - o (s = 1); its LETTER is the contig's letter at q read on strand s (complemented for s = 1): 0 A, 1 C, 2 G, 3 T.  N, any other
+ * character and a position outside the contig have no letter and are not counted: = the state's occurrences - the four letters.
+ * cand_states = uint64[n_cand][2 (s)][3 (state)], the rows of nm_motif_sites_count summed over the contigs of the candidate's bin;
+ * counts = int64[n_cand][2 radius + 1][2 (s)][3 (state)][4 (letter)], offset o at index o + radius, summed over those contigs.
+ * The cell (o, X) is the cand_states of the candidate narrowed to X at o (where that motif is within the reach limit): one call scores
+ * every one-position refinement of every candidate.  Inside the motif a letter the motif excludes counts 0.
+ * Launches: at most 3 (one per reach width) whatever the batch and the radius.  NM_CONTEXT_WAVE_ATOMICS=1 in the environment (read
+ * per call) makes every wave add its counts to the table itself instead of through the workgroup's sum; the results are the same.
+ * NM_EINVAL for NULLs, radius > NM_CONTEXT_MAX_RADIUS and a bad bin — each checked before any device is touched, the message names the
+ * argument; NM_ESTATE without an assembly or for a slot without an uploaded pileup (per-strand planes); NM_ERANGE for a motif beyond
+ * NM_MAX_MOTIF_LEN / the reach limit and for more than 2^32 work items.  n_cand = 0 is NM_OK.  A refusal leaves the ctx usable. */
+#define NM_CONTEXT_MAX_RADIUS 31
+int nm_motif_context_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot, const uint8_t *cand_len,
+                           const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t radius,
+                           uint64_t *cand_states, int64_t *counts);
+
 /* ---- METHYLATION TRACKS: a motif's site counts per WINDOW along the contigs of its bin ------------------------------------------------
  * Reference: none (motif_model_contig, find_motifs_bin.py:1285-1331, sums over the contig).  The exports above give one row per contig
  * or per bin; this call keeps the counts apart by position: a chimeric contig is a step function, an island an unmethylated stretch,

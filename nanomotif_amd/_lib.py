@@ -26,6 +26,7 @@ SYMBOLS = [
     "nm_motif_compare_count", "nm_motif_compare_sites", "nm_motif_compare_text",
     "nm_motif_strands_count", "nm_motif_strands_sites", "nm_motif_strands_text",
     "nm_motif_profile_count",
+    "nm_motif_context_count",
     "nm_tracks_windows", "nm_motif_tracks_count",
     "nm_motif_fractions_count",
 ]
@@ -160,6 +161,7 @@ def _load_locked():
     lib.nm_motif_strands_text.argtypes = [C.c_uint64, u32p, u32p, u8p, C.c_uint32, u64p, C.c_char_p, u64p, i32p, C.c_uint32, C.c_char_p, u64p, p,
                                           C.c_uint64, u64p]
     lib.nm_motif_profile_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u32p, u8p, C.c_uint32, u8p, C.c_uint32, u64p, i64p]
+    lib.nm_motif_context_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, i64p]
     lib.nm_tracks_windows.argtypes = [p, C.c_uint32, C.c_uint32, u64p, C.c_uint32, u32p]
     lib.nm_motif_tracks_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, u32p]
     lib.nm_motif_fractions_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p]

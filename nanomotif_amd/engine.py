@@ -34,6 +34,8 @@ PAIRS = tuple(f"{a}-{b}" for a in SITE_STATES for b in SITE_STATES)            #
 HEMI = ("mod-nomod", "nomod-mod")              # NM_STRANDS_HEMI: the two hemimethylated pairs
 PROFILE_MAX_RADIUS = 31                        # NM_PROFILE_MAX_RADIUS: offsets a profile reaches either side of the modified base
 PROFILE_CLASSES = ("mod", "nomod", "nocall", "other")                           # the last axis of ScanEngine.motif_profile's table
+CONTEXT_MAX_RADIUS = 31                        # NM_CONTEXT_MAX_RADIUS: offsets a context table reaches either side of the modified base
+CONTEXT_LETTERS = ("A", "C", "G", "T", "other")                                 # the last axis of ScanEngine.motif_context's table
 TRACKS_MIN_WINDOW = 128                        # NM_TRACKS_MIN_WINDOW: one lane's span of a wave-chunk; a window is a multiple of it ...
 TRACKS_MAX_WINDOW = 1 << 30                    # ... up to NM_TRACKS_MAX_WINDOW
 TRACK_ROW_BYTES = 24                           # a row of ScanEngine.motif_tracks on the device: six uint32
@@ -1124,6 +1126,31 @@ class ScanEngine:
         table[..., :3] = three
         table[..., 3] = sites[:, None, None, :, None] - three.sum(axis=-1)
         return labels, sites, table
+
+    # ------------------------------------------------------------------ sequence context of a motif's sites (nm_motif_context_count)
+    def motif_context(self, candidates, radius=10):
+        """The contig's letter at every offset around the sites of ``candidates`` (sequence of (Motif, mod_type, bin), or a
+        CandidateBatch with slots from ``slot_of_mod``, as ``motif_site_counts`` takes them), counted apart by the state of the site
+        itself (nm_motif_context_count).  An occurrence has its modified base at p on occurrence strand s (0 '+', 1 '-') and the state
+        ``motif_site_counts`` gives it; offset o counts in the motif's reading direction: the probe is p + o for s = 0 and p - o for
+        s = 1, its letter the contig's read on strand s.  Returns (states int64[n, 2 (s), 3 (mod, nomod, nocall)], table int64[n,
+        2 radius + 1, 2 (s), 3 (state), 5 (A, C, G, T, other)]); ``other`` is N, any other character and a position outside the
+        contig; offset o is at index o + radius; every (offset, s, state) row sums to ``states[:, s, state]``.  The cell (o, X) is the
+        ``states`` of the candidate narrowed to X at o.  Counts are summed over the contigs of the candidate's bin."""
+        radius = int(radius)
+        if not 0 <= radius <= CONTEXT_MAX_RADIUS:
+            raise ValueError(f"radius {radius} outside 0..{CONTEXT_MAX_RADIUS}")
+        b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(list(candidates))
+        n, width = len(b), 2 * radius + 1
+        states = np.zeros((n, 2, 3), dtype=np.uint64)
+        four = np.zeros((n, width, 2, 3, 4), dtype=np.int64)
+        if n:
+            _lib.check(self.lib.nm_motif_context_count(self.ctx, *self._batch_args(b), radius, _ptr(states, C.c_uint64), _ptr(four, C.c_int64)))
+        states = states.astype(np.int64)
+        table = np.empty((n, width, 2, 3, 5), dtype=np.int64)
+        table[..., :4] = four
+        table[..., 4] = states[:, None, :, :] - four.sum(axis=-1)
+        return states, table
 
     # ------------------------------------------------------------------ methylation along contigs (nm_tracks_windows, nm_motif_tracks_count)
     def track_windows(self, bin, window) -> np.ndarray:
