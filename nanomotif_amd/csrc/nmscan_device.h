@@ -198,10 +198,13 @@ struct JointWalk {
 //     [0..7] literal words of word-groups 0, 1   [8] summary   [9..28] words 4..13 of word-groups 0, 1   [29] base mask   [30..31] zero
 // summary: bit 10 g + (p - 4) is set iff word p >= 4 of word-group g is not empty.  The walk fetches a program as two
 // s_load_dwordx16: the first holds everything a candidate of literals needs (and the first seven class words).
-// base mask: all ones when the candidate's canonical base is C, zero when it is A.  The walk starts from
-// (mask & is-C) | (~mask & is-A) at the modified position (reverse: is-G / is-T): one v_bfi_b32 with a scalar operand per
-// accumulator word where the 8-plane walk has a v_mov_b32, no scalar instruction, one body for both mod types and no
-// start words held in registers (a body per base ends in scratch: four bodies share and copy tile words).
+// Canonical first: all candidates of a workgroup belong to one mod slot, so their canonical base is known before the
+// first chunk arrives.  Flipping L swaps A <-> C and G <-> T and commutes with complementation (which flips H), so the
+// tile of a C slot is built from (H, ~L) and the tile of an A slot from (H, L): plane 0 is then the canonical base and
+// plane 3 its complement whatever the slot, the walk starts from those two planes with plain moves, and the compiler
+// (compile_one_classes) applies the same swap to every base set of a C-slot candidate.  One body for both mod types.
+// base mask: all ones when the candidate's canonical base is C, zero when it is A.  Written, but not read by the walk
+// (the flip comes from the slot, a scalar of the workgroup); a probe build can still read it.
 constexpr int CLS_PROG_DW = 32, CLS_SUMMARY_DW = 8, CLS_WORDS_DW = 9, CLS_BASE_DW = 29;
 constexpr int cls_plane(int p) { return p < 4 ? p : p < 8 ? p - 4 : 4 + (p - 8) / 2; }         // planes of ClassTile
 constexpr bool cls_neg(int p) { return p >= 4 && (p < 8 || ((p - 8) & 1)); }
@@ -213,9 +216,29 @@ constexpr int cls_word_of_set(uint32_t set) {
            set == 14 ? 4 : set == 13 ? 5 : set == 11 ? 6 : set == 7 ? 7 :
            set == 12 ? 8 : set == 3 ? 9 : set == 6 ? 10 : set == 9 ? 11 : set == 10 ? 12 : 13 /* set == 5 */;
 }
+// the base set of a C slot as its flipped tile sees it: A <-> C, G <-> T
+constexpr uint32_t cls_swap_set(uint32_t set) { return ((set & 5u) << 1) | ((set & 10u) >> 1); }
+// what the swap does to a class word: literals and 3-sets trade places pairwise, L+ <-> L-, X+ <-> X-, H stays
+constexpr int cls_swap_word(int p) { return p < 8 ? (p ^ 1) : p < 10 ? p : (p ^ 1); }
+constexpr uint32_t cls_comp_set(uint32_t set) { return ((set & 1u) << 3) | ((set & 2u) << 1) | ((set & 4u) >> 1) | ((set & 8u) >> 3); }
+constexpr bool cls_swap_ok() {
+    for (uint32_t set = 1; set < 15; ++set) {
+        const int p = cls_word_of_set(set), q = cls_word_of_set(cls_swap_set(set));
+        if (cls_swap_set(cls_swap_set(set)) != set) return false;
+        if (q != cls_swap_word(p)) return false;                                      // the expected word
+        if (cls_mirror(p) != cls_word_of_set(cls_comp_set(set))) return false;        // (the mirror is complementation)
+        if (cls_mirror(q) != cls_swap_word(cls_mirror(p))) return false;              // the swap commutes with it
+    }
+    return true;
+}
+static_assert(cls_swap_ok(), "A<->C, G<->T swap of a base set: class word and mirror, all 14 sets");
+static_assert(cls_word_of_set(cls_swap_set(2)) == 0 && cls_word_of_set(cls_swap_set(4)) == 3,
+              "a C slot's canonical base is plane 0 of its tile, the complement plane 3");
 
-// Planes is-A / C / G / T, H, L, X (and V when BV).  pack_kernel writes H and L as zero at invalid positions, so C, G,
-// T, H, L and X are zero there on their own; is-A (~H & ~L) is masked with V.
+// Planes is-A / C / G / T, H, L, X (and V when BV) of the code (H, L ^ cm); cm is the wave-uniform flip of the slot, all
+// ones for canonical base C, so for a C slot the planes read is-C / A / T / G, H, ~L, ~X.  pack_kernel writes H and L as
+// zero at invalid positions; in a boundary chunk the flipped L is masked with V before any plane is derived, so planes
+// 1..5 and X are zero there on their own as they are without the flip; plane 0 (~H & ~L) is masked with V.
 // BV = false: an all-valid chunk (needs_v == 0: the chunk and the halo are valid) — no V anywhere, a negative
 // constraint is acc & ~shift(P).  BV = true: a boundary chunk — a negative constraint is acc & ~shift(P) & shift(V):
 // nothing but V keeps an invalid position out of a negative class.  There V takes X's place in the tile and an X
@@ -228,10 +251,15 @@ struct ClassTile {
     static constexpr int VP = 6;                           // (BV) where V sits
     uint32_t w[7][K::NW];
 
-    __device__ __forceinline__ void expand(const RawChunk<K> &r) {
+    __device__ __forceinline__ void expand(const RawChunk<K> &r, const uint32_t cm) {
 #pragma unroll
         for (int j = 0; j < K::NW; ++j) {
-            const uint32_t hh = r.h[j], ll = r.l[j];
+            const uint32_t hh = r.h[j];
+            uint32_t ll = r.l[j] ^ cm;
+            // the flipped word is all the tile knows of L: left to fold the flip into the plane expressions, the compiler
+            // keeps the raw word beside the flipped one through the boundary body (six registers, and scratch at 80)
+            asm("" : "+v"(ll));
+            if (BV) ll &= r.v[j];
             w[0][j] = BV ? r.v[j] & ~(hh | ll) : ~(hh | ll);
             w[1][j] = ll & ~hh;
             w[2][j] = hh & ll;
@@ -293,11 +321,10 @@ struct ClassWalk {
     }
     __device__ __forceinline__ void walk(const uint32_t (&m)[CLS_PROG_DW], const TileT &tile, const uint32_t (&)[T_WORDS],
                                          const uint32_t (&)[T_WORDS]) {
-        const uint32_t cm = m[CLS_BASE_DW];                             // wave-uniform
 #pragma unroll
-        for (int t = 0; t < T_WORDS; ++t) {
-            accf[t] = (cm & tile.w[1][t + K::GN]) | (~cm & tile.w[0][t + K::GN]);
-            accr[t] = (cm & tile.w[2][t + K::GN]) | (~cm & tile.w[3][t + K::GN]);
+        for (int t = 0; t < T_WORDS; ++t) {                             // canonical first: plane 0 and its complement
+            accf[t] = tile.w[0][t + K::GN];
+            accr[t] = tile.w[3][t + K::GN];
         }
         word<0, 0>(m[0], tile); word<0, 1>(m[1], tile); word<0, 2>(m[2], tile); word<0, 3>(m[3], tile);
         word<1, 0>(m[4], tile); word<1, 1>(m[5], tile); word<1, 2>(m[6], tile); word<1, 3>(m[7], tile);
@@ -412,10 +439,12 @@ __device__ __forceinline__ void compile_one_classes(uint32_t k, const CandRec *_
     for (int i = 0; i < CLS_PROG_DW; ++i) prog[i] = 0;
     const CandRec c = rec[k];
     const uint8_t *m = masks + c.mask_off;
-    prog[CLS_BASE_DW] = ((c_slots >> c.slot) & 1u) ? 0xFFFFFFFFu : 0u;      // c_slots: bit s = mod slot s has canonical base C
+    const bool swap = ((c_slots >> c.slot) & 1u) != 0;                      // c_slots: bit s = mod slot s has canonical base C
+    prog[CLS_BASE_DW] = swap ? 0xFFFFFFFFu : 0u;
     for (int j = 0; j < c.len; ++j) {
-        const uint32_t set = m[j] & 15u;
+        uint32_t set = m[j] & 15u;
         if (set == 15u || j == c.modpos) continue;
+        if (swap) set = cls_swap_set(set);              // the tile of a C slot is built from (H, ~L)
         const int d = j - (int)c.modpos;
         const int g = (d >> 5) + 1;
         if (g < 0 || g > 1) continue;                   // (the host sends no such offset to a narrow variant)
@@ -553,10 +582,22 @@ __device__ __forceinline__ void emit_counts(const ScoreArgs &a, uint32_t n_mod, 
     if (K::PC) {
         // per-contig counters (motif_model_contig per contig, find_motifs_bin.py:1285-1331): a chunk lies inside ONE
         // contig, so the wave's sum goes straight to that (candidate, contig) row
+        if constexpr (K::CLS) {
+            // the sum is wanted in lane 0 only: five ds_swizzle butterflies (the lane pattern is an immediate) and the upper
+            // half through v_readlane, where __shfl_xor holds seven lane-index registers through every walk of the chunk
+#define NM_SWZ_ADD(o)                                                                         \
+            n_mod += (uint32_t)__builtin_amdgcn_ds_swizzle((int)n_mod, ((o) << 10) | 0x1f); \
+            n_non += (uint32_t)__builtin_amdgcn_ds_swizzle((int)n_non, ((o) << 10) | 0x1f);
+            NM_SWZ_ADD(16) NM_SWZ_ADD(8) NM_SWZ_ADD(4) NM_SWZ_ADD(2) NM_SWZ_ADD(1)
+#undef NM_SWZ_ADD
+            n_mod += (uint32_t)__builtin_amdgcn_readlane((int)n_mod, 32);
+            n_non += (uint32_t)__builtin_amdgcn_readlane((int)n_non, 32);
+        } else {
 #pragma unroll
-        for (int o = 32; o; o >>= 1) {
-            n_mod += __shfl_xor(n_mod, o);
-            n_non += __shfl_xor(n_non, o);
+            for (int o = 32; o; o >>= 1) {
+                n_mod += __shfl_xor(n_mod, o);
+                n_non += __shfl_xor(n_non, o);
+            }
         }
         if (lane == 0 && (n_mod | n_non)) {
             unsigned long long *row = a.out + (a.row_base[k0 + k] + contig_rank) * 2;
@@ -725,11 +766,14 @@ __device__ __forceinline__ void score_piece(const ScoreArgs &a, const uint4 sg, 
         most = max(most, range[j].y);
     }
     if (most == 0) return;
+    // CLS: the flip of the class tile, from the slot's canonical base (a scalar of the workgroup)
+    const uint32_t cm = K::CLS ? __builtin_amdgcn_readfirstlane(is_c[0] ? 0xFFFFFFFFu : 0u) : 0u;
 
     // one chunk of one pass: tile, then every slot's candidates of this pass
     auto score_tile = [&](auto tile_tag, const RawChunk<K> &cur, uint32_t pass0, uint32_t chunk) {
         typename decltype(tile_tag)::type tile;
-        tile.expand(cur);
+        if constexpr (K::CLS) tile.expand(cur, cm);
+        else tile.expand(cur);
         const uint32_t rank = K::PC ? ((cu32p)a.chunk_rank)[chunk] : 0u;
         // one slot at a time with the slot index a compile-time constant: left to `#pragma unroll`, the optimizer gave up on
         // the NS = 2 non-literal bodies ("loop not unrolled") and indexed cur.s[j] / range[j] / is_c[j] through private
@@ -738,7 +782,7 @@ __device__ __forceinline__ void score_piece(const ScoreArgs &a, const uint4 sg, 
             constexpr int j = decltype(jc)::value;
             if (range[j].y <= pass0) return;                         // wave-uniform
             const uint32_t nbj = min(H, range[j].y - pass0);
-            if constexpr (K::CLS)          // (one body: a class program carries its canonical base as a mask)
+            if constexpr (K::CLS)          // (one body: the tile is flipped so that plane 0 is the slot's canonical base)
                 score_candidates<K, 0>(a, tile, cur.s[j], range[j].x + pass0, nbj, range[j].z, range[j].w != 0, lds_acc, j, lane, rank);
             else if (K::COMPACT && is_c[j])
                 score_candidates<K, 1>(a, tile, cur.s[j], range[j].x + pass0, nbj, range[j].z, range[j].w != 0, lds_acc, j, lane, rank);
