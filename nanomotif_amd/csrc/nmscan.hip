@@ -114,11 +114,12 @@ __global__ void state_kernel(uint64_t n_rows, const uint32_t *__restrict__ conti
 
 __global__ void compile_kernel(uint32_t n_prog, const CandRec *__restrict__ rec, const uint8_t *__restrict__ masks,
                                uint32_t *__restrict__ programs, int wide, int np, int fold_modpos, int classes, uint32_t c_slots) {
-    // classes: write the class layout of the CLS variants (nmscan_device.h; wide, np and fold_modpos do not apply);
-    // c_slots: bit s = mod slot s has canonical base C (a class program carries its base)
+    // classes: write the class layout of the CLS variants (nmscan_device.h; wide, np and fold_modpos do not apply), 1 with the
+    // fused head of a walk, 2 with every literal left in its word (NM_SCORE_HEAD=0);
+    // c_slots: bit s = mod slot s has canonical base C (the compiler swaps the base sets of such a candidate)
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_prog) return;
-    if (classes) compile_one_classes(k, rec, masks, programs, c_slots);
+    if (classes) compile_one_classes(k, rec, masks, programs, c_slots, classes == 1);
     else compile_one(k, rec, masks, programs, wide, np, fold_modpos);
 }
 
@@ -685,8 +686,12 @@ int score_impl(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, const uint8
     const bool cf = light && !c->opt_no_cf;
     // IUPAC classes: exactly the batches that launch Variant<1, 1, true, 1, false, false, PC> take the class-plane twin of
     // that variant and the class program layout (the same 32 dwords per program).  NM_SCORE_CLASSES=0, read at every call,
-    // keeps them on the 8-plane path (same-process A/B, tests/test_gpu_iupac_classes.py).
+    // keeps them on the 8-plane path (same-process A/B, tests/test_gpu_iupac_classes.py).  NM_SCORE_HEAD=0, read at every
+    // call as well, compiles class programs without a head: every walk starts with plain moves and all literals stay in
+    // their words (tests/test_gpu_head_pair.py).
     const char *cls_env = getenv("NM_SCORE_CLASSES");
+    const char *head_env = getenv("NM_SCORE_HEAD");
+    const bool cls_head = !(head_env && atoi(head_env) == 0);
     const bool classes = !spec && !lit && !any_wide && all_compact && !cf && !(cls_env && atoi(cls_env) == 0);
     static_assert(nmdetail::CLS_PROG_DW == 32, "a class program takes the room of a narrow 8-plane one");
     static_assert(NM_MAX_MOD_SLOTS <= 32, "one bit per mod slot");
@@ -772,7 +777,7 @@ int score_impl(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, const uint8
         } else {
             hipLaunchKernelGGL(compile_kernel, dim3((n_prog + 255) / 256), dim3(256), 0, pst, n_prog,
                                reinterpret_cast<const CandRec *>(ds), ds + off_masks, d_prog, any_wide, (int)np,
-                               all_compact ? 1 : 0, classes ? 1 : 0, c_slots);
+                               all_compact ? 1 : 0, classes ? (cls_head ? 1 : 2) : 0, c_slots);
             HIP_TRY(hipGetLastError());
             if (cf) {
                 hipLaunchKernelGGL(common_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, pst, n_entries,

@@ -195,7 +195,7 @@ struct JointWalk {
 //     8, 9   H+ H-    10, 11   L+ L-    12, 13   X+ X-
 // The reverse strand takes the complemented set: A <-> T, C <-> G, and complementing flips H (so H+ <-> H-, X+ <-> X-)
 // and leaves L alone.  One program is CLS_PROG_DW dwords, forward half only:
-//     [0..7] literal words of word-groups 0, 1   [8] summary   [9..28] words 4..13 of word-groups 0, 1   [29] base mask   [30..31] zero
+//     [0..7] literal words of word-groups 0, 1   [8] summary   [9..28] words 4..13 of word-groups 0, 1   [29..31] head
 // summary: bit 10 g + (p - 4) is set iff word p >= 4 of word-group g is not empty.  The walk fetches a program as two
 // s_load_dwordx16: the first holds everything a candidate of literals needs (and the first seven class words).
 // Canonical first: all candidates of a workgroup belong to one mod slot, so their canonical base is known before the
@@ -203,9 +203,31 @@ struct JointWalk {
 // tile of a C slot is built from (H, ~L) and the tile of an A slot from (H, L): plane 0 is then the canonical base and
 // plane 3 its complement whatever the slot, the walk starts from those two planes with plain moves, and the compiler
 // (compile_one_classes) applies the same swap to every base set of a C-slot candidate.  One body for both mod types.
-// base mask: all ones when the candidate's canonical base is C, zero when it is A.  Written, but not read by the walk
-// (the flip comes from the slot, a scalar of the workgroup); a probe build can still read it.
-constexpr int CLS_PROG_DW = 32, CLS_SUMMARY_DW = 8, CLS_WORDS_DW = 9, CLS_BASE_DW = 29;
+// head: the first two literal constraints of a candidate in walk order (lowest dword, then lowest bit) are taken out of
+// their words and become the FIRST operation of its walk, acc = canonical plane & shift(P1) & shift(P2) straight from the
+// tile: one v_bitop3 per accumulator word where the walk had a move and two v_and.  It happens once, before the word
+// loop, so nothing is pending afterwards (a pair anywhere else needs state: docs/NEXT.md).  The descriptor is three
+// dwords, laid out so that the walk spends two scalar shifts on it (v_alignbit takes the low five bits of a shift operand
+// and the switch the id dword as it is; a scalar instruction of this kernel costs about an issue cycle):
+//     [29] id   [30] r1 | r2 << 8 | lit_left << 16   [31] (32 - r1) | (32 - r2) << 8, the reverse twins' shifts
+// id 0..35: the unordered pair (w1 <= w2) of literal words, w = 4 g + p = the word's dword (w1 == w2: two bits of one word,
+// r1 < r2); 36..43: a single literal w; 44: no literal, the walk starts with plain moves.  lit_left: a literal word is still
+// not empty (clear: the eight literal words are skipped behind one test).  A shift is never 0 here (the modified position
+// is folded and the offsets lie in [-31, 31]), so the head has no unshifted form.
+constexpr int CLS_PROG_DW = 32, CLS_SUMMARY_DW = 8, CLS_WORDS_DW = 9, CLS_HEAD_DW = 29, CLS_HEAD_FWD_DW = 30, CLS_HEAD_REV_DW = 31;
+constexpr int CLS_LIT_WORDS = 8, CLS_HEAD_SINGLE = 36, CLS_HEAD_NONE = 44, CLS_HEADS = 45;
+// (w1, w2) -> id; w2 < 0: a single head; w1 < 0 as well: none
+constexpr int cls_head_id(int w1, int w2) {
+    return w1 < 0 ? CLS_HEAD_NONE : w2 < 0 ? CLS_HEAD_SINGLE + w1 : w1 * CLS_LIT_WORDS - w1 * (w1 - 1) / 2 + (w2 - w1);
+}
+constexpr int cls_head_w1(int id) {
+    if (id >= CLS_HEAD_NONE) return -1;
+    if (id >= CLS_HEAD_SINGLE) return id - CLS_HEAD_SINGLE;
+    int w1 = 0;
+    while (w1 + 1 < CLS_LIT_WORDS && cls_head_id(w1 + 1, w1 + 1) <= id) ++w1;
+    return w1;
+}
+constexpr int cls_head_w2(int id) { return id >= CLS_HEAD_SINGLE ? -1 : cls_head_w1(id) + id - cls_head_id(cls_head_w1(id), cls_head_w1(id)); }
 constexpr int cls_plane(int p) { return p < 4 ? p : p < 8 ? p - 4 : 4 + (p - 8) / 2; }         // planes of ClassTile
 constexpr bool cls_neg(int p) { return p >= 4 && (p < 8 || ((p - 8) & 1)); }
 constexpr int cls_mirror(int p) { return p < 4 ? 3 - p : p < 8 ? 11 - p : (p == 10 || p == 11) ? p : (p ^ 1); }
@@ -234,6 +256,30 @@ constexpr bool cls_swap_ok() {
 static_assert(cls_swap_ok(), "A<->C, G<->T swap of a base set: class word and mirror, all 14 sets");
 static_assert(cls_word_of_set(cls_swap_set(2)) == 0 && cls_word_of_set(cls_swap_set(4)) == 3,
               "a C slot's canonical base is plane 0 of its tile, the complement plane 3");
+constexpr bool cls_heads_ok() {
+    int seen = 0;
+    for (int w1 = -1; w1 < CLS_LIT_WORDS; ++w1)
+        for (int w2 = -1; w2 < CLS_LIT_WORDS; ++w2) {
+            if (w2 >= 0 && (w1 < 0 || w2 < w1)) continue;
+            const int id = cls_head_id(w1, w2);
+            if (id < 0 || id >= CLS_HEADS || cls_head_w1(id) != w1 || cls_head_w2(id) != w2) return false;
+            ++seen;
+        }
+    for (int id = 0; id < CLS_HEADS; ++id)
+        if (cls_head_id(cls_head_w1(id), cls_head_w2(id)) != id) return false;
+    return seen == CLS_HEADS;                                                         // dense: 36 pairs, 8 singles, none
+}
+static_assert(cls_heads_ok(), "the 45 head ids and their (w1, w2) round-trip");
+// the reverse twin of literal word w = 4 g + p (narrow: GN = 1): plane 3 - p at word-group 2 GN - 1 - g
+constexpr bool cls_head_mirror_ok() {
+    for (int w = 0; w < CLS_LIT_WORDS; ++w) {
+        const int g = w / 4, p = w % 4;
+        if (cls_dword(g, p) != w || cls_plane(p) != p || cls_neg(p)) return false;    // a literal word is its dword, positive
+        if (cls_mirror(p) != 3 - p || cls_dword(2 * 1 - 1 - g, cls_mirror(p)) != CLS_LIT_WORDS - 1 - w) return false;
+    }
+    return true;
+}
+static_assert(cls_head_mirror_ok(), "mirror of a head word: plane 3 - p at word-group 2 GN - 1 - g");
 
 // Planes is-A / C / G / T, H, L, X (and V when BV) of the code (H, L ^ cm); cm is the wave-uniform flip of the slot, all
 // ones for canonical base C, so for a C slot the planes read is-C / A / T / G, H, ~L, ~X.  pack_kernel writes H and L as
@@ -319,15 +365,47 @@ struct ClassWalk {
             word<(4 * Q + 3) / 10, 4 + (4 * Q + 3) % 10>(m[CLS_WORDS_DW + 4 * Q + 3], tile);
         }
     }
-    __device__ __forceinline__ void walk(const uint32_t (&m)[CLS_PROG_DW], const TileT &tile, const uint32_t (&)[T_WORDS],
-                                         const uint32_t (&)[T_WORDS]) {
+    // no word of these variants has an unshifted constraint: the head (below) has no r = 0 form
+    static_assert(K::GN == 1 && !JointWalk<K>::template r0_possible<0>() && !JointWalk<K>::template r0_possible<1>(),
+                  "class walks: narrow, the modified position folded");
+    // literal word W of a head shifted into place, forward or as its reverse twin (r: that strand's shift)
+    template <int W, bool REV>
+    __device__ __forceinline__ uint32_t head_word(const TileT &tile, int t, uint32_t r) {
+        constexpr int G = REV ? 2 * K::GN - 1 - W / 4 : W / 4, P = REV ? 3 - W % 4 : W % 4;
+        return alignbit(tile.w[P][t + G + 1], tile.w[P][t + G], r);
+    }
+    // acc = canonical plane (& first literal (& second literal)), straight from the tile: no moves, one op per word
+    template <int ID>
+    __device__ __forceinline__ void head(const TileT &tile, uint32_t r1, uint32_t r2, uint32_t rr1, uint32_t rr2) {
+        constexpr int W1 = cls_head_w1(ID), W2 = cls_head_w2(ID);
 #pragma unroll
         for (int t = 0; t < T_WORDS; ++t) {                             // canonical first: plane 0 and its complement
-            accf[t] = tile.w[0][t + K::GN];
-            accr[t] = tile.w[3][t + K::GN];
+            uint32_t f = tile.w[0][t + K::GN], b = tile.w[3][t + K::GN];
+            if constexpr (W1 >= 0) { f &= head_word<W1, false>(tile, t, r1); b &= head_word<W1, true>(tile, t, rr1); }
+            if constexpr (W2 >= 0) { f &= head_word<W2, false>(tile, t, r2); b &= head_word<W2, true>(tile, t, rr2); }
+            accf[t] = f;
+            accr[t] = b;
         }
-        word<0, 0>(m[0], tile); word<0, 1>(m[1], tile); word<0, 2>(m[2], tile); word<0, 3>(m[3], tile);
-        word<1, 0>(m[4], tile); word<1, 1>(m[5], tile); word<1, 2>(m[6], tile); word<1, 3>(m[7], tile);
+    }
+    __device__ __forceinline__ void walk(const uint32_t (&m)[CLS_PROG_DW], const TileT &tile, const uint32_t (&)[T_WORDS],
+                                         const uint32_t (&)[T_WORDS]) {
+        const uint32_t r1 = m[CLS_HEAD_FWD_DW], r2 = r1 >> 8;           // (v_alignbit takes the low five bits of a shift)
+        const uint32_t rr1 = m[CLS_HEAD_REV_DW], rr2 = rr1 >> 8;
+        // dense ids, the plain moves an ordinary case: as `default:` the compiler hoists them in front of the compares
+#define NM_HEAD_CASE(i) case i: head<i>(tile, r1, r2, rr1, rr2); break;
+#define NM_HEAD_CASES5(i) NM_HEAD_CASE(i) NM_HEAD_CASE(i + 1) NM_HEAD_CASE(i + 2) NM_HEAD_CASE(i + 3) NM_HEAD_CASE(i + 4)
+        switch (m[CLS_HEAD_DW]) {                                       // wave-uniform, once per candidate
+            NM_HEAD_CASES5(0) NM_HEAD_CASES5(5) NM_HEAD_CASES5(10) NM_HEAD_CASES5(15) NM_HEAD_CASES5(20)
+            NM_HEAD_CASES5(25) NM_HEAD_CASES5(30) NM_HEAD_CASES5(35) NM_HEAD_CASES5(40)
+            default: __builtin_unreachable();
+        }
+#undef NM_HEAD_CASES5
+#undef NM_HEAD_CASE
+        static_assert(CLS_HEADS == 45, "one case per head id");
+        if (m[CLS_HEAD_FWD_DW] >> 16) {                                 // wave-uniform: a literal beyond the head
+            word<0, 0>(m[0], tile); word<0, 1>(m[1], tile); word<0, 2>(m[2], tile); word<0, 3>(m[3], tile);
+            word<1, 0>(m[4], tile); word<1, 1>(m[5], tile); word<1, 2>(m[6], tile); word<1, 3>(m[7], tile);
+        }
         if (m[CLS_SUMMARY_DW]) {                                        // wave-uniform: 20 class words skipped at once
             quad<0>(m, tile); quad<1>(m, tile); quad<2>(m, tile); quad<3>(m, tile); quad<4>(m, tile);
         }
@@ -433,14 +511,14 @@ __device__ __forceinline__ void compile_one(uint32_t k, const CandRec *__restric
 
 // The class layout (CLS variants: narrow, compact, so the modified position is folded and offsets lie in [-31, 31]): the
 // forward half only, one constraint per set of one, two or three bases, and the summary dword (layout: ClassWalk).
+// use_head: the first two literals become the head of the walk; without it every literal stays in its word (id 44).
 __device__ __forceinline__ void compile_one_classes(uint32_t k, const CandRec *__restrict__ rec, const uint8_t *__restrict__ masks,
-                                                    uint32_t *__restrict__ programs, uint32_t c_slots) {
+                                                    uint32_t *__restrict__ programs, uint32_t c_slots, bool use_head) {
     uint32_t *prog = programs + (size_t)k * CLS_PROG_DW;
     for (int i = 0; i < CLS_PROG_DW; ++i) prog[i] = 0;
     const CandRec c = rec[k];
     const uint8_t *m = masks + c.mask_off;
     const bool swap = ((c_slots >> c.slot) & 1u) != 0;                      // c_slots: bit s = mod slot s has canonical base C
-    prog[CLS_BASE_DW] = swap ? 0xFFFFFFFFu : 0u;
     for (int j = 0; j < c.len; ++j) {
         uint32_t set = m[j] & 15u;
         if (set == 15u || j == c.modpos) continue;
@@ -452,6 +530,23 @@ __device__ __forceinline__ void compile_one_classes(uint32_t k, const CandRec *_
         prog[cls_dword(g, p)] |= 1u << ((uint32_t)d & 31u);
         if (p >= 4) prog[CLS_SUMMARY_DW] |= 1u << (10 * g + p - 4);
     }
+    // the head: after the swap, the first two literal constraints in walk order leave their words
+    int w1 = -1, w2 = -1;
+    uint32_t r1 = 0, r2 = 0, left = 0;
+    for (int w = 0; w < CLS_LIT_WORDS; ++w) {
+        uint32_t mm = prog[w];
+        while (use_head && mm && w2 < 0) {
+            const uint32_t r = (uint32_t)__ffs(mm) - 1u;
+            mm &= mm - 1;
+            if (w1 < 0) { w1 = w; r1 = r; }
+            else { w2 = w; r2 = r; }
+        }
+        prog[w] = mm;
+        left |= mm;
+    }
+    prog[CLS_HEAD_DW] = (uint32_t)cls_head_id(w1, w2);
+    prog[CLS_HEAD_FWD_DW] = r1 | r2 << 8 | (left ? 1u << 16 : 0u);
+    prog[CLS_HEAD_REV_DW] = ((32u - r1) & 31u) | ((32u - r2) & 31u) << 8;
 }
 
 // Light batches (a round of the greedy search): the constraints shared by ALL candidates of a (slot, bin) group — the
@@ -514,17 +609,22 @@ __device__ __forceinline__ void common_one(uint32_t g, uint4 *__restrict__ range
 // ---- the scoring kernel ------------------------------------------------------------------------------------------------
 // score_kernel and what it is made of, for the two translation units that instantiate it (they define
 // NM_SCORE_KERNEL_SOURCE before including this header): nmscan.hip — every variant but the class-plane ones — and
-// nmscore_classes.hip, which is nothing but this header with NM_SCORE_CLASSES_UNIT defined and exists because of one
-// compiler flag.  The flag is declared HERE, in the line below that build.py reads, so that the kernel's source and what
-// decides its register count stay in one file:
+// nmscore_classes.hip, which is nothing but this header with NM_SCORE_CLASSES_UNIT defined and exists because of its
+// compiler flags.  They are declared HERE, in the line below that build.py reads, so that the kernel's source and what
+// decides its register count and its branches stay in one file:
 //
-// NM_UNIT_FLAGS nmscore_classes.hip: -fno-slp-vectorize
+// NM_UNIT_FLAGS nmscore_classes.hip: -fno-slp-vectorize -mllvm -structurizecfg-skip-uniform-regions -mllvm -enable-tail-merge=0
 //
 // The SLP vectorizer pairs the eight accumulator words of the class walk and, through them, the words of the tile into
 // <2 x i32> values; those want aligned register pairs, the halo words get copied into place (v_pk_mov_b32, v_mov_b32), and
 // the class variants end at 86 - 94 VGPRs (5 waves per SIMD), or at 80 with scratch when held to 6 waves.  Without that
-// pass: 80 VGPRs, no scratch, 6 waves, no copy of a plane word.  The pass cannot be switched off per function.  Every other
-// variant keeps the flags and the code it had.
+// pass: 80 VGPRs, no scratch, 6 waves, no copy of a plane word.  The pass cannot be switched off per function.
+// The head switch of ClassWalk::walk is a 45-way scalar compare tree whose leaves join in one block.  The structurizer
+// runs over uniform control flow as well and turns every level of that join into a flag (s_mov_b64 / s_andn2_b64 vcc, exec /
+// s_cbranch_vccnz, 44 per body): measured 4.5 % slower than no head at all.  -structurizecfg-skip-uniform-regions leaves
+// uniform regions as compares and branches (74 / 78 VGPRs).  Branch folding then merges the ends of leaves into shared
+// tails behind one more taken branch per walk (1 % of the kernel): -enable-tail-merge=0.  profiles/r17/head_pair.md.
+// Every other variant keeps the flags and the code it had.
 #ifdef NM_SCORE_KERNEL_SOURCE
 
 namespace nmdetail {

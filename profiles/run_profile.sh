@@ -13,7 +13,7 @@ rc=$?
 if [ $rc -ne 0 ]; then echo "run_profile.sh: kernel-trace run exited with $rc, stopping (log: $out/bench_under_trace.log)" >&2; exit $rc; fi
 find /tmp/prof_$tag/trace -name "*kernel_stats.csv" -exec cp {} $out/kernel_stats.csv \;
 find /tmp/prof_$tag/trace -name "*kernel_trace.csv" -exec sh -c 'head -1 "$1" > '$out'/kernel_trace_score.csv; grep score_kernel "$1" >> '$out'/kernel_trace_score.csv' _ {} \;
-for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU GRBM_GUI_ACTIVE" "TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum"; do
+for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU" "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU SQ_THREAD_CYCLES_VALU GRBM_GUI_ACTIVE" "TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum" "SQ_IFETCH SQ_INSTS_BRANCH SQ_ACTIVE_INST_MISC SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE"; do
   name=$(echo $pass | tr ' ' '_' | cut -c1-40)
   timeout -k 10 900 rocprofv3 --pmc $pass --output-format csv -d /tmp/prof_$tag/pmc_$name -- $B --steps 3 --warmup 1 --prewarm 0 > $out/bench_under_pmc_$name.log 2>&1
   rc=$?

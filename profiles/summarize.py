@@ -48,6 +48,7 @@ names = {"pmc_FETCH_SIZE.csv": "pmc_FETCH_SIZE.csv", "pmc_WRITE_SIZE.csv": "pmc_
          "pmc_SQ_WAVES_SQ_INSTS_VALU_SQ_INSTS_SALU_SQ_.csv": "pmc_sq_insts.csv",
          "pmc_SQ_WAIT_INST_ANY_SQ_WAIT_ANY_SQ_ACTIVE_I.csv": "pmc_sq_wait.csv",
          "pmc_TCC_HIT_sum_TCC_MISS_sum_TCC_EA0_RDREQ_s.csv": "pmc_tcc.csv",
+         "pmc_SQ_IFETCH_SQ_INSTS_BRANCH_SQ_ACTIVE_INST.csv": "pmc_sq_ifetch.csv",
          "kernel_trace_score.csv": "kernel_trace_score.csv", "bench_under_trace.json": "bench_under_trace.json"}
 for a, b in names.items():
     if not os.path.exists(os.path.join(src, a)):
@@ -111,6 +112,7 @@ here hold the rows of this repository's kernels only.  Generated by `profiles/su
 | integer-VALU rate | {c['SQ_INSTS_VALU']/(avg_us*1e-6)/1e11:.2f}e11 wave-instr/s = **{c['SQ_INSTS_VALU']/(avg_us*1e-6)/1.2288e12*100:.0f} % of the chip's issue peak** (256 CU x 4 SIMD x 2.4 GHz / 2 cycles per wave64 op = 1.23e12) = {c['SQ_INSTS_VALU']/(avg_us*1e-6)/6.1e11*100:.0f} % of the 6.1e11 this instruction mix reaches in `tools/valu_peak.hip` (half its ops are the half-rate v_alignbit_b32) | see DESIGN.md §4 |
 | scalar side | SQ_INST_CYCLES_SALU {c.get('SQ_INST_CYCLES_SALU', 0)/1e6:.1f} M, SQ_BUSY_CYCLES {c.get('SQ_BUSY_CYCLES', 0)/1e6:.1f} M, SALU / VALU instructions {c['SQ_INSTS_SALU']/c['SQ_INSTS_VALU']:.2f} | `pmc_sq_insts.csv`, `pmc_sq_wait.csv` |
 | wave time split | ACTIVE_INST_ANY {c['SQ_ACTIVE_INST_ANY']/c['SQ_WAVE_CYCLES']*100:.0f} %, WAIT_INST_ANY {c['SQ_WAIT_INST_ANY']/c['SQ_WAVE_CYCLES']*100:.0f} %, WAIT_ANY {c['SQ_WAIT_ANY']/c['SQ_WAVE_CYCLES']*100:.0f} % of SQ_WAVE_CYCLES | `pmc_sq_wait.csv` |
+| instruction fetch | SQ_IFETCH {c.get('SQ_IFETCH', 0)/1e6:.2f} M, SQC_ICACHE_REQ {c.get('SQC_ICACHE_REQ', 0)/1e6:.2f} M (hits {c.get('SQC_ICACHE_HITS', 0)/1e6:.2f} M, misses {c.get('SQC_ICACHE_MISSES', 0)/1e6:.3f} M, duplicate misses {c.get('SQC_ICACHE_MISSES_DUPLICATE', 0)/1e6:.3f} M); SQ_INSTS_BRANCH {c.get('SQ_INSTS_BRANCH', 0)/1e6:.1f} M, SQ_ACTIVE_INST_MISC {c.get('SQ_ACTIVE_INST_MISC', 0)/1e6:.1f} M | `pmc_sq_ifetch.csv` |
 """
 open(os.path.join(dst, "SUMMARY.md"), "w").write(md)
 print(md)
