@@ -125,20 +125,33 @@ def motif_zoo():
 # bgzip + tabix of a bedMethyl text (what `bgzip p.bed; tabix -p bed p.bed.gz` produce), written from the format
 # specifications (SAM spec §4.1 BGZF; tabix.pdf) — htslib / pysam are not in the image
 # ---------------------------------------------------------------------------------------------
-def write_bgzf_tabix(bed_text: bytes, gz_path: str, block_size: int = 0xFF00, level: int = 6, strategy: int = 0):
+def write_bgzf_tabix(bed_text: bytes, gz_path: str, block_size: int = 0xFF00, level: int = 6, strategy: int = 0, member_sizes=None,
+                     deflate=None):
+    """member_sizes: the text size of every member, in place of the one block_size; deflate: a callable that turns a member's text into
+    its raw deflate stream, in place of zlib (tests/deflate_streams.py: hand-built streams) — the index describes those members too."""
+    import bisect
     import struct
     import zlib
 
-    def block(data: bytes) -> bytes:
-        c = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
-        comp = c.compress(data) + c.flush()
+    def block(data: bytes, deflate=None) -> bytes:
+        if deflate is None:
+            c = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
+            comp = c.compress(data) + c.flush()
+        else:
+            comp = deflate(data)
+        assert len(comp) + 25 <= 0xFFFF
         return (struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, len(comp) + 25) + comp
                 + struct.pack("<II", zlib.crc32(data), len(data)))
 
     # blocks cut at arbitrary byte positions (lines straddle blocks, as in real files)
+    if member_sizes is None:
+        starts = list(range(0, len(bed_text), block_size))
+    else:
+        assert sum(member_sizes) == len(bed_text) and all(0 < n <= 65536 for n in member_sizes)
+        starts = [sum(member_sizes[:k]) for k in range(len(member_sizes))]
     blocks, block_coff, coff = [], [], 0
-    for i in range(0, len(bed_text), block_size):
-        b = block(bed_text[i:i + block_size])
+    for k, i in enumerate(starts):
+        b = block(bed_text[i:starts[k + 1] if k + 1 < len(starts) else len(bed_text)], deflate)
         block_coff.append(coff)
         blocks.append(b)
         coff += len(b)
@@ -149,8 +162,8 @@ def write_bgzf_tabix(bed_text: bytes, gz_path: str, block_size: int = 0xFF00, le
     def voff(text_off: int) -> int:
         if text_off >= len(bed_text):
             return coff << 16
-        k = text_off // block_size
-        return (block_coff[k] << 16) | (text_off - k * block_size)
+        k = bisect.bisect_right(starts, text_off) - 1
+        return (block_coff[k] << 16) | (text_off - starts[k])
 
     def reg2bin(beg, end):
         end -= 1
@@ -199,6 +212,24 @@ def write_bgzf_tabix(bed_text: bytes, gz_path: str, block_size: int = 0xFF00, le
     idx = b"".join(out)
     with open(gz_path + ".tbi", "wb") as f:                 # the index is itself BGZF
         f.write(b"".join(block(idx[i:i + block_size]) for i in range(0, len(idx), block_size)) + eof)
+
+
+def pileup_columns(t):
+    """the rows of a NativePileup / DevicePileup as host columns, contigs numbered as the file names them"""
+    from nanomotif_amd import pileup as pp
+    if isinstance(t, pp.NativePileup):
+        return {k: v.copy() for k, v in t.ingest_columns(np.arange(len(t.contig_names), dtype=np.uint32)).items()}
+    t.map_contigs(np.arange(len(t.contig_names), dtype=np.uint32))
+    return t.to_host()
+
+
+def assert_same_rows(dev, host):
+    """every row of the device parser equals the host reader's, fraction_mod bit for bit"""
+    assert dev.contig_names == host.contig_names and len(dev) == len(host)
+    cd, ch = pileup_columns(dev), pileup_columns(host)
+    for k in ("contig", "position", "mod_type", "strand", "nvalid_cov"):
+        assert np.array_equal(cd[k], ch[k]), k
+    assert np.array_equal(cd["fraction_mod"].view(np.uint64), ch["fraction_mod"].view(np.uint64))
 
 
 REF_TBI = os.path.join(GOLDEN, "data_geobacillus-plasmids.pileup.bed.gz.tbi")

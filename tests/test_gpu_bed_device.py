@@ -160,19 +160,7 @@ def test_contig_names_come_back_with_their_runs(tmp_path):
         eng.close()
 
 
-def _columns(t, lut=None):
-    if isinstance(t, pp.NativePileup):
-        return {k: v.copy() for k, v in t.ingest_columns(np.arange(len(t.contig_names), dtype=np.uint32)).items()}
-    t.map_contigs(np.arange(len(t.contig_names), dtype=np.uint32))
-    return t.to_host()
-
-
-def _assert_same_rows(dev, host):
-    assert dev.contig_names == host.contig_names and len(dev) == len(host)
-    cd, ch = _columns(dev), _columns(host)
-    for k in ("contig", "position", "mod_type", "strand", "nvalid_cov"):
-        assert np.array_equal(cd[k], ch[k]), k
-    assert np.array_equal(cd["fraction_mod"].view(np.uint64), ch["fraction_mod"].view(np.uint64))
+from helpers import assert_same_rows as _assert_same_rows      # (shared with tests/test_gpu_bed_inflate_streams.py)
 
 
 def test_bgzip_and_tabix_subset_on_the_device_parser(tmp_path):
@@ -226,9 +214,10 @@ def test_bgzip_and_tabix_subset_on_the_device_parser(tmp_path):
         dev = pp.DevicePileup(eng, gz, contigs=[mg.names[4], "not_in_the_file"], index_path=gz + ".tbi")
         assert dev.indexed and dev.contig_names == [mg.names[4]] and dev.contigs_not_indexed == 1
         dev.close()
-    # every kind of DEFLATE block through the device decoder: stored (level 0), fixed Huffman codes (Z_FIXED, and what zlib
+    # every kind zlib writes through the device decoder: stored (level 0), fixed Huffman codes (Z_FIXED, and what zlib
     # picks for tiny blocks), dynamic codes at the extremes of the compressor's effort, run-length matches (Z_RLE: distance 1,
-    # overlapping copies), literals only (Z_HUFFMAN_ONLY)
+    # overlapping copies), literals only (Z_HUFFMAN_ONLY) — what RFC 1951 allows beyond that (15-bit codes, length 258, distance
+    # 32 768, mixed and empty blocks, ...) is in tests/test_gpu_bed_inflate_streams.py, on the streams of tests/deflate_streams.py
     import zlib
     for tag, kw in (("stored", dict(level=0)), ("fixed", dict(level=6, strategy=zlib.Z_FIXED)), ("tiny", dict(level=6, block_size=96)),
                     ("fast", dict(level=1)), ("best", dict(level=9, block_size=0xFF00)), ("rle", dict(level=6, strategy=zlib.Z_RLE)),
