@@ -196,7 +196,8 @@ struct JointWalk {
 // The reverse strand takes the complemented set: A <-> T, C <-> G, and complementing flips H (so H+ <-> H-, X+ <-> X-)
 // and leaves L alone.  One program is CLS_PROG_DW dwords, forward half only:
 //     [0..7] literal words of word-groups 0, 1   [8] summary   [9..28] words 4..13 of word-groups 0, 1   [29..31] head
-// summary: bit 10 g + (p - 4) is set iff word p >= 4 of word-group g is not empty.  The walk fetches a program as two
+// summary: bit 10 g + (p - 4) is set iff word p >= 4 of word-group g is not empty, and bit 20 + q iff one of the four
+// class words 4 q .. 4 q + 3 (counted from dword 9) is: the walk tests the whole dword, then one bit per quad.  It fetches a program as two
 // s_load_dwordx16: the first holds everything a candidate of literals needs (and the first seven class words).
 // Canonical first: all candidates of a workgroup belong to one mod slot, so their canonical base is known before the
 // first chunk arrives.  Flipping L swaps A <-> C and G <-> T and commutes with complementation (which flips H), so the
@@ -215,6 +216,7 @@ struct JointWalk {
 // not empty (clear: the eight literal words are skipped behind one test).  A shift is never 0 here (the modified position
 // is folded and the offsets lie in [-31, 31]), so the head has no unshifted form.
 constexpr int CLS_PROG_DW = 32, CLS_SUMMARY_DW = 8, CLS_WORDS_DW = 9, CLS_HEAD_DW = 29, CLS_HEAD_FWD_DW = 30, CLS_HEAD_REV_DW = 31;
+constexpr int CLS_QUAD_BIT = 20;                // summary: bit CLS_QUAD_BIT + q is set iff one of class words 4 q .. 4 q + 3 is not empty
 constexpr int CLS_LIT_WORDS = 8, CLS_HEAD_SINGLE = 36, CLS_HEAD_NONE = 44, CLS_HEADS = 45;
 // (w1, w2) -> id; w2 < 0: a single head; w1 < 0 as well: none
 constexpr int cls_head_id(int w1, int w2) {
@@ -355,10 +357,12 @@ struct ClassWalk {
             and_in<G, P>(tile, r);
         }
     }
-    // the four class words behind summary bits 4 Q .. 4 Q + 3
+    // the four class words behind summary bits 4 Q .. 4 Q + 3, skipped on the quad's own bit: a one-bit test is s_bitcmp1_b32 +
+    // s_cbranch where the four-bit mask is s_and_b32 + s_cmp_eq_u32 + s_cbranch, and a scalar instruction of this walk costs
+    // its issue cycle whether a branch is taken or not (profiles/r18/walk_order.md)
     template <int Q>
     __device__ __forceinline__ void quad(const uint32_t (&m)[CLS_PROG_DW], const TileT &tile) {
-        if (m[CLS_SUMMARY_DW] & (0xFu << (4 * Q))) {                    // wave-uniform
+        if (m[CLS_SUMMARY_DW] & (1u << (CLS_QUAD_BIT + Q))) {           // wave-uniform
             word<(4 * Q + 0) / 10, 4 + (4 * Q + 0) % 10>(m[CLS_WORDS_DW + 4 * Q + 0], tile);
             word<(4 * Q + 1) / 10, 4 + (4 * Q + 1) % 10>(m[CLS_WORDS_DW + 4 * Q + 1], tile);
             word<(4 * Q + 2) / 10, 4 + (4 * Q + 2) % 10>(m[CLS_WORDS_DW + 4 * Q + 2], tile);
@@ -528,7 +532,7 @@ __device__ __forceinline__ void compile_one_classes(uint32_t k, const CandRec *_
         if (g < 0 || g > 1) continue;                   // (the host sends no such offset to a narrow variant)
         const int p = cls_word_of_set(set);
         prog[cls_dword(g, p)] |= 1u << ((uint32_t)d & 31u);
-        if (p >= 4) prog[CLS_SUMMARY_DW] |= 1u << (10 * g + p - 4);
+        if (p >= 4) prog[CLS_SUMMARY_DW] |= 1u << (10 * g + p - 4) | 1u << (CLS_QUAD_BIT + (10 * g + p - 4) / 4);
     }
     // the head: after the swap, the first two literal constraints in walk order leave their words
     int w1 = -1, w2 = -1;
@@ -751,6 +755,9 @@ __device__ __forceinline__ void score_heavy(const ScoreArgs &a, const TileT &til
                 const uint32_t sites = jw.accf[t] | jw.accr[t];  // forward sites sit on the canonical base, reverse on its complement
                 n_mod += __popc(sites & sw[0][t]);
                 n_non += __popc(sites & sw[1][t]);
+                // CLS: v_bcnt_u32_b32 adds to its second operand; pinned between the words the two counters stay two chains
+                // of four v_bcnt (left alone the compiler sums each counter as a tree and joins it with a v_add3_u32)
+                if constexpr (K::CLS) { asm("" : "+v"(n_mod)); asm("" : "+v"(n_non)); }
             } else {
                 n_mod += __popc(jw.accf[t] & sw[0][t]) + __popc(jw.accr[t] & sw[K::COMPACT ? 0 : 2][t]);
                 n_non += __popc(jw.accf[t] & sw[1][t]) + __popc(jw.accr[t] & sw[K::COMPACT ? 1 : 3][t]);
