@@ -17,7 +17,6 @@ namespace {
 struct CompareArgs : ExportArgs {
     const uint32_t *cand_row0;           // first row of the candidate in the (candidate, contig) table
     const unsigned long long *cand_planes;   // [n_cand][8] MP UP MM UM of slot A, then of slot B
-    const uint32_t *programs;            // [n_cand][PROG6_DW] sliced to the candidate's width
     uint32_t transition_set;             // bit t = transition t is exported
     unsigned long long *table;           // count pass: [row][18], may be NULL
 };
@@ -32,15 +31,9 @@ __global__ __launch_bounds__(256) void compare_kernel(CompareArgs a) {
     const unsigned long long *pl = a.cand_planes + (size_t)k * 8;
     const StatePlanes stp[2] = {slot_planes(pl), slot_planes(pl + 4)};
     RawChunk<K> raw;
-    raw.load(a.seq, stp, w.chunk, lane);                                 // sequence planes once, the state planes of both slots
     Tile<K> tile;
-    tile.expand(raw);
     uint32_t af[T_WORDS], ar[T_WORDS];
-#pragma unroll
-    for (int t = 0; t < T_WORDS; ++t) af[t] = ar[t] = 0xFFFFFFFFu;
-    const cu32p prog = (cu32p)(a.programs + (size_t)k * PROG6_DW);
-    eval_strand<K>(prog, tile, af);                                      // one walk per strand serves both samples
-    eval_strand<K>(prog + K::PDW, tile, ar);
+    find_occurrences<K>(a, w, stp, lane, raw, tile, af, ar);             // sequence planes once, one walk per strand: both serve both samples
     const uint32_t set = a.transition_set;
     if (!FILL) {
         uint32_t c[18], n = 0;
@@ -103,46 +96,22 @@ int compare_begin(CompareBatch &cb, nm_ctx *c, uint32_t n_cand, const uint32_t *
     if (!c->dH) return fail(NM_ESTATE, "nm_upload_contigs has not been called");
     if (transition_set == 0 || (transition_set & ~NM_COMPARE_ALL))
         return fail(NM_EINVAL, "transition_set %u: a non-empty combination of the bits 0..8 (bit 3 * state_a + state_b)", transition_set);
-    std::vector<uint32_t> row0(n_cand, 0), programs((size_t)n_cand * PROG6_DW, 0);
-    std::vector<unsigned long long> planes((size_t)n_cand * 8, 0);
-    std::vector<uint8_t> width(n_cand, 0);
-    uint64_t items = 0, rows = 0;
     if (row_offset && row_offset[0] != 0) return fail(NM_EINVAL, "row_offset[0] must be 0");
-    for (uint32_t k = 0; k < n_cand; ++k) {
-        const uint32_t bin = cand_bin[k];
-        const uint32_t slots[2] = {cand_slot_a[k], cand_slot_b[k]};
-        for (int s = 0; s < 2; ++s) {
-            if (slots[s] >= NM_MAX_MOD_SLOTS || !c->slots[slots[s]].present || !c->slots[slots[s]].planes[2])
-                return fail(NM_ESTATE, "candidate %u uses mod slot %u (sample %c) with no pileup uploaded", k, slots[s], s ? 'B' : 'A');
-            for (int j = 0; j < 4; ++j) planes[(size_t)k * 8 + 4 * s + j] = (unsigned long long)(uintptr_t)c->slots[slots[s]].planes[2 + j];
-        }
-        if (bin >= c->n_bins) return fail(NM_EINVAL, "candidate %u: bin %u >= n_bins %u", k, bin, c->n_bins);
-        uint32_t full[PROG6_DW];
-        int reach = 0;
-        const int rc = compile_program(cand_masks + cand_mask_offset[k], cand_len[k], cand_modpos[k], full, &reach);
-        if (rc) return rc;
-        slice_program(full, reach + 1, programs.data() + (size_t)k * PROG6_DW);
-        if (row_offset) {
-            if (row_offset[k + 1] < row_offset[k] || row_offset[k + 1] - row_offset[k] < c->bin_ncontigs[bin])
-                return fail(NM_EINVAL, "candidate %u: %llu rows for the %u resident contigs of bin %u", k,
-                            (unsigned long long)(row_offset[k + 1] - row_offset[k]), c->bin_ncontigs[bin], bin);
-            if (row_offset[k + 1] >= 0xFFFFFFFFull) return fail(NM_ERANGE, "more than 2^32 (candidate, contig) rows in one batch");
-            row0[k] = (uint32_t)row_offset[k];
-            rows = row_offset[k + 1];
-        }
-        width[k] = (uint8_t)reach;
-        items += c->bin_nchunks[bin];
-        if (items >= 0xFFFFFFF0ull) return fail(NM_ERANGE, "more than 2^32 (candidate, chunk) work items in one batch: send fewer candidates");
-    }
+    std::vector<unsigned long long> planes((size_t)n_cand * 8, 0);
+    Staged st;
+    const int rc = stage_candidates(c, {n_cand, cand_bin, {cand_len, cand_modpos, cand_mask_offset, cand_masks}}, nullptr, row_offset, false, st,
+                                    [&](uint32_t k, uint32_t, uint64_t &) {                // the two slots of the candidate
+                                        const int ra = slot_state_planes(c, "cand_slot_a", k, cand_slot_a[k], planes.data() + (size_t)k * 8);
+                                        return ra ? ra : slot_state_planes(c, "cand_slot_b", k, cand_slot_b[k], planes.data() + (size_t)k * 8 + 4);
+                                    });
+    if (rc) return rc;
     CompareArgs &a = cb.base;
     a.transition_set = transition_set;
     std::vector<ExportTable> reserved;
-    if (row_offset) reserved.push_back({&a.table, (size_t)rows * 144});
-    return export_begin(cb, c, n_cand, cand_bin, width.data(),
-                        {{&a.cand_row0, row0.data(), row0.size() * 4},
-                         {&a.cand_planes, planes.data(), planes.size() * 8},
-                         {&a.programs, programs.data(), programs.size() * 4}},
-                        reserved, compare_kernels<false>, with_scan);
+    if (row_offset) reserved.push_back({&a.table, (size_t)st.rows * 144});
+    return export_begin(cb, c, n_cand, cand_bin, st.width.data(), st.programs,
+                        {{&a.cand_row0, st.row0.data(), st.row0.size() * 4}, {&a.cand_planes, planes.data(), planes.size() * 8}}, reserved,
+                        compare_kernels<false>, with_scan);
 }
 
 }  // namespace

@@ -29,28 +29,10 @@ constexpr int CTX_MAX_CELLS = (2 * NM_CONTEXT_MAX_RADIUS + 1) * CTX_ROW;
 
 struct ContextArgs : ExportArgs {
     const unsigned long long *cand_planes;   // [n_cand][4] MP UP MM UM of the candidate's mod slot
-    const uint32_t *programs;                // [n_cand][PROG6_DW] sliced to the candidate's width
     uint32_t radius, wave_atomics;
     unsigned long long *states;              // [n_cand][2][3]
     unsigned long long *table;               // [n_cand][2 radius + 1][2][3][4]
 };
-
-// word t of a plane's six halo words seen `sh` positions further along '+': UP = sh >= 0 (bits = sh), else bits = 32 + sh
-template <bool UP>
-__device__ __forceinline__ uint32_t shifted(const uint32_t (&w)[T_WORDS + 2], int t, uint32_t bits) {
-    return UP ? alignbit(w[t + 2], w[t + 1], bits) : alignbit(w[t + 1], w[t], bits);
-}
-
-// index into cls_owner of the owner of work item `it` of this launch (scalar loads, scalar control flow)
-__device__ __forceinline__ uint32_t class_slot(const ExportArgs &a, uint32_t it) {
-    const cu32p item0 = (cu32p)a.cls_item0;
-    uint32_t lo = 0, hi = a.n_cls;
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (item0[mid] <= it) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // The wave's sums of twelve dwords per lane: lane 16 g (g = 0..3) returns those of p[6 (g >> 1) + 3 (g & 1) + j] in out[j].  The
 // steps over lane bits 5 and 4 keep one half of the dwords and send the other; the four remaining steps are a plain butterfly.
@@ -121,23 +103,18 @@ __device__ __forceinline__ void context_item(const ContextArgs &a, const WorkIte
     const uint32_t k = w.owner;
     const StatePlanes stp[1] = {slot_planes(a.cand_planes + (size_t)k * 4)};
     RawChunk<K> raw;
-    raw.load(a.seq, stp, w.chunk, lane);
     Tile<K> tile;
-    tile.expand(raw);
     uint32_t af[T_WORDS], ar[T_WORDS];
-#pragma unroll
-    for (int t = 0; t < T_WORDS; ++t) af[t] = ar[t] = 0xFFFFFFFFu;
-    const cu32p prog = (cu32p)(a.programs + (size_t)k * PROG6_DW);
-    eval_strand<K>(prog, tile, af);
-    eval_strand<K>(prog + K::PDW, tile, ar);
+    find_occurrences<K>(a, w, stp, lane, raw, tile, af, ar);
     uint32_t fs[3][T_WORDS], rs[3][T_WORDS], c[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int t = 0; t < T_WORDS; ++t) {
-        const uint32_t mp = raw.s[0][0][t], up = raw.s[0][1][t] & ~mp, mm = raw.s[0][2][t], um = raw.s[0][3][t] & ~mm;
-        fs[0][t] = af[t] & mp; fs[1][t] = af[t] & up; fs[2][t] = af[t] & ~(mp | up);
-        rs[0][t] = ar[t] & mm; rs[1][t] = ar[t] & um; rs[2][t] = ar[t] & ~(mm | um);
+        uint32_t f[3], r[3];
+        split_states(raw.s[0], t, af[t], ar[t], f, r);
 #pragma unroll
         for (int st = 0; st < 3; ++st) {
+            fs[st][t] = f[st];
+            rs[st][t] = r[st];
             c[st] += __popc(fs[st][t]);
             c[3 + st] += __popc(rs[st][t]);
         }
@@ -212,34 +189,17 @@ int nm_motif_context_count(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin,
     if (!c) return fail(NM_EINVAL, "ctx is NULL");
     if (n_cand == 0) return NM_OK;
     if (!c->dH) return fail(NM_ESTATE, "nm_upload_contigs has not been called");
-    std::vector<uint32_t> programs((size_t)n_cand * PROG6_DW, 0);
-    std::vector<unsigned long long> planes((size_t)n_cand * 4, 0);
-    std::vector<uint8_t> width(n_cand, 0);
-    uint64_t items = 0;
-    for (uint32_t k = 0; k < n_cand; ++k) {
-        const uint32_t slot = cand_mod_slot[k], bin = cand_bin[k];
-        if (bin >= c->n_bins) return fail(NM_EINVAL, "candidate %u: cand_bin %u >= n_bins %u", k, bin, c->n_bins);
-        if (slot >= NM_MAX_MOD_SLOTS || !c->slots[slot].present || !c->slots[slot].planes[2])
-            return fail(NM_ESTATE, "cand_mod_slot[%u] = %u: no pileup uploaded in that mod slot", k, slot);
-        for (int j = 0; j < 4; ++j) planes[(size_t)k * 4 + j] = (unsigned long long)(uintptr_t)c->slots[slot].planes[2 + j];
-        uint32_t full[PROG6_DW];
-        int reach = 0;
-        const int rc = compile_program(cand_masks + cand_mask_offset[k], cand_len[k], cand_modpos[k], full, &reach);
-        if (rc) return rc;
-        slice_program(full, reach + 1, programs.data() + (size_t)k * PROG6_DW);
-        width[k] = (uint8_t)reach;
-        items += c->bin_nchunks[bin];
-        if (items >= 0xFFFFFFF0ull) return fail(NM_ERANGE, "more than 2^32 (candidate, chunk) work items in one batch: send fewer candidates");
-    }
+    Staged st;
+    int rc = stage_candidates(c, {n_cand, cand_bin, {cand_len, cand_modpos, cand_mask_offset, cand_masks}}, cand_mod_slot, nullptr, false, st, no_check);
+    if (rc) return rc;
     const char *env = getenv("NM_CONTEXT_WAVE_ATOMICS");
     const size_t row = (size_t)(2 * radius + 1) * CTX_ROW;
     ContextBatch cb;
     ContextArgs &a = cb.base;
     a.radius = radius;
     a.wave_atomics = env && env[0] && env[0] != '0';
-    const int rc = export_begin(cb, c, n_cand, cand_bin, width.data(),
-                                {{&a.cand_planes, planes.data(), planes.size() * 8}, {&a.programs, programs.data(), programs.size() * 4}},
-                                {{&a.states, (size_t)n_cand * 48}, {&a.table, (size_t)n_cand * row * 8}}, context_kernels, false);
+    rc = export_begin(cb, c, n_cand, cand_bin, st.width.data(), st.programs, {{&a.cand_planes, st.planes.data(), st.planes.size() * 8}},
+                      {{&a.states, (size_t)n_cand * 48}, {&a.table, (size_t)n_cand * row * 8}}, context_kernels, false);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(cand_states, a.states, (size_t)n_cand * 48, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(counts, a.table, (size_t)n_cand * row * 8, hipMemcpyDeviceToHost, c->stream));

@@ -23,7 +23,6 @@ struct CovArgs : ExportArgs {
     const uint32_t *set_cand0;           // [n_sets + 1] first candidate of a set
     const unsigned long long *set_planes;    // [n_sets][4] MP UP MM UM of the set's mod slot
     const uint32_t *cand_row0;           // first row of a candidate in the (candidate, contig) table
-    const uint32_t *programs;            // [n_cand][PROG6_DW] sliced to the width of the candidate's SET
     unsigned long long *set_table;       // count pass: [row][10]
     unsigned long long *cand_table;      // count pass: [row][4]
 };
@@ -45,7 +44,7 @@ __global__ __launch_bounds__(256) void coverage_kernel(CovArgs a) {
 #pragma unroll
     for (int t = 0; t < T_WORDS; ++t) anyf[t] = anyr[t] = multif[t] = multir[t] = 0u;
     for (uint32_t k = c0; k < c1; ++k) {                                // wave-uniform
-        uint32_t af[T_WORDS], ar[T_WORDS];
+        uint32_t af[T_WORDS], ar[T_WORDS];                              // (written out, not walk_strands: profiles/r19/export_prologue.md)
 #pragma unroll
         for (int t = 0; t < T_WORDS; ++t) af[t] = ar[t] = 0xFFFFFFFFu;
         const cu32p prog = (cu32p)(a.programs + (size_t)k * PROG6_DW);
@@ -138,25 +137,23 @@ int coverage_begin(CovBatch &cb, nm_ctx *c, uint32_t n_sets, const uint32_t *set
     std::vector<uint32_t> srow0(n_sets, 0), crow0(n_cand, 0), programs((size_t)n_cand * PROG6_DW, 0);
     std::vector<unsigned long long> planes((size_t)n_sets * 4, 0);
     std::vector<uint8_t> set_width(n_sets, 0);
+    const Motifs motifs{cand_len, cand_modpos, cand_mask_offset, cand_masks};
     uint64_t items = 0, srows = 0, crows = 0;
     for (uint32_t s = 0; s < n_sets; ++s) {
-        const uint32_t slot = set_mod_slot[s], bin = set_bin[s];
-        if (slot >= NM_MAX_MOD_SLOTS || !c->slots[slot].present || !c->slots[slot].planes[2])
-            return fail(NM_ESTATE, "set %u uses mod slot %u with no pileup uploaded", s, slot);
-        if (bin >= c->n_bins) return fail(NM_EINVAL, "set %u: bin %u >= n_bins %u", s, bin, c->n_bins);
+        const uint32_t bin = set_bin[s];
+        if (bin >= c->n_bins) return fail(NM_EINVAL, "set %u: set_bin %u >= n_bins %u", s, bin, c->n_bins);
+        int rc = slot_state_planes(c, "set_mod_slot", s, set_mod_slot[s], planes.data() + (size_t)s * 4);
+        if (rc) return rc;
         const uint32_t ncontigs = c->bin_ncontigs[bin];
-        // the set's width = the reach class of its widest candidate; every program of the set is sliced to it
+        // the set's width = the reach class of its widest candidate; every program of the set is sliced to THAT width, not to its own
         uint32_t full[PROG6_DW];
-        int width = 0;
+        int width = 0, reach = 0;
         for (uint32_t k = set_cand_offset[s]; k < set_cand_offset[s + 1]; ++k) {
-            int reach = 0;
-            const int rc = compile_program(cand_masks + cand_mask_offset[k], cand_len[k], cand_modpos[k], full, &reach);
-            if (rc) return rc;
+            if ((rc = compile_motif(motifs, k, full, &reach))) return rc;
             width = std::max(width, reach);
         }
         for (uint32_t k = set_cand_offset[s]; k < set_cand_offset[s + 1]; ++k) {
-            int reach = 0;
-            (void)compile_program(cand_masks + cand_mask_offset[k], cand_len[k], cand_modpos[k], full, &reach);
+            (void)compile_motif(motifs, k, full, &reach);
             slice_program(full, width + 1, programs.data() + (size_t)k * PROG6_DW);
             if (tables && (cand_row_offset[k + 1] < cand_row_offset[k] || cand_row_offset[k + 1] - cand_row_offset[k] < ncontigs))
                 return fail(NM_EINVAL, "candidate %u: cand_row_offset gives fewer rows than the %u resident contigs of bin %u (or descends)", k, ncontigs, bin);
@@ -169,18 +166,16 @@ int coverage_begin(CovBatch &cb, nm_ctx *c, uint32_t n_sets, const uint32_t *set
         srow0[s] = (uint32_t)(tables ? set_row_offset[s] : srows);
         srows = tables ? set_row_offset[s + 1] : srows + ncontigs;
         if (srows >= 0xFFFFFFFFull) return fail(NM_ERANGE, "more than 2^32 (set, contig) rows in one call");
-        for (int j = 0; j < 4; ++j) planes[(size_t)s * 4 + j] = (unsigned long long)(uintptr_t)c->slots[slot].planes[2 + j];
         set_width[s] = (uint8_t)width;
         items += c->bin_nchunks[bin];
         if (items >= 0xFFFFFFF0ull) return fail(NM_ERANGE, "more than 2^32 (set, chunk) work items in one call: send fewer sets");
     }
     CovArgs &a = cb.base;
-    return export_begin(cb, c, n_sets, set_bin, set_width.data(),
+    return export_begin(cb, c, n_sets, set_bin, set_width.data(), programs,
                         {{&a.set_row0, srow0.data(), srow0.size() * 4},
                          {&a.set_cand0, set_cand_offset, (size_t)(n_sets + 1) * 4},
                          {&a.cand_row0, crow0.data(), crow0.size() * 4},
-                         {&a.set_planes, planes.data(), planes.size() * 8},
-                         {&a.programs, programs.data(), programs.size() * 4}},
+                         {&a.set_planes, planes.data(), planes.size() * 8}},
                         {{&a.set_table, (size_t)srows * 80}, {&a.cand_table, (size_t)crows * 32}}, coverage_kernels<false>, with_scan);
 }
 

@@ -1,14 +1,26 @@
-// The scaffold the four record exports share (nmsites.hip, nmcoverage.hip, nmcompare.hip, nmstrands.hip; included by nothing else).  Each of them
-// hands out one wave per work item = (owner, chunk of the owner's bin) — an owner is a candidate (sites, compare) or a set of
-// candidates (coverage) — and runs the same three steps:
+// The scaffold the eight export units share; included by them and by nothing else.  Each hands out one wave per work item = (owner,
+// chunk of the owner's bin) — an owner is a candidate, in nmcoverage.hip a set of candidates — and runs up to three steps:
 //   count  the unit's kernel writes the number of records of every work item into the item table (and its own count tables)
 //   scan   one device-wide exclusive prefix (rocPRIM) over the work items, which are numbered in (owner, contig rank, chunk)
 //          order: that IS the order of the output, so nothing is sorted; a gather picks every owner's first rank
 //   fill   the unit's kernel computes its masks again and every record is written at its rank; work items whose ranks miss the
 //          caller's window of records are skipped before anything is loaded
 // Owners of different width (word-groups G = 1, 2, 3 either side of the modified base) run in one launch per width and pass: at
-// most 3 + 1 + 1 + 3 launches whatever a call holds.  What a unit keeps is what differs: its validation, how a work item's
-// positions are classified and counted, which of them become records, and the records' codes.
+// most 3 + 1 + 1 + 3 launches whatever a call holds.
+//   all three steps (records): nmsites.hip, nmcoverage.hip, nmcompare.hip, nmstrands.hip — export_begin(with_scan) + export_window
+//   the count step only (tables): nmprofile.hip, nmtracks.hip, nmfractions.hip, nmcontext.hip — export_begin alone
+// Two more pieces belong to every unit and are owned by none:
+//   stage_candidates  the host loop over a call's candidates: programs, widths, the work-item count and, on request, the state-plane
+//                     addresses of a per-candidate mod slot and the row prefix of a (candidate, contig) table.  Its refusals come in ONE
+//                     order — bin, the unit's own check, program, rows, work items — so a candidate wrong in two ways is refused the
+//                     same way by every entry point.  (nmcoverage.hip stages sets and uses compile_motif / slot_state_planes.)
+//   find_occurrences  the kernel prologue: the chunk and the state words loaded, the tile expanded, one walk per strand into fresh
+//                     accumulators (walk_strands).  A free function with reference out-parameters: as a struct with members it costs
+//                     4 - 5 VGPRs and a wave per SIMD at G = 2.  compare, tracks and context call it, fractions walk_strands;
+//                     sites_kernel, strands_kernel, coverage_kernel and profile_kernel keep the lines written out, because through
+//                     the helper they allocated other registers or measured about 1 % slower (profiles/r19/export_prologue.md).
+// What a unit keeps is what differs: its own arguments and checks, how a work item's occurrences are classified and reduced, which
+// of them become records, and the records' codes.
 #pragma once
 #include <rocprim/device/device_scan.hpp>
 
@@ -30,6 +42,8 @@ struct ExportArgs {
     unsigned long long first, capacity;  // fill pass: the window of ranks that is written
     uint32_t *out_contig, *out_pos;
     uint8_t *out_code;
+    // (keep `programs` the last member: profile_kernel's arguments then lie as they did when it was ProfileArgs' first, and so does its code)
+    const uint32_t *programs;            // [n_cand][PROG6_DW] sliced to the width the candidate runs at
 };
 
 struct WorkItem {                        // wave-uniform
@@ -37,20 +51,26 @@ struct WorkItem {                        // wave-uniform
     unsigned long long off0;             // fill pass: rank of the item's first record
 };
 
-// The work item of this wave; false when it has none (past the end, or FILL and no rank of the item is in the window).
-template <bool FILL>
-__device__ __forceinline__ bool locate_item(const ExportArgs &a, WorkItem &w) {
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t it = blockIdx.x * 4 + wave;                          // wave-uniform from here on
-    if (it >= a.n_items) return false;
-    // the owner this work item belongs to: last entry of the prefix that is <= it (scalar loads, scalar control flow)
+// index into cls_owner of the owner of work item `it` of this launch: the last entry of the prefix that is <= it (scalar loads,
+// scalar control flow)
+__device__ __forceinline__ uint32_t class_slot(const ExportArgs &a, uint32_t it) {
     const cu32p item0 = (cu32p)a.cls_item0;
     uint32_t lo = 0, hi = a.n_cls;
     while (hi - lo > 1) {
         const uint32_t mid = (lo + hi) >> 1;
         if (item0[mid] <= it) lo = mid; else hi = mid;
     }
-    const uint32_t ck = it - item0[lo];
+    return lo;
+}
+
+// The work item of this wave; false when it has none (past the end, or FILL and no rank of the item is in the window).
+template <bool FILL>
+__device__ __forceinline__ bool locate_item(const ExportArgs &a, WorkItem &w) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t it = blockIdx.x * 4 + wave;                          // wave-uniform from here on
+    if (it >= a.n_items) return false;
+    const uint32_t lo = class_slot(a, it);
+    const uint32_t ck = it - ((cu32p)a.cls_item0)[lo];
     w.owner = ((cu32p)a.cls_owner)[lo];
     w.item = ((cu32p)a.owner_item0)[w.owner] + ck;
     w.chunk = ((cu32p)a.owner_chunk0)[w.owner] + ck;
@@ -75,11 +95,49 @@ __device__ __forceinline__ StatePlanes slot_planes(const unsigned long long *pl)
     return s;
 }
 
+// both strands' occurrences of one program in the tile, into fresh accumulators
+template <class K>
+__device__ __forceinline__ void walk_strands(const uint32_t *program, const Tile<K> &tile, uint32_t (&af)[T_WORDS], uint32_t (&ar)[T_WORDS]) {
+#pragma unroll
+    for (int t = 0; t < T_WORDS; ++t) af[t] = ar[t] = 0xFFFFFFFFu;
+    const cu32p prog = (cu32p)program;
+    eval_strand<K>(prog, tile, af);
+    eval_strand<K>(prog + K::PDW, tile, ar);
+}
+
+// The prologue of a work item: its chunk and the state words of `stp` loaded, the tile expanded, the owner's occurrences on '+' (af)
+// and '-' (ar).  (Out-parameters, not members of a result: see the head of this file.)
+template <class K>
+__device__ __forceinline__ void find_occurrences(const ExportArgs &a, const WorkItem &w, const StatePlanes (&stp)[K::NS], int lane, RawChunk<K> &raw,
+                                                 Tile<K> &tile, uint32_t (&af)[T_WORDS], uint32_t (&ar)[T_WORDS]) {
+    raw.load(a.seq, stp, w.chunk, lane);
+    tile.expand(raw);
+    walk_strands<K>(a.programs + (size_t)w.owner * PROG6_DW, tile, af, ar);
+}
+
+// word t of a plane's T_WORDS + 2 words (the lane's own and one either side) seen `sh` positions further along '+': UP = sh >= 0
+// (bits = sh), else bits = 32 + sh
+template <bool UP>
+__device__ __forceinline__ uint32_t shifted(const uint32_t (&w)[T_WORDS + 2], int t, uint32_t bits) {
+    return UP ? alignbit(w[t + 2], w[t + 1], bits) : alignbit(w[t + 1], w[t], bits);
+}
+
 // the three disjoint states of one strand's word in one slot (a position called both ways is methylated)
 struct States {
     uint32_t s[3];
     __device__ __forceinline__ States(uint32_t m, uint32_t u) : s{m, u & ~m, ~(m | u)} {}
 };
+
+// the occurrences af ('+') and ar ('-') of word t by the state of their own base in the slot's words s = MP UP MM UM: f / r [0] mod,
+// [1] nomod, [2] nocall
+__device__ __forceinline__ void split_states(const uint32_t (&s)[4][T_WORDS], int t, uint32_t af, uint32_t ar, uint32_t (&f)[3], uint32_t (&r)[3]) {
+    const States sf(s[0][t], s[1][t]), sr(s[2][t], s[3][t]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        f[i] = af & sf.s[i];
+        r[i] = ar & sr.s[i];
+    }
+}
 
 // the occurrences of `acc` whose transition is in `set`
 __device__ __forceinline__ uint32_t pick9(uint32_t set, uint32_t acc, const States &a, const States &b) {
@@ -206,13 +264,85 @@ struct ExportBatch {
     }
 };
 
+// The motif arguments of an entry point and, with their number and bins, its candidates (include/nmscan.h: as nm_score_batch takes them).
+struct Motifs {
+    const uint8_t *len, *modpos;
+    const uint32_t *mask_offset;
+    const uint8_t *masks;
+};
+struct Candidates {
+    uint32_t n;
+    const uint32_t *bin;
+    Motifs motifs;
+};
+
+// The addresses of MP UP MM UM of a mod slot, for slot_planes; `arg`[i] is where the caller named the slot.
+inline int slot_state_planes(const nm_ctx *c, const char *arg, uint32_t i, uint32_t slot, unsigned long long *out) {
+    if (slot >= NM_MAX_MOD_SLOTS || !c->slots[slot].present || !c->slots[slot].planes[2])
+        return fail(NM_ESTATE, "%s[%u]: no pileup uploaded in mod slot %u", arg, i, slot);
+    for (int j = 0; j < 4; ++j) out[j] = (unsigned long long)(uintptr_t)c->slots[slot].planes[2 + j];
+    return NM_OK;
+}
+
+// Motif k compiled into the six-group program full[PROG6_DW]; *reach: its width class (slice_program cuts it to a width).
+inline int compile_motif(const Motifs &m, uint32_t k, uint32_t *full, int *reach) {
+    return compile_program(m.masks + m.mask_offset[k], m.len[k], m.modpos[k], full, reach);
+}
+
+// What stage_candidates leaves for export_begin and the unit's uploads.
+struct Staged {
+    std::vector<uint32_t> programs, row0;    // [n][PROG6_DW]; first row of a candidate (zeros without rows)
+    std::vector<unsigned long long> planes;  // [n][4] MP UP MM UM of cand_mod_slot (empty without it)
+    std::vector<uint8_t> width;
+    uint64_t rows = 0;
+};
+
+inline int no_check(uint32_t, uint32_t, uint64_t &) { return NM_OK; }
+
+// The per-candidate staging of a call, every refusal in one order: bin, the mod slot (mod_slot != NULL: the call has a cand_mod_slot
+// argument), check(k, bin, need) — the unit's own; `need` = rows the candidate takes, preset to the resident contigs of its bin —,
+// program, rows, work items.  Rows: from the caller's row_offset, else (lay_rows) laid out here back to back, else none.
+template <class Check>
+int stage_candidates(const nm_ctx *c, const Candidates &cd, const uint8_t *mod_slot, const uint64_t *row_offset, bool lay_rows, Staged &st, Check check) {
+    st.programs.assign((size_t)cd.n * PROG6_DW, 0);
+    st.row0.assign(cd.n, 0);
+    st.planes.assign(mod_slot ? (size_t)cd.n * 4 : 0, 0);
+    st.width.assign(cd.n, 0);
+    uint64_t items = 0;
+    for (uint32_t k = 0; k < cd.n; ++k) {
+        const uint32_t bin = cd.bin[k];
+        if (bin >= c->n_bins) return fail(NM_EINVAL, "candidate %u: cand_bin %u >= n_bins %u", k, bin, c->n_bins);
+        uint64_t need = c->bin_ncontigs[bin];
+        uint32_t full[PROG6_DW];
+        int reach = 0;
+        int rc = mod_slot ? slot_state_planes(c, "cand_mod_slot", k, mod_slot[k], st.planes.data() + (size_t)k * 4) : NM_OK;
+        if (!rc) rc = check(k, bin, need);
+        if (!rc) rc = compile_motif(cd.motifs, k, full, &reach);
+        if (rc) return rc;
+        slice_program(full, reach + 1, st.programs.data() + (size_t)k * PROG6_DW);
+        st.width[k] = (uint8_t)reach;
+        if (row_offset || lay_rows) {
+            const uint64_t r0 = row_offset ? row_offset[k] : st.rows, r1 = row_offset ? row_offset[k + 1] : st.rows + need;
+            if (r1 < r0 || r1 - r0 < need)
+                return fail(NM_EINVAL, "candidate %u: row_offset gives %llu rows, bin %u takes %llu", k, (unsigned long long)(r1 - r0), bin, (unsigned long long)need);
+            if (r1 >= 0xFFFFFFFFull) return fail(NM_ERANGE, "more than 2^32 rows in one batch: send fewer candidates");
+            st.row0[k] = (uint32_t)r0;
+            st.rows = r1;
+        }
+        items += c->bin_nchunks[bin];
+        if (items >= 0xFFFFFFF0ull) return fail(NM_ERANGE, "more than 2^32 (candidate, chunk) work items in one batch: send fewer candidates");
+    }
+    return NM_OK;
+}
+
 // Stage a validated call and enqueue its count pass (and, with_scan, the prefix + gather).  owner_bin / owner_width: per owner its
-// bin and width class 0..2; the work items (one per chunk of the bin) must number less than 2^32 in all.  uploads / reserved: the
-// unit's own tables, wired into eb.base before the count pass runs; eb.base holds whatever else the unit has set.
+// bin and width class 0..2; the work items (one per chunk of the bin) must number less than 2^32 in all.  programs: of every
+// candidate; uploads / reserved: the unit's own tables, wired into eb.base before the count pass runs; eb.base holds whatever else
+// the unit has set.
 template <class Args>
 int export_begin(ExportBatch<Args> &eb, nm_ctx *c, uint32_t n_owners, const uint32_t *owner_bin, const uint8_t *owner_width,
-                 const std::vector<ExportTable> &uploads, const std::vector<ExportTable> &reserved, ExportKernels<Args> &count_kernels,
-                 bool with_scan) {
+                 const std::vector<uint32_t> &programs, const std::vector<ExportTable> &uploads, const std::vector<ExportTable> &reserved,
+                 ExportKernels<Args> &count_kernels, bool with_scan) {
     std::vector<uint32_t> item0(n_owners + 1, 0), chunk0(n_owners, 0), cls_owner[3], cls_item0[3];
     uint32_t items = 0;
     for (uint32_t k = 0; k < n_owners; ++k) {                             // reach-class lists with class-local prefixes of the chunk counts
@@ -249,6 +379,7 @@ int export_begin(ExportBatch<Args> &eb, nm_ctx *c, uint32_t n_owners, const uint
         up.push_back({&eb.cls_owner[g], cls_owner[g].data(), cls_owner[g].size() * 4});
         up.push_back({&eb.cls_item0[g], cls_item0[g].data(), cls_item0[g].size() * 4});
     }
+    up.push_back({&a.programs, programs.data(), programs.size() * 4});
     std::vector<ExportTable> zeroed = {{&a.item_cnt, ((size_t)items + 1) * 8}};
     up.insert(up.end(), uploads.begin(), uploads.end());
     zeroed.insert(zeroed.end(), reserved.begin(), reserved.end());

@@ -32,7 +32,6 @@ struct FractionsArgs : ExportArgs {
     const unsigned long long *cand_planes;   // [n_cand][2] presence planes P+ P- of the candidate's read-statistics slot
     const uint32_t *cand_slot;               // [n_cand] that slot: the index into rs
     const RsSlot *rs;                        // [NM_MAX_MOD_SLOTS]
-    const uint32_t *programs;                // [n_cand][PROG6_DW] sliced to the candidate's width
     uint32_t n_bins;                         // NM_FRACTIONS_MIN_BINS..NM_FRACTIONS_MAX_BINS
     uint32_t n_rows;                         // rows of the table
     unsigned long long *table;               // [n_rows][2][n_bins + NM_FRACTIONS_EXTRA]
@@ -54,16 +53,13 @@ __global__ __launch_bounds__(256) void fractions_kernel(FractionsArgs a) {
     const unsigned long long *pl = a.cand_planes + (size_t)k * 2;
     const uint32_t *Pp = reinterpret_cast<const uint32_t *>(pl[0]), *Pm = reinterpret_cast<const uint32_t *>(pl[1]);
     const StatePlanes stp[1] = {StatePlanes{nullptr, nullptr, Pp, Pp, Pm, Pm}};
+    // (find_occurrences in its two parts: in one piece the kernel allocates 77 VGPRs for 79 at G = 1, profiles/r19/export_prologue.md)
     RawChunk<K> raw;
     raw.load(a.seq, stp, w.chunk, lane);
     Tile<K> tile;
     tile.expand(raw);
     uint32_t acc[2][T_WORDS];
-#pragma unroll
-    for (int t = 0; t < T_WORDS; ++t) acc[0][t] = acc[1][t] = 0xFFFFFFFFu;
-    const cu32p prog = (cu32p)(a.programs + (size_t)k * PROG6_DW);
-    eval_strand<K>(prog, tile, acc[0]);
-    eval_strand<K>(prog + K::PDW, tile, acc[1]);
+    walk_strands<K>(a.programs + (size_t)k * PROG6_DW, tile, acc[0], acc[1]);
     uint32_t any = 0;
 #pragma unroll
     for (int t = 0; t < T_WORDS; ++t) any |= acc[0][t] | acc[1][t];
@@ -139,47 +135,37 @@ int nm_motif_fractions_count(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bi
     if (!c) return fail(NM_EINVAL, "ctx is NULL");
     if (n_cand == 0) return NM_OK;
     if (!c->dH) return fail(NM_ESTATE, "nm_upload_contigs has not been called");
-    std::vector<uint32_t> row0(n_cand, 0), slots(n_cand, 0), programs((size_t)n_cand * PROG6_DW, 0);
+    std::vector<uint32_t> slots(n_cand, 0);
     std::vector<unsigned long long> planes((size_t)n_cand * 2, 0);
-    std::vector<uint8_t> width(n_cand, 0);
     std::vector<RsSlot> rs(NM_MAX_MOD_SLOTS, RsSlot{});
     const size_t words = plane_words(c);
-    uint64_t items = 0, rows = 0;
-    for (uint32_t k = 0; k < n_cand; ++k) {
-        const uint32_t slot = cand_rs_slot[k], bin = cand_bin[k];
-        if (bin >= c->n_bins) return fail(NM_EINVAL, "candidate %u: cand_bin %u >= n_bins %u", k, bin, c->n_bins);
-        if (slot >= NM_MAX_MOD_SLOTS || !c->readstats[slot].present)
-            return fail(NM_ESTATE, "candidate %u: read-statistics slot %u holds no pileup (nm_readstats_upload)", k, slot);
-        const ReadStats &r = c->readstats[slot];
-        uint32_t full[PROG6_DW];
-        int reach = 0;
-        const int rc = compile_program(cand_masks + cand_mask_offset[k], cand_len[k], cand_modpos[k], full, &reach);
-        if (rc) return rc;
-        slice_program(full, reach + 1, programs.data() + (size_t)k * PROG6_DW);
-        planes[(size_t)k * 2] = (unsigned long long)(uintptr_t)r.planes;
-        planes[(size_t)k * 2 + 1] = (unsigned long long)(uintptr_t)(r.planes + words);
-        rs[slot] = RsSlot{{r.rank[0], r.rank[1]}, {r.base[0], r.base[1]}, {r.val[0], r.val[1]}};
-        slots[k] = slot;
-        row0[k] = (uint32_t)rows;
-        width[k] = (uint8_t)reach;
-        rows += c->bin_ncontigs[bin];
-        if (rows >= 0xFFFFFFFFull) return fail(NM_ERANGE, "more than 2^32 (candidate, contig) rows in one batch: send fewer candidates");
-        items += c->bin_nchunks[bin];
-        if (items >= 0xFFFFFFF0ull) return fail(NM_ERANGE, "more than 2^32 (candidate, chunk) work items in one batch: send fewer candidates");
-    }
+    Staged st;
+    int rc = stage_candidates(c, {n_cand, cand_bin, {cand_len, cand_modpos, cand_mask_offset, cand_masks}}, nullptr, nullptr, true, st,
+                              [&](uint32_t k, uint32_t, uint64_t &) {                          // the candidate's read-statistics slot
+                                  const uint32_t slot = cand_rs_slot[k];
+                                  if (slot >= NM_MAX_MOD_SLOTS || !c->readstats[slot].present)
+                                      return fail(NM_ESTATE, "candidate %u: read-statistics slot %u holds no pileup (nm_readstats_upload)", k, slot);
+                                  const ReadStats &r = c->readstats[slot];
+                                  planes[(size_t)k * 2] = (unsigned long long)(uintptr_t)r.planes;
+                                  planes[(size_t)k * 2 + 1] = (unsigned long long)(uintptr_t)(r.planes + words);
+                                  rs[slot] = RsSlot{{r.rank[0], r.rank[1]}, {r.base[0], r.base[1]}, {r.val[0], r.val[1]}};
+                                  slots[k] = slot;
+                                  return (int)NM_OK;
+                              });
+    if (rc) return rc;
+    const uint64_t rows = st.rows;
     if (rows == 0) return NM_OK;                                          // every candidate in a bin without a contig
     const size_t row_bytes = (size_t)2 * (n_bins + NM_FRACTIONS_EXTRA) * 8;
     FractionsBatch fb;
     FractionsArgs &a = fb.base;
     a.n_bins = n_bins;
     a.n_rows = (uint32_t)rows;
-    const int rc = export_begin(fb, c, n_cand, cand_bin, width.data(),
-                                {{&a.cand_row0, row0.data(), row0.size() * 4},
-                                 {&a.cand_planes, planes.data(), planes.size() * 8},
-                                 {&a.cand_slot, slots.data(), slots.size() * 4},
-                                 {&a.rs, rs.data(), rs.size() * sizeof(RsSlot)},
-                                 {&a.programs, programs.data(), programs.size() * 4}},
-                                {{&a.table, (size_t)rows * row_bytes}}, fractions_kernels, false);
+    rc = export_begin(fb, c, n_cand, cand_bin, st.width.data(), st.programs,
+                      {{&a.cand_row0, st.row0.data(), st.row0.size() * 4},
+                       {&a.cand_planes, planes.data(), planes.size() * 8},
+                       {&a.cand_slot, slots.data(), slots.size() * 4},
+                       {&a.rs, rs.data(), rs.size() * sizeof(RsSlot)}},
+                      {{&a.table, (size_t)rows * row_bytes}}, fractions_kernels, false);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(counts, a.table, (size_t)rows * row_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

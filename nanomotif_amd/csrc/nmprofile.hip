@@ -24,7 +24,6 @@ using namespace nmdetail;
 namespace {
 
 struct ProfileArgs : ExportArgs {
-    const uint32_t *programs;                // [n_cand][PROG6_DW] sliced to the candidate's width
     const unsigned long long *target_planes; // [n_targets][4] MP UP MM UM
     const uint32_t *target_base;             // per target 0: canonical base A, 1: C (a dword each: scalar loads)
     uint32_t n_targets, radius;
@@ -42,12 +41,6 @@ struct HaloWords {
         w[T_WORDS + 1] = plane[base + T_WORDS];
     }
 };
-
-// word t of a plane seen `sh` positions further along '+': UP = sh >= 0 (bits = sh), else bits = 32 + sh
-template <bool UP>
-__device__ __forceinline__ uint32_t shifted(const uint32_t (&w)[T_WORDS + 2], int t, uint32_t bits) {
-    return UP ? alignbit(w[t + 2], w[t + 1], bits) : alignbit(w[t + 1], w[t], bits);
-}
 
 // the three counted classes of the probes of `acc` in (m, u, letter): mod, nomod, nocall
 __device__ __forceinline__ void count3(uint32_t acc, uint32_t m, uint32_t u, uint32_t letter, uint32_t &c0, uint32_t &c1, uint32_t &c2) {
@@ -102,6 +95,8 @@ __global__ __launch_bounds__(256) void profile_kernel(ProfileArgs a) {
     if (!locate_item<false>(a, w)) return;
     const uint32_t k = w.owner;
     const StatePlanes stp[1] = {slot_planes(a.target_planes)};           // RawChunk wants a slot: its state words are not used here
+    // (the prologue written out, not find_occurrences: through the helper the kernel has the same registers and 7 more instructions, and
+    // took 0.8 - 1.2 % longer in four of four runs against the parent, beyond the parent's own spread: profiles/r19/export_prologue.md)
     RawChunk<K> raw;
     raw.load(a.seq, stp, w.chunk, lane);
     Tile<K> tile;
@@ -175,38 +170,23 @@ int nm_motif_profile_count(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin,
     std::vector<uint32_t> tbase(n_targets, 0);
     for (uint32_t t = 0; t < n_targets; ++t) {
         const uint32_t slot = target_slot[t];
-        if (slot >= NM_MAX_MOD_SLOTS || !c->slots[slot].present || !c->slots[slot].planes[2])
-            return fail(NM_ESTATE, "target_slot[%u] = %u: no pileup uploaded in that mod slot", t, slot);
+        const int rc = slot_state_planes(c, "target_slot", t, slot, planes.data() + (size_t)t * 4);
+        if (rc) return rc;
         const uint8_t can = c->slots[slot].canonical;
         if (can != 'A' && can != 'C') return fail(NM_ESTATE, "target_slot[%u] = %u: canonical base %u is neither A nor C", t, slot, (unsigned)can);
-        for (int j = 0; j < 4; ++j) planes[(size_t)t * 4 + j] = (unsigned long long)(uintptr_t)c->slots[slot].planes[2 + j];
         tbase[t] = can == 'C';
     }
-    std::vector<uint32_t> programs((size_t)n_cand * PROG6_DW, 0);
-    std::vector<uint8_t> width(n_cand, 0);
-    uint64_t items = 0;
-    for (uint32_t k = 0; k < n_cand; ++k) {
-        const uint32_t bin = cand_bin[k];
-        if (bin >= c->n_bins) return fail(NM_EINVAL, "candidate %u: cand_bin %u >= n_bins %u", k, bin, c->n_bins);
-        uint32_t full[PROG6_DW];
-        int reach = 0;
-        const int rc = compile_program(cand_masks + cand_mask_offset[k], cand_len[k], cand_modpos[k], full, &reach);
-        if (rc) return rc;
-        slice_program(full, reach + 1, programs.data() + (size_t)k * PROG6_DW);
-        width[k] = (uint8_t)reach;
-        items += c->bin_nchunks[bin];
-        if (items >= 0xFFFFFFF0ull) return fail(NM_ERANGE, "more than 2^32 (candidate, chunk) work items in one batch: send fewer candidates");
-    }
+    Staged st;
+    int rc = stage_candidates(c, {n_cand, cand_bin, {cand_len, cand_modpos, cand_mask_offset, cand_masks}}, nullptr, nullptr, false, st, no_check);
+    if (rc) return rc;
     const size_t row = (size_t)n_targets * (2 * radius + 1) * 12;
     ProfileBatch pb;
     ProfileArgs &a = pb.base;
     a.n_targets = n_targets;
     a.radius = radius;
-    const int rc = export_begin(pb, c, n_cand, cand_bin, width.data(),
-                                {{&a.programs, programs.data(), programs.size() * 4},
-                                 {&a.target_planes, planes.data(), planes.size() * 8},
-                                 {&a.target_base, tbase.data(), tbase.size() * 4}},
-                                {{&a.sites, (size_t)n_cand * 16}, {&a.table, (size_t)n_cand * row * 8}}, profile_kernels, false);
+    rc = export_begin(pb, c, n_cand, cand_bin, st.width.data(), st.programs,
+                      {{&a.target_planes, planes.data(), planes.size() * 8}, {&a.target_base, tbase.data(), tbase.size() * 4}},
+                      {{&a.sites, (size_t)n_cand * 16}, {&a.table, (size_t)n_cand * row * 8}}, profile_kernels, false);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(cand_sites, a.sites, (size_t)n_cand * 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(counts, a.table, (size_t)n_cand * row * 8, hipMemcpyDeviceToHost, c->stream));

@@ -17,7 +17,6 @@ namespace {
 struct SitesArgs : ExportArgs {
     const uint32_t *cand_row0;           // first row of the candidate in the (candidate, contig) table
     const unsigned long long *cand_planes;   // [n_cand][4] MP UP MM UM of the candidate's mod slot
-    const uint32_t *programs;            // [n_cand][PROG6_DW] sliced to the candidate's width
     uint32_t state_set;                  // NM_SITES_MOD | NM_SITES_NOMOD | NM_SITES_NOCALL
     unsigned long long *table;           // count pass: [row][6], may be NULL
 };
@@ -26,6 +25,9 @@ __device__ __forceinline__ uint32_t pick(uint32_t set, uint32_t m, uint32_t u, u
     return ((set & 1u) ? m : 0u) | ((set & 2u) ? u : 0u) | ((set & 4u) ? n : 0u);
 }
 
+// sites_kernel keeps its prologue and its six-way split written out (not find_occurrences / split_states of nmexport.h): through them its
+// count pass carried 4 v_mov_b32, 1 s_branch and 3 v_add3_u32 more and measured about 1 % slower than before; as written here it
+// compiles to the instructions it had (profiles/r19/export_prologue.md).
 template <int G, bool FILL>
 __global__ __launch_bounds__(256) void sites_kernel(SitesArgs a) {
     using K = Variant<G, G, false, 1, false, false>;
@@ -98,42 +100,16 @@ int sites_begin(SitesBatch &sb, nm_ctx *c, uint32_t n_cand, const uint32_t *cand
     if (!c->dH) return fail(NM_ESTATE, "nm_upload_contigs has not been called");
     if (state_set == 0 || (state_set & ~7u)) return fail(NM_EINVAL, "state_set %u: a non-empty combination of NM_SITES_MOD / NOMOD / NOCALL", state_set);
     if (row_offset && row_offset[0] != 0) return fail(NM_EINVAL, "row_offset[0] must be 0");
-    std::vector<uint32_t> row0(n_cand, 0), programs((size_t)n_cand * PROG6_DW, 0);
-    std::vector<unsigned long long> planes((size_t)n_cand * 4, 0);
-    std::vector<uint8_t> width(n_cand, 0);
-    uint64_t items = 0, rows = 0;
-    for (uint32_t k = 0; k < n_cand; ++k) {
-        const uint32_t slot = cand_mod_slot[k], bin = cand_bin[k];
-        if (slot >= NM_MAX_MOD_SLOTS || !c->slots[slot].present || !c->slots[slot].planes[2])
-            return fail(NM_ESTATE, "candidate %u uses mod slot %u with no pileup uploaded", k, slot);
-        if (bin >= c->n_bins) return fail(NM_EINVAL, "candidate %u: bin %u >= n_bins %u", k, bin, c->n_bins);
-        uint32_t full[PROG6_DW];
-        int reach = 0;
-        const int rc = compile_program(cand_masks + cand_mask_offset[k], cand_len[k], cand_modpos[k], full, &reach);
-        if (rc) return rc;
-        slice_program(full, reach + 1, programs.data() + (size_t)k * PROG6_DW);
-        for (int j = 0; j < 4; ++j) planes[(size_t)k * 4 + j] = (unsigned long long)(uintptr_t)c->slots[slot].planes[2 + j];
-        if (row_offset) {
-            if (row_offset[k + 1] < row_offset[k] || row_offset[k + 1] - row_offset[k] < c->bin_ncontigs[bin])
-                return fail(NM_EINVAL, "candidate %u: %llu rows for the %u resident contigs of bin %u", k,
-                            (unsigned long long)(row_offset[k + 1] - row_offset[k]), c->bin_ncontigs[bin], bin);
-            if (row_offset[k + 1] >= 0xFFFFFFFFull) return fail(NM_ERANGE, "more than 2^32 (candidate, contig) rows in one batch");
-            row0[k] = (uint32_t)row_offset[k];
-            rows = row_offset[k + 1];
-        }
-        width[k] = (uint8_t)reach;
-        items += c->bin_nchunks[bin];
-        if (items >= 0xFFFFFFF0ull) return fail(NM_ERANGE, "more than 2^32 (candidate, chunk) work items in one batch: send fewer candidates");
-    }
+    Staged st;
+    const int rc = stage_candidates(c, {n_cand, cand_bin, {cand_len, cand_modpos, cand_mask_offset, cand_masks}}, cand_mod_slot, row_offset, false, st, no_check);
+    if (rc) return rc;
     SitesArgs &a = sb.base;
     a.state_set = state_set;
     std::vector<ExportTable> reserved;
-    if (row_offset) reserved.push_back({&a.table, (size_t)rows * 48});
-    return export_begin(sb, c, n_cand, cand_bin, width.data(),
-                        {{&a.cand_row0, row0.data(), row0.size() * 4},
-                         {&a.cand_planes, planes.data(), planes.size() * 8},
-                         {&a.programs, programs.data(), programs.size() * 4}},
-                        reserved, sites_kernels<false>, with_scan);
+    if (row_offset) reserved.push_back({&a.table, (size_t)st.rows * 48});
+    return export_begin(sb, c, n_cand, cand_bin, st.width.data(), st.programs,
+                        {{&a.cand_row0, st.row0.data(), st.row0.size() * 4}, {&a.cand_planes, st.planes.data(), st.planes.size() * 8}}, reserved,
+                        sites_kernels<false>, with_scan);
 }
 
 }  // namespace

@@ -20,7 +20,6 @@ namespace {
 struct StrandsArgs : ExportArgs {
     const uint32_t *cand_row0;           // first row of the candidate in the (candidate, contig) table
     const unsigned long long *cand_planes;   // [n_cand][4] MP UP MM UM of the candidate's mod slot
-    const uint32_t *programs;            // [n_cand][PROG6_DW] sliced to the candidate's width
     const int32_t *cand_partner;         // partner offset d of the candidate (a dword each: a scalar load, no vector round trip before the shifted reads)
     uint32_t pair_set;                   // bit t = pair t is exported
     unsigned long long *table;           // count pass: [row][18], may be NULL
@@ -56,6 +55,8 @@ __global__ __launch_bounds__(256) void strands_kernel(StrandsArgs a) {
     qfu.load(stp[0].UM, base + (ptrdiff_t)wf);
     qrm.load(stp[0].MP, base + (ptrdiff_t)wr);
     qru.load(stp[0].UP, base + (ptrdiff_t)wr);
+    // (the prologue written out, not find_occurrences: through the helper the fill variants allocate other registers — 105 / 117 VGPRs for
+    // 106 / 119 at G = 1 / 2, 40 more instructions at G = 3 — and no trace exercises them: profiles/r19/export_prologue.md)
     RawChunk<K> raw;
     raw.load(a.seq, stp, w.chunk, lane);                                 // sequence planes, the chunk's own state words
     Tile<K> tile;
@@ -137,47 +138,24 @@ int strands_begin(StrandsBatch &sb, nm_ctx *c, uint32_t n_cand, const uint32_t *
     if (pair_set == 0 || (pair_set & ~NM_STRANDS_ALL))
         return fail(NM_EINVAL, "pair_set %u: a non-empty combination of the bits 0..8 (bit 3 * own state + partner state)", pair_set);
     if (row_offset && row_offset[0] != 0) return fail(NM_EINVAL, "row_offset[0] must be 0");
-    std::vector<uint32_t> row0(n_cand, 0), programs((size_t)n_cand * PROG6_DW, 0);
-    std::vector<unsigned long long> planes((size_t)n_cand * 4, 0);
-    std::vector<uint8_t> width(n_cand, 0);
     std::vector<int32_t> partner(cand_partner_offset, cand_partner_offset + n_cand);
-    uint64_t items = 0, rows = 0;
-    for (uint32_t k = 0; k < n_cand; ++k) {
-        const uint32_t slot = cand_mod_slot[k], bin = cand_bin[k];
-        if (slot >= NM_MAX_MOD_SLOTS || !c->slots[slot].present || !c->slots[slot].planes[2])
-            return fail(NM_ESTATE, "candidate %u uses mod slot %u with no pileup uploaded", k, slot);
-        if (bin >= c->n_bins) return fail(NM_EINVAL, "candidate %u: bin %u >= n_bins %u", k, bin, c->n_bins);
-        uint32_t full[PROG6_DW];
-        int reach = 0;
-        const int rc = compile_program(cand_masks + cand_mask_offset[k], cand_len[k], cand_modpos[k], full, &reach);
-        if (rc) return rc;
-        slice_program(full, reach + 1, programs.data() + (size_t)k * PROG6_DW);
-        // the partner lies inside the occurrence's span: inside the contig, and no further from the own base than the program reaches
-        const int at = (int)cand_modpos[k] + (int)cand_partner_offset[k];
-        if (at < 0 || at >= (int)cand_len[k])
-            return fail(NM_EINVAL, "candidate %u: partner offset %d from mod_position %u lies outside the motif of length %u", k, (int)cand_partner_offset[k],
-                        (unsigned)cand_modpos[k], (unsigned)cand_len[k]);
-        for (int j = 0; j < 4; ++j) planes[(size_t)k * 4 + j] = (unsigned long long)(uintptr_t)c->slots[slot].planes[2 + j];
-        if (row_offset) {
-            if (row_offset[k + 1] < row_offset[k] || row_offset[k + 1] - row_offset[k] < c->bin_ncontigs[bin])
-                return fail(NM_EINVAL, "candidate %u: %llu rows for the %u resident contigs of bin %u", k,
-                            (unsigned long long)(row_offset[k + 1] - row_offset[k]), c->bin_ncontigs[bin], bin);
-            if (row_offset[k + 1] >= 0xFFFFFFFFull) return fail(NM_ERANGE, "more than 2^32 (candidate, contig) rows in one batch");
-            row0[k] = (uint32_t)row_offset[k];
-            rows = row_offset[k + 1];
-        }
-        width[k] = (uint8_t)reach;
-        items += c->bin_nchunks[bin];
-        if (items >= 0xFFFFFFF0ull) return fail(NM_ERANGE, "more than 2^32 (candidate, chunk) work items in one batch: send fewer candidates");
-    }
+    Staged st;
+    const int rc = stage_candidates(c, {n_cand, cand_bin, {cand_len, cand_modpos, cand_mask_offset, cand_masks}}, cand_mod_slot, row_offset, false, st,
+                                    [&](uint32_t k, uint32_t, uint64_t &) {
+                                        // the partner lies inside the occurrence's span: inside the contig, and no further from the own base than the program reaches
+                                        const int at = (int)cand_modpos[k] + partner[k];
+                                        if (at >= 0 && at < (int)cand_len[k]) return (int)NM_OK;
+                                        return fail(NM_EINVAL, "candidate %u: partner offset %d from mod_position %u lies outside the motif of length %u", k, partner[k],
+                                                    (unsigned)cand_modpos[k], (unsigned)cand_len[k]);
+                                    });
+    if (rc) return rc;
     StrandsArgs &a = sb.base;
     a.pair_set = pair_set;
     std::vector<ExportTable> reserved;
-    if (row_offset) reserved.push_back({&a.table, (size_t)rows * 144});
-    return export_begin(sb, c, n_cand, cand_bin, width.data(),
-                        {{&a.cand_row0, row0.data(), row0.size() * 4},
-                         {&a.cand_planes, planes.data(), planes.size() * 8},
-                         {&a.programs, programs.data(), programs.size() * 4},
+    if (row_offset) reserved.push_back({&a.table, (size_t)st.rows * 144});
+    return export_begin(sb, c, n_cand, cand_bin, st.width.data(), st.programs,
+                        {{&a.cand_row0, st.row0.data(), st.row0.size() * 4},
+                         {&a.cand_planes, st.planes.data(), st.planes.size() * 8},
                          {&a.cand_partner, partner.data(), partner.size() * 4}},
                         reserved, strands_kernels<false>, with_scan);
 }

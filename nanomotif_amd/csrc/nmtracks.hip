@@ -23,7 +23,6 @@ namespace {
 struct TracksArgs : ExportArgs {
     const uint32_t *cand_row0;               // first row of the candidate in the table
     const unsigned long long *cand_planes;   // [n_cand][4] MP UP MM UM of the candidate's mod slot
-    const uint32_t *programs;                // [n_cand][PROG6_DW] sliced to the candidate's width
     const uint32_t *contig_win0;             // [n_contigs] first window of the contig, relative to the first window of its bin
     uint32_t lanes_per_window;               // window_bp / 128
     uint32_t n_rows;                         // rows of the table
@@ -39,15 +38,9 @@ __global__ __launch_bounds__(256) void tracks_kernel(TracksArgs a) {
     const uint32_t k = w.owner;
     const StatePlanes stp[1] = {slot_planes(a.cand_planes + (size_t)k * 4)};
     RawChunk<K> raw;
-    raw.load(a.seq, stp, w.chunk, lane);
     Tile<K> tile;
-    tile.expand(raw);
     uint32_t af[T_WORDS], ar[T_WORDS];
-#pragma unroll
-    for (int t = 0; t < T_WORDS; ++t) af[t] = ar[t] = 0xFFFFFFFFu;
-    const cu32p prog = (cu32p)(a.programs + (size_t)k * PROG6_DW);
-    eval_strand<K>(prog, tile, af);
-    eval_strand<K>(prog + K::PDW, tile, ar);
+    find_occurrences<K>(a, w, stp, lane, raw, tile, af, ar);
     uint32_t any = 0;
 #pragma unroll
     for (int t = 0; t < T_WORDS; ++t) any |= af[t] | ar[t];
@@ -55,9 +48,13 @@ __global__ __launch_bounds__(256) void tracks_kernel(TracksArgs a) {
     uint32_t c[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int t = 0; t < T_WORDS; ++t) {
-        const uint32_t mp = raw.s[0][0][t], up = raw.s[0][1][t] & ~mp, mm = raw.s[0][2][t], um = raw.s[0][3][t] & ~mm;
-        c[0] += __popc(af[t] & mp); c[1] += __popc(af[t] & up); c[2] += __popc(af[t] & ~(mp | up));
-        c[3] += __popc(ar[t] & mm); c[4] += __popc(ar[t] & um); c[5] += __popc(ar[t] & ~(mm | um));
+        uint32_t f[3], r[3];
+        split_states(raw.s[0], t, af[t], ar[t], f, r);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            c[i] += __popc(f[i]);
+            c[3 + i] += __popc(r[i]);
+        }
     }
     uint32_t p[3];
 #pragma unroll
@@ -150,50 +147,32 @@ int nm_motif_tracks_count(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, 
     std::vector<uint32_t> win0(c->n_contigs, 0);
     std::vector<uint64_t> bin_windows(c->n_bins, 0);
     std::vector<uint8_t> bin_done(c->n_bins, 0);
-    std::vector<uint32_t> row0(n_cand, 0), programs((size_t)n_cand * PROG6_DW, 0);
-    std::vector<unsigned long long> planes((size_t)n_cand * 4, 0);
-    std::vector<uint8_t> width(n_cand, 0);
-    uint64_t items = 0;
-    for (uint32_t k = 0; k < n_cand; ++k) {
-        const uint32_t slot = cand_mod_slot[k], bin = cand_bin[k];
-        if (bin >= c->n_bins) return fail(NM_EINVAL, "candidate %u: cand_bin %u >= n_bins %u", k, bin, c->n_bins);
-        if (slot >= NM_MAX_MOD_SLOTS || !c->slots[slot].present || !c->slots[slot].planes[2])
-            return fail(NM_ESTATE, "candidate %u uses mod slot %u with no pileup uploaded", k, slot);
-        if (!bin_done[bin]) {
-            uint64_t at = 0;
-            for (uint32_t i : contigs_of(c, bin)) {
-                if (at >= 0xFFFFFFFFull) return fail(NM_ERANGE, "more than 2^32 windows in bin %u", bin);
-                win0[i] = (uint32_t)at;
-                at += windows_of(c->contig_len[i], window_bp);
-            }
-            bin_windows[bin] = at;
-            bin_done[bin] = 1;
-        }
-        if (row_offset[k + 1] < row_offset[k] || row_offset[k + 1] - row_offset[k] < bin_windows[bin])
-            return fail(NM_EINVAL, "candidate %u: row_offset gives %llu rows for the %llu windows of bin %u", k,
-                        (unsigned long long)(row_offset[k + 1] - row_offset[k]), (unsigned long long)bin_windows[bin], bin);
-        if (row_offset[k + 1] >= 0xFFFFFFFFull) return fail(NM_ERANGE, "more than 2^32 (candidate, window) rows in one batch: send fewer candidates");
-        uint32_t full[PROG6_DW];
-        int reach = 0;
-        rc = compile_program(cand_masks + cand_mask_offset[k], cand_len[k], cand_modpos[k], full, &reach);
-        if (rc) return rc;
-        slice_program(full, reach + 1, programs.data() + (size_t)k * PROG6_DW);
-        for (int j = 0; j < 4; ++j) planes[(size_t)k * 4 + j] = (unsigned long long)(uintptr_t)c->slots[slot].planes[2 + j];
-        row0[k] = (uint32_t)row_offset[k];
-        width[k] = (uint8_t)reach;
-        items += c->bin_nchunks[bin];
-        if (items >= 0xFFFFFFF0ull) return fail(NM_ERANGE, "more than 2^32 (candidate, chunk) work items in one batch: send fewer candidates");
-    }
-    const uint64_t rows = row_offset[n_cand];
+    Staged st;
+    rc = stage_candidates(c, {n_cand, cand_bin, {cand_len, cand_modpos, cand_mask_offset, cand_masks}}, cand_mod_slot, row_offset, false, st,
+                          [&](uint32_t, uint32_t bin, uint64_t &need) {                        // a candidate takes a row per window of its bin
+                              if (!bin_done[bin]) {
+                                  uint64_t at = 0;
+                                  for (uint32_t i : contigs_of(c, bin)) {
+                                      if (at >= 0xFFFFFFFFull) return fail(NM_ERANGE, "more than 2^32 windows in bin %u", bin);
+                                      win0[i] = (uint32_t)at;
+                                      at += windows_of(c->contig_len[i], window_bp);
+                                  }
+                                  bin_windows[bin] = at;
+                                  bin_done[bin] = 1;
+                              }
+                              need = bin_windows[bin];
+                              return (int)NM_OK;
+                          });
+    if (rc) return rc;
+    const uint64_t rows = st.rows;
     if (rows == 0) return NM_OK;                                          // every candidate in a bin without a contig
     TracksBatch tb;
     TracksArgs &a = tb.base;
     a.lanes_per_window = window_bp / NM_TRACKS_MIN_WINDOW;
     a.n_rows = (uint32_t)rows;
-    rc = export_begin(tb, c, n_cand, cand_bin, width.data(),
-                      {{&a.cand_row0, row0.data(), row0.size() * 4},
-                       {&a.cand_planes, planes.data(), planes.size() * 8},
-                       {&a.programs, programs.data(), programs.size() * 4},
+    rc = export_begin(tb, c, n_cand, cand_bin, st.width.data(), st.programs,
+                      {{&a.cand_row0, st.row0.data(), st.row0.size() * 4},
+                       {&a.cand_planes, st.planes.data(), st.planes.size() * 8},
                        {&a.contig_win0, win0.data(), win0.size() * 4}},
                       {{&a.table, (size_t)rows * 24}}, tracks_kernels, false);
     if (rc) return rc;

@@ -115,6 +115,23 @@ class CandidateBatch:
     def __len__(self):
         return len(self.bins)
 
+    def slice(self, k, e):
+        """The candidates [k, e): views of the per-candidate arrays, the mask pool shared."""
+        return CandidateBatch(self.bins[k:e], self.slots[k:e], self.lens[k:e], self.modpos[k:e], self.offsets[k:e], self.masks)
+
+
+def _budget_groups(costs, limit):
+    """Consecutive owners grouped while the sum of their ``costs`` fits ``limit``; a group holds at least one owner.  Yields (k, e, sum
+    of the costs of the owners [k, e))."""
+    n, k = len(costs), 0
+    while k < n:
+        e, held = k + 1, int(costs[k])
+        while e < n and held + int(costs[e]) <= limit:
+            held += int(costs[e])
+            e += 1
+        yield k, e, held
+        k = e
+
 
 class DeviceWindowStore:
     """Window requests of the lock-step search served by the engine's window kernels (nm_win_*): same interface as
@@ -819,11 +836,15 @@ class ScanEngine:
             b._args = args
         return args
 
+    def _as_batch(self, candidates, slot_of=None) -> CandidateBatch:
+        """``candidates`` as a CandidateBatch: itself if it is one, else ``make_batch`` of the sequence."""
+        return candidates if isinstance(candidates, CandidateBatch) else self.make_batch(list(candidates), slot_of=slot_of)
+
     def score(self, candidates) -> np.ndarray:
         """int64[n, 2] = (n_mod, n_nomod) per candidate — what ``model.update`` receives (find_motifs_bin.py:1320)."""
         if not isinstance(candidates, CandidateBatch) and any(len(c[0].tokens) > MAX_REACH + 1 for c in candidates):
             return self._score_with_wide(candidates)
-        b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(candidates)
+        b = self._as_batch(candidates)
         out = np.zeros((len(b), 2), dtype=np.int64)
         if len(b):
             _lib.check(self.lib.nm_score_batch(self.ctx, *self._batch_args(b), out.ctypes.data_as(C.c_void_p)))
@@ -869,7 +890,7 @@ class ScanEngine:
         """Per-contig (n_mod, n_nomod): ``motif_model_contig`` (find_motifs_bin.py:1285-1331) for every resident contig of
         each candidate's bin in one launch (nm_score_batch_per_contig).  Returns a list, per candidate, of
         (contig names, int64[n_contigs, 2])."""
-        b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(candidates)
+        b = self._as_batch(candidates)
         names = {}
         for bid in np.unique(b.bins).tolist():
             names[bid] = self.bin_contigs(int(bid))
@@ -911,12 +932,7 @@ class ScanEngine:
         ``dtype``: the records' type, whose ``owner`` field is filled in here; ``unit``: what the library's message calls a group.
         The ctypes pointers of those arguments keep their arrays alive.  Yields (k, e, first_record, records of the group, the window's
         records)."""
-        n, k = len(totals), 0
-        while k < n:
-            e, held = k + 1, int(totals[k])
-            while e < n and held + int(totals[e]) <= limit:
-                held += int(totals[e])
-                e += 1
+        for k, e, held in _budget_groups(totals, limit):
             args = group_args(k, e)
             first = 0
             while True:
@@ -937,7 +953,6 @@ class ScanEngine:
                 first += cap
                 if first >= held:
                     break
-            k = e
 
     def _site_batches(self, windows, b: CandidateBatch, names, rows, table):
         """The windows of ``_record_windows`` over the candidates ``b`` as ``SiteBatch`` objects."""
@@ -952,7 +967,7 @@ class ScanEngine:
         """Per (candidate, contig) the six site counts (fwd mod, fwd nomod, fwd nocall, rev mod, rev nomod, rev nocall) of every
         resident contig of the candidate's bin (nm_motif_sites_count): ``score_per_contig`` split by strand, plus the occurrences
         that carry no call.  Returns a list, per candidate, of (contig names, int64[n_contigs, 6])."""
-        b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(candidates)
+        b = self._as_batch(candidates)
         names, rows, _, table = self._site_counts(b, 7)
         return [(names[int(b.bins[k])], table[int(rows[k]):int(rows[k + 1])]) for k in range(len(b))]
 
@@ -964,13 +979,13 @@ class ScanEngine:
         in the order candidate, contig (``bin_contigs`` order), position, '+' before '-'.  No batch holds more than ``max_records``
         records (default: ``SITE_BUDGET_BYTES`` = 256 MiB of device records, 9 bytes each); a candidate with more is delivered in
         several windows.  The concatenation does not depend on ``max_records``."""
-        b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(candidates)
+        b = self._as_batch(candidates)
         state_set = site_state_set(states)
         limit = self._record_limit(max_records)
         names, rows, totals, table = self._site_counts(b, state_set)
 
         def group_args(k, e):
-            sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
+            sub = b.slice(k, e)
             return (self.ctx, *self._batch_args(sub), state_set)
         windows = self._record_windows(self.lib.nm_motif_sites, group_args, totals, limit, SITE_DTYPE, "candidate", "batch")
         yield from self._site_batches(windows, b, names, rows, table)
@@ -1022,7 +1037,7 @@ class ScanEngine:
         names, rows, totals, table = self._compare_counts(b, slots_b, tset)
 
         def group_args(k, e):
-            sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
+            sub = b.slice(k, e)
             return (self.ctx, *self._compare_args(sub, np.ascontiguousarray(slots_b[k:e])), tset)
         windows = self._record_windows(self.lib.nm_motif_compare_sites, group_args, totals, limit, SITE_DTYPE, "candidate", "batch")
         yield from self._site_batches(windows, b, names, rows, table)
@@ -1066,7 +1081,7 @@ class ScanEngine:
         names, rows, totals, table = self._strands_counts(b, d, pset)
 
         def group_args(k, e):
-            sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
+            sub = b.slice(k, e)
             return (self.ctx, *self._strands_args(sub, np.ascontiguousarray(d[k:e])), pset)
         windows = self._record_windows(self.lib.nm_motif_strands_sites, group_args, totals, limit, SITE_DTYPE, "candidate", "batch")
         yield from self._site_batches(windows, b, names, rows, table)
@@ -1113,7 +1128,7 @@ class ScanEngine:
         if not 0 <= radius <= PROFILE_MAX_RADIUS:
             raise ValueError(f"radius {radius} outside 0..{PROFILE_MAX_RADIUS}")
         labels, slots = self._profile_targets(targets)
-        b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(list(candidates), slot_of=lambda mt: 0)
+        b = self._as_batch(candidates, slot_of=lambda mt: 0)
         n, nt, width = len(b), len(slots), 2 * radius + 1
         sites = np.zeros((n, 2), dtype=np.uint64)
         three = np.zeros((n, nt, width, 2, 2, 3), dtype=np.int64)
@@ -1140,7 +1155,7 @@ class ScanEngine:
         radius = int(radius)
         if not 0 <= radius <= CONTEXT_MAX_RADIUS:
             raise ValueError(f"radius {radius} outside 0..{CONTEXT_MAX_RADIUS}")
-        b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(list(candidates))
+        b = self._as_batch(candidates)
         n, width = len(b), 2 * radius + 1
         states = np.zeros((n, 2, 3), dtype=np.uint64)
         four = np.zeros((n, width, 2, 3, 4), dtype=np.int64)
@@ -1177,27 +1192,21 @@ class ScanEngine:
         limit = TRACK_BUDGET_BYTES if max_bytes is None else int(max_bytes)
         if limit < 1:
             raise ValueError("max_bytes must be at least 1")
-        b = candidates if isinstance(candidates, CandidateBatch) else self.make_batch(list(candidates))
+        b = self._as_batch(candidates)
         return self._track_groups(b, w, limit)
 
     def _track_groups(self, b: CandidateBatch, w: int, limit: int):
         bins = [int(x) for x in b.bins]
         names = {bid: self.bin_contigs(bid) for bid in sorted(set(bins))}
         prefix = {bid: self.track_windows(bid, w) for bid in names}
-        n, k = len(b), 0
-        while k < n:
-            e, held = k + 1, int(prefix[bins[k]][-1]) * TRACK_ROW_BYTES
-            while e < n and held + int(prefix[bins[e]][-1]) * TRACK_ROW_BYTES <= limit:
-                held += int(prefix[bins[e]][-1]) * TRACK_ROW_BYTES
-                e += 1
+        for k, e, _ in _budget_groups([int(prefix[bid][-1]) * TRACK_ROW_BYTES for bid in bins], limit):
             rows = np.zeros(e - k + 1, dtype=np.uint64)
             np.cumsum([int(prefix[bins[j]][-1]) for j in range(k, e)], out=rows[1:])
             table = np.zeros((max(int(rows[-1]), 1), 6), dtype=np.uint32)
-            sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
+            sub = b.slice(k, e)
             _lib.check(self.lib.nm_motif_tracks_count(self.ctx, *self._batch_args(sub), w, _ptr(rows, C.c_uint64), _ptr(table, C.c_uint32)))
             for j in range(k, e):
                 yield names[bins[j]], prefix[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
-            k = e
 
     # ------------------------------------------------------------------ read-fraction histograms at motif sites (nm_motif_fractions_count)
     def motif_fractions(self, candidates, bins=20, max_bytes=None):
@@ -1229,20 +1238,14 @@ class ScanEngine:
         names = {bid: self.bin_contigs(bid) for bid in sorted(set(bins))}
         width = nb + FRACTIONS_EXTRA
         row_bytes = 2 * width * 8
-        n, k = len(b), 0
-        while k < n:
-            e, held = k + 1, len(names[bins[k]]) * row_bytes
-            while e < n and held + len(names[bins[e]]) * row_bytes <= limit:
-                held += len(names[bins[e]]) * row_bytes
-                e += 1
+        for k, e, _ in _budget_groups([len(names[bid]) * row_bytes for bid in bins], limit):
             rows = np.zeros(e - k + 1, dtype=np.int64)
             np.cumsum([len(names[bins[j]]) for j in range(k, e)], out=rows[1:])
             table = np.zeros((max(int(rows[-1]), 1), 2, width), dtype=np.uint64)
-            sub = CandidateBatch(b.bins[k:e], b.slots[k:e], b.lens[k:e], b.modpos[k:e], b.offsets[k:e], b.masks)
+            sub = b.slice(k, e)
             _lib.check(self.lib.nm_motif_fractions_count(self.ctx, *self._batch_args(sub), nb, _ptr(table, C.c_uint64)))
             for j in range(k, e):
                 yield candidates[j], names[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
-            k = e
 
     # ------------------------------------------------------------------ coverage of a set of motifs (nm_motif_coverage_*)
     def _coverage_args(self, sets):

@@ -477,6 +477,9 @@ def test_errors_are_loud_and_leave_the_engine_usable(engine_cls):
         with pytest.raises(NmScanError) as e:                           # no such bin
             call([(Motif("GATC", 1), "a", 7)], LABELS)
         assert e.value.code == -1
+        with pytest.raises(NmScanError) as e:                           # no such bin and no pileup in a slot: the bin is refused first
+            call([(Motif("GATC", 1), "a", 7)], ("a", 5))
+        assert e.value.code == -1
         with pytest.raises(NmScanError) as e:                           # beyond the reach limit: nm_motif_sites' code
             call([(Motif("GATC", 1), "a", "b"), (far, "a", "b")], LABELS)
         assert e.value.code == sites_code

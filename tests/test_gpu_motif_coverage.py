@@ -417,6 +417,9 @@ def test_errors_are_loud_and_leave_the_engine_usable(engine_cls):
         with pytest.raises(NmScanError) as e:                           # no pileup in the slot
             call([("b", 1, [Motif("GATC", 1)])])
         assert e.value.code == -3                                       # NM_ESTATE
+        with pytest.raises(NmScanError) as e:                           # no such bin and no pileup in the slot: the bin is refused first
+            call([(7, 1, [Motif("GATC", 1)])])
+        assert e.value.code == -1
         with pytest.raises(NmScanError) as e:                           # reaches further than 95 from the modified base
             call([("b", "a", [Motif("GATC", 1), Motif("A" + "." * 100 + "T", 0)])])
         assert e.value.code == -5                                       # NM_ERANGE

@@ -375,6 +375,9 @@ def test_errors_are_loud(engine_cls):
     with pytest.raises(NmScanError) as e:
         list(eng.motif_sites(eng.make_batch([(Motif("GATC", 1), "a", 7)])))      # no such bin
     assert e.value.code == -1
+    with pytest.raises(NmScanError) as e:                               # no such bin and no pileup in the slot: the bin is refused first
+        list(eng.motif_sites(eng.make_batch([(Motif("GATC", 1), "a", 7)], slot_of=lambda mt: 5)))
+    assert e.value.code == -1
     with pytest.raises(ValueError):
         list(eng.motif_sites([(Motif("GATC", 1), "a", "b")], states=("methylated",)))
     assert eng.lib.nm_motif_sites(eng.ctx, 1, None, None, None, None, None, None, 7, 0, 0, None, None, None, None, None) == -1

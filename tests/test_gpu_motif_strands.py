@@ -229,6 +229,8 @@ def test_errors_are_loud_and_leave_the_engine_usable(engine_cls):
     for slot in (5, 8, 200):                                            # a slot without a pileup; a slot beyond the eight
         empty_slot[:] = slot
         assert count((len(bt), _ptr(bt.bins, C.c_uint32), _ptr(empty_slot, C.c_uint8)) + args[3:]) == -3, slot
+    no_bin = np.full(len(bt), 7, np.uint32)                             # no such bin and no pileup in the slot: the bin is refused first
+    assert count((len(bt), _ptr(no_bin, C.c_uint32), _ptr(empty_slot, C.c_uint8)) + args[3:]) == -1
     contig, pos, code, off, nw = np.zeros(8, np.uint32), np.zeros(8, np.uint32), np.zeros(8, np.uint8), np.zeros(2, np.uint64), C.c_uint64(0)
     sites = lambda args, pset=0x1FF, out=True: eng.lib.nm_motif_strands_sites(
         eng.ctx, *args, pset, 0, 8, *((_ptr(contig, C.c_uint32), _ptr(pos, C.c_uint32), _ptr(code, C.c_uint8)) if out else (None, None, None)), _ptr(off, C.c_uint64),
