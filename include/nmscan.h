@@ -575,6 +575,35 @@ int nm_motif_context_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bi
                            const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t radius,
                            uint64_t *cand_states, int64_t *counts);
 
+/* ---- K-MER METHYLATION: the methylation of EVERY sequence context of a bin, without a motif ------------------------------------------
+ * Reference: none (modkit and nanodisco users know the table as the k-mer table).  Every call above takes a motif; this one takes a
+ * SHAPE and counts every context of it at once: the one check on discovery that needs no motif as input.
+ *
+ * SHAPE: n_offsets = F (0 .. NM_KMER_MAX_FLANKS) strictly ascending non-zero offsets in [-NM_KMER_MAX_OFFSET, NM_KMER_MAX_OFFSET],
+ *   counted in the reading direction of the site's strand.  One shape per call.
+ * REQUEST = (bin, mod slot); X = the slot's canonical base.  SITES of every resident contig of the bin: every '+' position p that
+ *   holds X (strand 0), and every p that holds the complement of X (a site on '-', strand 1).  The letter at reading offset o is the
+ *   contig's letter at p + o for a '+' site and the complement of the letter at p - o for a '-' site.  A site's window is COMPLETE
+ *   when all F probed positions lie inside the contig and hold A, C, G or T.  Its STATE is nm_motif_sites_count's: the slot's planes
+ *   on the site's strand at p, 0 mod (a position called both ways is mod), 1 nomod, 2 nocall.
+ * totals = uint64[n_req][2 (strand)][3 (state)]: ALL sites, complete or not — the six counts nm_motif_sites_count gives the one-letter
+ *   motif X, summed over the bin's contigs.
+ * table  = uint64[n_req][4^F][3 (state)]: the COMPLETE sites, summed over strands and contigs.  The row is the base-4 number of the F
+ *   letters, the first (lowest) offset the most significant digit, A = 0, C = 1, G = 2, T = 3; F = 0: one row.  Row r is the
+ *   strand-summed row nm_motif_sites_count gives the motif spelled by the shape with r's letters, X at offset 0 and `.` in the gaps;
+ *   totals summed over strands - table summed over rows = the incomplete sites per state.  The caller's arrays need not be zeroed.
+ * One launch plus the zeroing whatever n_req is.  F <= 6: per-workgroup histogram in LDS, flushed once per run of chunks; above:
+ *   64-bit atomics into the table.  NM_KMER_GLOBAL_ATOMICS=1 forces the latter at any F, NM_KMER_RUN_CHUNKS=<1..4096> sets the chunks
+ *   per work item (both read per call; the results are the same).
+ * Refusals, in this order: NM_EINVAL for NULLs; NM_EINVAL for the shape (more than NM_KMER_MAX_FLANKS offsets, or offsets[f] that is 0,
+ *   out of range or not above offsets[f - 1]: the message names f); NM_ESTATE without an assembly; per request NM_EINVAL for a bad bin,
+ *   then NM_ESTATE for a slot without an uploaded pileup; NM_ERANGE for more than 2^32 work items.  n_req = 0 is NM_OK and touches
+ *   nothing.  A request whose bin has no resident contig gives zeros.  A refusal leaves the ctx usable. */
+#define NM_KMER_MAX_FLANKS 10
+#define NM_KMER_MAX_OFFSET 31
+int nm_kmer_methylation(nm_ctx *ctx, uint32_t n_req, const uint32_t *req_bin, const uint8_t *req_mod_slot, uint32_t n_offsets,
+                        const int8_t *offsets, uint64_t *totals, uint64_t *table);
+
 /* ---- METHYLATION TRACKS: a motif's site counts per WINDOW along the contigs of its bin ------------------------------------------------
  * Reference: none (motif_model_contig, find_motifs_bin.py:1285-1331, sums over the contig).  The exports above give one row per contig
  * or per bin; this call keeps the counts apart by position: a chimeric contig is a step function, an island an unmethylated stretch,

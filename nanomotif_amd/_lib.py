@@ -27,6 +27,7 @@ SYMBOLS = [
     "nm_motif_strands_count", "nm_motif_strands_sites", "nm_motif_strands_text",
     "nm_motif_profile_count",
     "nm_motif_context_count",
+    "nm_kmer_methylation",
     "nm_tracks_windows", "nm_motif_tracks_count",
     "nm_motif_fractions_count",
 ]
@@ -162,6 +163,7 @@ def _load_locked():
                                           C.c_uint64, u64p]
     lib.nm_motif_profile_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u32p, u8p, C.c_uint32, u8p, C.c_uint32, u64p, i64p]
     lib.nm_motif_context_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, i64p]
+    lib.nm_kmer_methylation.argtypes = [p, C.c_uint32, u32p, u8p, C.c_uint32, i8p, u64p, u64p]
     lib.nm_tracks_windows.argtypes = [p, C.c_uint32, C.c_uint32, u64p, C.c_uint32, u32p]
     lib.nm_motif_tracks_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, u32p]
     lib.nm_motif_fractions_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p]

@@ -46,6 +46,67 @@ FRACTIONS_BUDGET_BYTES = 256 << 20             # default size of the table of on
 UNEXPLAINED_DTYPE =np.dtype([("set", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])   # ScanEngine.unexplained_sites
 
 
+KMER_MAX_FLANKS = 10                           # NM_KMER_MAX_FLANKS: counted positions of a k-mer shape ...
+KMER_MAX_OFFSET = 31                           # ... each within NM_KMER_MAX_OFFSET of the modified base
+KMER_BUDGET_BYTES = 256 << 20                  # default size of the tables of one library call of ScanEngine.kmer_methylation
+KMER_LETTERS = "ACGT"                          # the digits 0..3 of a row index
+
+
+def kmer_shape(shape) -> tuple:
+    """The counted offsets of a k-mer shape, ascending: ``shape`` is a shape string — ``N`` a counted position, ``.`` a skipped one,
+    exactly one ``*`` for the modified base, e.g. ``NNN*......NNN`` — or a sequence of distinct non-zero offsets.  At most
+    ``KMER_MAX_FLANKS`` offsets, each within ``KMER_MAX_OFFSET`` of the modified base; ValueError otherwise."""
+    if isinstance(shape, str):
+        bad = sorted(set(shape) - set("N.*"))
+        if bad:
+            raise ValueError(f"shape {shape!r}: only N, . and * are expected, got {''.join(bad)!r}")
+        if shape.count("*") != 1:
+            raise ValueError(f"shape {shape!r}: exactly one * (the modified base) is expected, got {shape.count('*')}")
+        centre = shape.index("*")
+        offsets = [j - centre for j, ch in enumerate(shape) if ch == "N"]
+    else:
+        offsets = sorted(int(o) for o in shape)
+        if len(set(offsets)) != len(offsets) or 0 in offsets:
+            raise ValueError(f"shape {list(shape)!r}: distinct non-zero offsets are expected")
+    if len(offsets) > KMER_MAX_FLANKS:
+        raise ValueError(f"shape {shape!r}: {len(offsets)} counted positions, at most {KMER_MAX_FLANKS} are possible")
+    if any(abs(o) > KMER_MAX_OFFSET for o in offsets):
+        raise ValueError(f"shape {shape!r}: a counted position lies more than {KMER_MAX_OFFSET} from the modified base")
+    return tuple(offsets)
+
+
+def kmer_text(shape, canonical: str, row: int) -> str:
+    """The k-mer of table row ``row`` under ``shape``: its letters at the counted positions (the first offset is the most significant
+    base-4 digit, A C G T = 0 1 2 3), the canonical base at the modified position, ``.`` in the gaps — from the lowest offset (or the
+    modified base) to the highest."""
+    offsets = kmer_shape(shape)
+    row = int(row)
+    if not 0 <= row < 4 ** len(offsets):
+        raise ValueError(f"row {row} outside 0..{4 ** len(offsets) - 1}")
+    lo, hi = min(offsets + (0,)), max(offsets + (0,))
+    text = ["."] * (hi - lo + 1)
+    text[-lo] = canonical
+    for f, o in enumerate(offsets):
+        text[o - lo] = KMER_LETTERS[(row >> 2 * (len(offsets) - 1 - f)) & 3]
+    return "".join(text)
+
+
+def kmer_row(shape, text: str) -> int:
+    """The table row of a k-mer text of ``kmer_text`` (the letters at the skipped positions and at the modified base play no part)."""
+    offsets = kmer_shape(shape)
+    lo = min(offsets + (0,))
+    row = 0
+    for o in offsets:
+        row = row * 4 + KMER_LETTERS.index(text[o - lo])
+    return row
+
+
+def kmer_motif(shape, canonical: str, row: int) -> Motif:
+    """The ``Motif`` whose strand-summed ``motif_site_counts`` row is table row ``row``: ``kmer_text`` with its modified position."""
+    offsets = kmer_shape(shape)
+    return Motif(kmer_text(offsets, canonical, row), -min(offsets + (0,)))
+
+
 def site_state_set(states) -> int:
     """("mod", "nocall") -> the state_set bits of nm_motif_sites."""
     states = tuple(states)
@@ -1166,6 +1227,35 @@ class ScanEngine:
         table[..., :4] = four
         table[..., 4] = states[:, None, :, :] - four.sum(axis=-1)
         return states, table
+
+    # ------------------------------------------------------------------ methylation of every k-mer context (nm_kmer_methylation)
+    def kmer_methylation(self, requests, shape, max_bytes=None):
+        """The methylation of EVERY sequence context of a shape around the A (or C) of a bin, without a motif (nm_kmer_methylation).
+        ``requests``: sequence of (mod type or slot number, bin name or id); ``shape``: see ``kmer_shape``, F counted offsets in the
+        reading direction of the site's strand.  Sites are the positions that hold the slot's canonical base X ('+') or its complement
+        (a site on '-'); the state of a site is ``motif_site_counts``'.  Returns (totals int64[n, 2 (strand), 3 (mod, nomod, nocall)]:
+        all sites = ``motif_site_counts`` of the one-letter motif X summed over the bin's contigs; table int64[n, 4^F, 3]: the sites
+        whose F probed positions all lie inside the contig and hold A, C, G or T, summed over strands and contigs, row = the base-4
+        number of the letters (``kmer_text`` / ``kmer_motif`` spell a row).  Consecutive requests share one library call while their
+        tables fit ``max_bytes`` (default ``KMER_BUDGET_BYTES``; a request is 24 x 4^F bytes); a call holds at least one request.  The
+        result does not depend on ``max_bytes``."""
+        offsets = np.asarray(kmer_shape(shape), dtype=np.int8)
+        limit = KMER_BUDGET_BYTES if max_bytes is None else int(max_bytes)
+        if limit < 1:
+            raise ValueError("max_bytes must be at least 1")
+        requests = list(requests)
+        n, rows = len(requests), 4 ** len(offsets)
+        bi, so = self.bin_index, self.slot_of_mod
+        slots = np.fromiter((so[r[0]] if isinstance(r[0], str) else int(r[0]) for r in requests), dtype=np.uint8, count=n)
+        bins = np.fromiter((bi[r[1]] if isinstance(r[1], str) else int(r[1]) for r in requests), dtype=np.uint32, count=n)
+        totals = np.zeros((n, 2, 3), dtype=np.uint64)
+        table = np.zeros((n, rows, 3), dtype=np.uint64)
+        off = np.ascontiguousarray(offsets) if len(offsets) else np.zeros(1, dtype=np.int8)
+        for k, e, _ in _budget_groups([rows * 24 + 48] * n, limit):
+            b, s = np.ascontiguousarray(bins[k:e]), np.ascontiguousarray(slots[k:e])
+            _lib.check(self.lib.nm_kmer_methylation(self.ctx, e - k, _ptr(b, C.c_uint32), _ptr(s, C.c_uint8), len(offsets), _ptr(off, C.c_int8),
+                                                    _ptr(totals[k:e], C.c_uint64), _ptr(table[k:e], C.c_uint64)))
+        return totals.astype(np.int64), table.astype(np.int64)
 
     # ------------------------------------------------------------------ methylation along contigs (nm_tracks_windows, nm_motif_tracks_count)
     def track_windows(self, bin, window) -> np.ndarray:
