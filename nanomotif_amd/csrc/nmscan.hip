@@ -421,14 +421,19 @@ int release_stage(nm_ctx *c, hipStream_t s) {   // call after the last device wo
     return NM_OK;
 }
 
+constexpr size_t EV_POOL_MAX = 65536;
+
+static hipError_t ev_pool_grow(nm_ctx *c) {             // one more event pair for the timing pool (the callers keep it below EV_POOL_MAX)
+    hipEvent_t a = nullptr, b = nullptr;
+    hipError_t e = hipEventCreate(&a);
+    if (e == hipSuccess) e = hipEventCreate(&b);
+    if (e == hipSuccess) c->ev_pool.emplace_back(a, b);
+    return e;
+}
+
 void busy_begin(nm_ctx *c) {
     if (!c->ev_collect_all) return;
-    if (c->ev_used == c->ev_pool.size()) {
-        if (c->ev_pool.size() >= 65536) return;
-        hipEvent_t a = nullptr, b = nullptr;
-        if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
-        c->ev_pool.emplace_back(a, b);
-    }
+    if (c->ev_used == c->ev_pool.size() && (c->ev_pool.size() >= EV_POOL_MAX || ev_pool_grow(c) != hipSuccess)) return;
     (void)hipEventRecord(c->ev_pool[c->ev_used].first, c->stream);
     c->busy_open = true;
 }
@@ -453,15 +458,13 @@ int join_lanes(nm_ctx *c) {
 namespace {
 
 
-// Launch shape of a batch.  heavy: one workgroup column per classification (blockIdx.y), candidates VALU-bound;
-// light (<= 6 candidates per (slot, bin) group on average — a round of the greedy search): HBM-bound, groups share their
-// common constraints (CF), two classifications (the usual 6mA + 5mC batch) share one pass over the sequence planes.
+// Launch shape of a batch: which kernel variant its plan (nmscore_plan.h: plan_shape) asks for.
 struct LaunchShape {
     int wide;                 // 0: offsets in [-32, 31], 1: [-64, 63], 2: [-96, 95]
-    bool compact, lit, light;
-    uint32_t n_active;
-    bool per_contig = false;
-    bool classes = false;     // narrow compact non-literal heavy batch: the class-plane variants and their program layout
+    bool compact, lit, light; // light: the streaming (CF) variants
+    bool fuse;                // two slots in one workgroup column
+    bool per_contig;
+    bool classes;             // narrow compact non-literal heavy batch: the class-plane variants and their program layout
 };
 
 template <class K>
@@ -470,15 +473,14 @@ void launch_variant(const ScoreArgs &a, uint32_t gx, uint32_t gy, hipStream_t s)
 }
 
 template <int G, bool COMPACT, bool LIT>
-void launch_by_load(const ScoreArgs &a, uint32_t gx, const LaunchShape &sh, hipStream_t s) {
-    if (!sh.light) launch_variant<Variant<G, G, COMPACT, 1, LIT, false>>(a, gx, std::max(sh.n_active, 1u), s);
-    else if (sh.n_active == 2 && LIT) launch_variant<Variant<G, G, COMPACT, 2, LIT, true>>(a, gx, 1, s);   // (fusing two slots on the 8-plane tile needs 128 VGPRs)
-    else launch_variant<Variant<G, G, COMPACT, 1, LIT, true>>(a, gx, std::max(sh.n_active, 1u), s);
+void launch_by_load(const ScoreArgs &a, uint32_t gx, uint32_t gy, const LaunchShape &sh, hipStream_t s) {
+    if (!sh.light) launch_variant<Variant<G, G, COMPACT, 1, LIT, false>>(a, gx, gy, s);
+    else if (sh.fuse && LIT) launch_variant<Variant<G, G, COMPACT, 2, LIT, true>>(a, gx, gy, s);   // (fusing two slots on the 8-plane tile needs 128 VGPRs)
+    else launch_variant<Variant<G, G, COMPACT, 1, LIT, true>>(a, gx, gy, s);
 }
 
-void launch_score(const ScoreArgs &a, uint32_t gx, const LaunchShape &sh, hipStream_t s) {
+void launch_score(const ScoreArgs &a, uint32_t gx, uint32_t gy, const LaunchShape &sh, hipStream_t s) {
     if (sh.per_contig) {      // (candidate, contig) counters: the plain one-slot-per-column kernels with the other reduction key
-        const uint32_t gy = std::max(sh.n_active, 1u);
         if (sh.wide == 2 && sh.compact) launch_variant<Variant<3, 3, true, 1, false, false, true>>(a, gx, gy, s);
         else if (sh.wide == 2) launch_variant<Variant<3, 3, false, 1, false, false, true>>(a, gx, gy, s);
         else if (!sh.wide && sh.compact && sh.classes) launch_score_classes(a, gx, gy, true, s);
@@ -489,309 +491,95 @@ void launch_score(const ScoreArgs &a, uint32_t gx, const LaunchShape &sh, hipStr
         return;
     }
     if (sh.wide == 2) {       // motifs that reach more than 63 positions from the modified base (search frames above 127)
-        if (sh.compact) launch_by_load<3, true, false>(a, gx, sh, s);
-        else launch_by_load<3, false, false>(a, gx, sh, s);
+        if (sh.compact) launch_by_load<3, true, false>(a, gx, gy, sh, s);
+        else launch_by_load<3, false, false>(a, gx, gy, sh, s);
     } else if (!sh.wide && sh.compact) {
-        if (sh.classes) launch_score_classes(a, gx, std::max(sh.n_active, 1u), false, s);
-        else if (sh.lit) launch_by_load<1, true, true>(a, gx, sh, s);
-        else launch_by_load<1, true, false>(a, gx, sh, s);
-    } else if (!sh.wide) launch_by_load<1, false, false>(a, gx, sh, s);
-    else if (sh.compact) launch_by_load<2, true, false>(a, gx, sh, s);
-    else launch_by_load<2, false, false>(a, gx, sh, s);
+        if (sh.classes) launch_score_classes(a, gx, gy, false, s);
+        else if (sh.lit) launch_by_load<1, true, true>(a, gx, gy, sh, s);
+        else launch_by_load<1, true, false>(a, gx, gy, sh, s);
+    } else if (!sh.wide) launch_by_load<1, false, false>(a, gx, gy, sh, s);
+    else if (sh.compact) launch_by_load<2, true, false>(a, gx, gy, sh, s);
+    else launch_by_load<2, false, false>(a, gx, gy, sh, s);
 }
 
-int score_impl(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot,
-               const uint8_t *cand_len, const uint8_t *cand_modpos, const uint32_t *cand_mask_offset,
-               const uint8_t *cand_masks, unsigned long long *d_out, int64_t *h_out, const uint64_t *row_offset = nullptr,
-               bool defer = false, const SpecSource *spec = nullptr, hipStream_t spec_stream = nullptr, int flight = 0) {
-    // defer: host counts, collected later by nm_score_batch_end (the call returns with everything enqueued)
-    // spec: the motifs are written on the device (SpecSource, nmscan_internal.h); always deferred, noted in c->spec_wait, on spec_stream
-    if (!c) return fail(NM_EINVAL, "ctx is NULL");
-    if (!c->dH) return fail(NM_ESTATE, "nm_upload_contigs has not been called");
-    nm_ctx::Waiting &wait_slot = spec ? c->spec_wait[flight] : c->score_wait[flight];
-    if (defer) {
-        if (wait_slot.open) return fail(NM_ESTATE, "nm_score_batch_begin: the previous batch has not been collected (nm_score_batch_end)");
-        nmdetail::wait_set(c, wait_slot, nm_ctx::Waiting{nullptr, 0, nullptr, true});
-    }
-    if (n_cand == 0) return NM_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    // ---- one pass over the candidates: validate, classify the batch, count per (slot, bin) bucket.
-    // Candidates whose bin has no contig on this device (multi-GPU shard) contribute zero and get no program.
-    const uint32_t n_bins = c->n_bins;
-    std::vector<uint32_t> &bucket = c->bucket;          // counting sort by (slot, bin)
-    bucket.assign((size_t)NM_MAX_MOD_SLOTS * n_bins + 1, 0);
-    int any_wide = 0;                                    // widest offset class of the batch: 0 / 1 / 2 (see LaunchShape)
-    bool all_compact = true, all_literal = true;
-    uint32_t n_prog = 0;
-    uint64_t mask_bytes = 0, mask_lo = ~0ull;   // byte range of cand_masks the resident candidates reference
-    bool slot_used[NM_MAX_MOD_SLOTS] = {};
-    for (uint32_t k = 0; k < n_cand; ++k) {
-        const uint32_t slot = cand_mod_slot[k], bin = cand_bin[k];
-        if (slot >= NM_MAX_MOD_SLOTS || !c->slots[slot].present)
-            return fail(NM_ESTATE, "candidate %u uses mod slot %u with no pileup uploaded", k, slot);
-        if (bin >= n_bins) return fail(NM_EINVAL, "candidate %u: bin %u >= n_bins %u", k, bin, n_bins);
-        if (c->bin_nchunks[bin] == 0) continue;         // not resident here: the rank that holds the bin validates it
-        if (spec) {                                      // motif unknown here: literal, compact, narrow by contract; mask_stride bytes each
-            mask_lo = 0;
-            mask_bytes = std::max<uint64_t>(mask_bytes, (uint64_t)(k + 1) * spec->mask_stride);
-            bucket[(size_t)slot * n_bins + bin + 1] += 1;
-            slot_used[slot] = true;
-            n_prog += 1;
-            continue;
-        }
-        const uint32_t len = cand_len[k], mp = cand_modpos[k];
-        if (len == 0 || len > NM_MAX_MOTIF_LEN) return fail(NM_ERANGE, "candidate %u: motif length %u outside 1..%d", k, len, NM_MAX_MOTIF_LEN);
-        if (mp >= len) return fail(NM_EINVAL, "candidate %u: mod_position %u outside motif of length %u", k, mp, len);
-        const uint8_t *m = cand_masks + cand_mask_offset[k];
-        uint32_t all_and = 15u, any_zero = 0, any_set = 0;
-        for (uint32_t j = 0; j < len; ++j) {
-            const uint32_t v = m[j] & 15u;
-            all_and &= v;
-            any_zero |= (v == 0);
-            any_set |= (v != 15u) & ((v & (v - 1)) != 0);      // a 2- or 3-base set
-        }
-        if (any_set) all_literal = false;
-        if (any_zero) return fail(NM_EINVAL, "candidate %u: empty base set in the motif", k);
-        if (all_and == 15u) return fail(NM_EINVAL, "candidate %u: motif has no specified position", k);
-        mask_lo = std::min<uint64_t>(mask_lo, cand_mask_offset[k]);
-        mask_bytes = std::max<uint64_t>(mask_bytes, (uint64_t)cand_mask_offset[k] + len);
-        // offsets relative to the modified base span [-mp, len-1-mp] forward and the mirror image in reverse
-        {
-            const uint32_t reach = std::max(mp, len - 1 - mp);
-            if (reach > 95) return fail(NM_ERANGE, "candidate %u: a position %u away from the modified base (the engine reaches 95)", k, reach);
-            any_wide = std::max(any_wide, reach > 63 ? 2 : reach > 31 ? 1 : 0);
-        }
-        const uint32_t can_mask = c->slots[slot].canonical == 'A' ? NM_BASE_A : NM_BASE_C;
-        if ((m[mp] & 15u) != can_mask) all_compact = false;
-        bucket[(size_t)slot * n_bins + bin + 1] += 1;
-        slot_used[slot] = true;
-        n_prog += 1;
-    }
-    if (n_prog == 0) { mask_lo = 0; mask_bytes = 0; }
-    uint32_t active[NM_MAX_MOD_SLOTS], n_active = 0;
-    int slot_to_active[NM_MAX_MOD_SLOTS];
-    for (int sl = 0; sl < NM_MAX_MOD_SLOTS; ++sl) {
-        slot_to_active[sl] = -1;
-        if (slot_used[sl]) { slot_to_active[sl] = (int)n_active; active[n_active++] = (uint32_t)sl; }
-    }
-    // ---- staging layout: candidate records (sorted) | orig_index | mask bytes | cand_range
-    const bool per_contig = row_offset != nullptr;
-    const uint64_t out_rows = per_contig ? row_offset[n_cand] : n_cand;
-    if (per_contig)
-        for (uint32_t k = 0; k < n_cand; ++k)
-            if (row_offset[k + 1] - row_offset[k] != c->bin_ncontigs[cand_bin[k]])
-                return fail(NM_EINVAL, "candidate %u: %llu output rows for a bin of %u resident contigs", k,
-                            (unsigned long long)(row_offset[k + 1] - row_offset[k]), c->bin_ncontigs[cand_bin[k]]);
-    const bool lit = all_literal && all_compact && !any_wide && !c->opt_no_lit && !per_contig;   // literal-only tiles exist for the narrow compact kernels
-    const uint32_t np = lit ? 4u : 8u;
-    const uint32_t pdw = 2u * (2u + 2u * (uint32_t)any_wide) * np;         // dwords per program: [strand][word-group][plane]
-    const size_t rec_bytes = (size_t)n_prog * sizeof(CandRec);
-    const size_t off_orig = (rec_bytes + 15) & ~(size_t)15;
-    const size_t off_masks = (off_orig + (size_t)n_prog * 4 + 15) & ~(size_t)15;
-    const size_t off_range = (off_masks + (mask_bytes - mask_lo) + 15) & ~(size_t)15;
-    const uint32_t n_entries = std::max(n_active, 1u) * n_bins;
-    const size_t range_bytes = (size_t)n_entries * sizeof(uint4);
-    const size_t off_rows = (off_range + range_bytes + 15) & ~(size_t)15;          // per-contig mode: row base per sorted candidate
-    // The static segment table covers every bin; a batch whose candidates sit in a few bins only — the long tail of the
-    // search: a handful of tasks still open among hundreds of bins — would launch thousands of workgroups that find no
-    // candidate range and leave.  Such a batch brings its own table: the segments of the bins it has candidates for.
-    std::vector<uint8_t> bin_active(n_bins, 0);
-    uint32_t n_active_bins = 0;
-    size_t n_active_segs = 0;
-    for (uint32_t b = 0; b < n_bins; ++b) {
-        bool act = false;
-        for (int sl = 0; sl < NM_MAX_MOD_SLOTS && !act; ++sl) act = slot_used[sl] && bucket[(size_t)sl * n_bins + b + 1] > 0;
-        if (!act) continue;
-        bin_active[b] = 1;
-        n_active_bins += 1;
-        n_active_segs += (c->bin_nchunks[b] + c->seg_chunks - 1) / c->seg_chunks;
-    }
-    const bool own_segments = n_prog && n_active_segs * 4 <= (size_t)c->n_segments * 3 && getenv("NM_ALL_SEGMENTS") == nullptr;
-    const size_t off_segs = (off_rows + (per_contig ? (size_t)n_prog * 8 : 0) + 15) & ~(size_t)15;
-    const size_t off_posof = ((own_segments ? off_segs + n_active_segs * sizeof(uint4) : off_segs) + 15) & ~(size_t)15;     // spec: sorted position of candidate k
-    const size_t off_xin = (off_posof + (size_t)n_cand * 4 + 15) & ~(size_t)15;                                            // spec: the writer's extra input
-    const size_t total = spec ? off_xin + spec->extra_in
-                              : own_segments ? off_segs + n_active_segs * sizeof(uint4) : off_rows + (per_contig ? (size_t)n_prog * 8 : 0);
-    // host counts come back through the pinned half of the staging pair (a copy into pageable memory is staged by the
-    // runtime and costs tens of microseconds more per round of the search); tables too large for that go directly
-    const size_t out_bytes = (size_t)out_rows * 2 * sizeof(int64_t);
-    const bool via_stage = defer || (h_out && out_bytes <= ((size_t)4 << 20));
-    const size_t off_counts = (total + 15) & ~(size_t)15;
-    const size_t off_xout = (off_counts + out_bytes + 15) & ~(size_t)15;                // spec: the writer's extra output, behind the counts
-    const size_t stage_end = spec ? off_xout + spec->extra_out : off_counts + out_bytes;
-    int rc = ensure_stage(c, via_stage ? stage_end : total, 1);
-    if (rc) return rc;
-    // scoring lane of this call (nm_set_score_lanes): asynchronous device-output batches take the lane of their staging
-    // pair — a pair, its half of the program table and its stream are reused together; every other call runs on the
-    // ctx stream after the second lane has drained
-    hipStream_t sst = spec ? spec_stream : c->stream;
-    const bool laned = c->score_lanes == 2 && d_out && !h_out && !spec && !defer;
-    if (!laned && !spec) {
-        rc = join_lanes(c);
-        if (rc) return rc;
-    } else if (laned && ((c->cur_stage - c->stage) & 1)) {
-        sst = c->lane_stream;
-        c->lane_pending = true;
-    }
-    if (laned) {
-        // two launches that write the same count table are ordered (memset, kernel) only within one stream: when an
-        // earlier launch in flight wrote d_out from the other lane, this lane waits for it (its staging pair's event)
-        for (auto &st : c->stage)
-            if (&st != c->cur_stage && st.pending && st.last_out == d_out && st.last_stream && st.last_stream != sst)
-                HIP_TRY(hipStreamWaitEvent(sst, st.busy, 0));
-    }
-    uint8_t *hs = static_cast<uint8_t *>(c->h_stage);
-    CandRec *h_rec = reinterpret_cast<CandRec *>(hs);
-    uint32_t *h_orig = reinterpret_cast<uint32_t *>(hs + off_orig);
-    uint4 *h_range = reinterpret_cast<uint4 *>(hs + off_range);
-    if (!spec) memcpy(hs + off_masks, cand_masks + mask_lo, mask_bytes - mask_lo);
-    memset(h_range, 0, range_bytes);
-    if (own_segments) {
-        uint4 *h_segs = reinterpret_cast<uint4 *>(hs + off_segs);
-        size_t at = 0;
-        for (uint32_t b = 0; b < n_bins; ++b)
-            if (bin_active[b])
-                for (uint32_t k = 0; k < c->bin_nchunks[b]; k += c->seg_chunks)
-                    h_segs[at++] = make_uint4(c->bin_chunk0[b] + k, std::min<uint32_t>(c->seg_chunks, c->bin_nchunks[b] - k), b, 0);
-    }
-    uint32_t n_groups = 0;
-    // exclusive prefix over the buckets -> first sorted index of each (slot, bin); stable within a bucket
-    for (size_t i = 1; i < bucket.size(); ++i) bucket[i] += bucket[i - 1];
-    for (int sl = 0; sl < NM_MAX_MOD_SLOTS; ++sl) {
-        if (slot_to_active[sl] < 0) continue;
-        for (uint32_t b = 0; b < n_bins; ++b) {
-            const uint32_t lo = bucket[(size_t)sl * n_bins + b], hi = bucket[(size_t)sl * n_bins + b + 1];
-            if (hi > lo) {
-                h_range[(size_t)slot_to_active[sl] * n_bins + b] = make_uint4(lo, hi - lo, 0xFFFFFFFFu, 0);
-                n_groups += 1;
-            }
-        }
-    }
-    for (uint32_t k = 0; k < n_cand; ++k) {
-        const uint32_t slot = cand_mod_slot[k], bin = cand_bin[k];
-        if (c->bin_nchunks[bin] == 0) continue;
-        const uint32_t at = bucket[(size_t)slot * n_bins + bin]++;
-        if (spec) {
-            h_rec[at] = CandRec{k * spec->mask_stride, k, 0, 0, (uint8_t)slot, 0};
-            h_orig[at] = k;
-            reinterpret_cast<uint32_t *>(hs + off_posof)[k] = at;
-            continue;
-        }
-        h_rec[at] = CandRec{(uint32_t)(cand_mask_offset[k] - mask_lo), k, cand_len[k], cand_modpos[k], (uint8_t)slot, 0};
-        h_orig[at] = k;
-        if (per_contig) reinterpret_cast<uint64_t *>(hs + off_rows)[at] = row_offset[k];
-    }
-    // measured crossover (profiles/): up to ~6 candidates per (slot, bin) group the launch is HBM-bound
-    const bool light = (uint64_t)n_prog <= 6ull * n_groups && !per_contig;
-    const bool cf = light && !c->opt_no_cf;
-    // IUPAC classes: exactly the batches that launch Variant<1, 1, true, 1, false, false, PC> take the class-plane twin of
-    // that variant and the class program layout (the same 32 dwords per program).  NM_SCORE_CLASSES=0, read at every call,
-    // keeps them on the 8-plane path (same-process A/B, tests/test_gpu_iupac_classes.py).  NM_SCORE_HEAD=0, read at every
-    // call as well, compiles class programs without a head: every walk starts with plain moves and all literals stay in
-    // their words (tests/test_gpu_head_pair.py).
-    const char *cls_env = getenv("NM_SCORE_CLASSES");
-    const char *head_env = getenv("NM_SCORE_HEAD");
-    const bool cls_head = !(head_env && atoi(head_env) == 0);
-    const bool classes = !spec && !lit && !any_wide && all_compact && !cf && !(cls_env && atoi(cls_env) == 0);
-    static_assert(nmdetail::CLS_PROG_DW == 32, "a class program takes the room of a narrow 8-plane one");
-    static_assert(NM_MAX_MOD_SLOTS <= 32, "one bit per mod slot");
-    uint32_t c_slots = 0;
-    for (int sl = 0; sl < NM_MAX_MOD_SLOTS; ++sl) c_slots |= (c->slots[sl].canonical == 'C' ? 1u : 0u) << sl;
-    // device-side program buffer: one part per staging pair, so that compiling the next batches (on the copy stream)
-    // overlaps the scoring kernel of batch k; reuse of a part is gated like its staging pair (ensure_stage).  A light
-    // batch appends one common program per (slot, bin) entry.
-    const size_t need_dw = ((size_t)std::max(n_prog, 1u) + (cf ? n_entries : 0)) * pdw;
-    if (c->prog_cap_dw < need_dw) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipStreamSynchronize(c->copy_stream));
-        HIP_TRY(nmdetail::sync_flight_streams(c));
-        rc = join_lanes(c);
-        if (rc) return rc;
-        if (c->d_programs) (void)nmdetail::dev_free(c->d_programs);
-        c->d_programs = nullptr;
-        c->prog_cap_dw = 0;
-        HIP_TRY(nmdetail::dev_malloc(&c->d_programs, need_dw * 2 * 4 * NM_STAGE_RING));
-        c->prog_cap_dw = need_dw * 2;
-    }
-    uint32_t *const d_prog = c->d_programs + (size_t)(c->cur_stage - c->stage) * c->prog_cap_dw;
-    // staged tables travel and are compiled on the copy stream; the scoring stream waits for the compiled programs
-    // a call that returns host counts has nothing to overlap the compile with (the caller waits for this very batch):
-    // it prepares on the scoring stream itself — no event, no cross-stream wait in its chain of launch latencies
-    const bool inline_prep = (h_out || defer) && !c->opt_no_inline;
-    hipStream_t pst = inline_prep ? sst : c->copy_stream;
-    if (spec && spec->extra_in) spec->fill_host(hs + off_xin);
-    uint8_t *ds = static_cast<uint8_t *>(c->d_stage);
-    // ---- output counters
-    unsigned long long *out = spec ? reinterpret_cast<unsigned long long *>(ds + off_counts) : d_out;
-    if (!out) {
-        if (c->counts_cap < out_rows) {
-            if (c->d_counts) (void)nmdetail::dev_free(c->d_counts);
-            c->d_counts = nullptr;
-            c->counts_cap = 0;
-            HIP_TRY(nmdetail::dev_malloc(&c->d_counts, (size_t)out_rows * 2 * sizeof(unsigned long long) * 2));
-            c->counts_cap = (size_t)out_rows * 2;
-        }
-        out = c->d_counts;
-    }
-    // a batch somebody waits for (a round of the search): tables in, outputs cleared, results out by KERNELS on its own stream — no
-    // copy engine in the chain (nmscan_internal.h: stage_in); everything else keeps the copy engines
-    const bool by_kernels = inline_prep && pst == sst && total <= STAGE_KERNEL_MAX && (via_stage || !h_out) && getenv("NM_STAGE_COPIES") == nullptr;
-    const size_t clear_bytes = spec ? stage_end - off_counts : (size_t)out_rows * 2 * sizeof(unsigned long long);
-    if (by_kernels) {
-        rc = stage_in(pst, c->h_stage, c->d_stage, total, out, clear_bytes);
+// What the enqueueing steps of one scoring call share: its plan, where it runs and what it writes.
+struct ScoreRun {
+    const ScoreRequest &rq;
+    const ScorePlan &p;
+    hipStream_t sst, pst;               // the scoring stream, and the one the tables travel and are compiled on
+    bool laned;
+    uint8_t *hs, *ds;                   // the staging pair
+    uint32_t *d_prog;
+    unsigned long long *out;
+    hipEvent_t e0, e1;
+    bool timed_launch;
+};
+
+// Everything the scoring launch waits for, in the order the measured step time rests on: tables in, the timing pair, the
+// programs (compiled here, or written by the spec source between its own clear and the scoring), the hand-over from the
+// copy stream, the clear of the count table.
+int score_prepare(nm_ctx *c, ScoreRun &r, uint32_t c_slots) {       // c_slots: bit s = mod slot s has canonical base C
+    const ScorePlan &p = r.p;
+    // a batch somebody waits for: tables in and outputs cleared by ONE kernel on its own stream (nmscan_internal.h: stage_in)
+    if (p.by_kernels) {
+        const int rc = stage_in(r.pst, r.hs, r.ds, p.total, r.out, p.clear_bytes);
         if (rc) return rc;
     } else {
-        HIP_TRY(hipMemcpyAsync(c->d_stage, c->h_stage, total, hipMemcpyHostToDevice, pst));
+        HIP_TRY(hipMemcpyAsync(r.ds, r.hs, p.total, hipMemcpyHostToDevice, r.pst));
     }
-    hipEvent_t e0 = c->ev0, e1 = c->ev1;
-    const bool timed_launch = c->ev_collect || !defer;          // (a deferred batch of the search is not asked for its kernel time)
+    r.e0 = c->ev0;
+    r.e1 = c->ev1;
+    r.timed_launch = c->ev_collect || !r.rq.defer;          // (a deferred batch of the search is not asked for its kernel time)
     if (c->ev_collect) {
         if (c->ev_used == c->ev_pool.size()) {
-            if (c->ev_pool.size() >= 65536) return fail(NM_ESTATE, "timing pool exhausted: call nm_timing_reset");
-            hipEvent_t a_ = nullptr, b_ = nullptr;
-            HIP_TRY(hipEventCreate(&a_));
-            HIP_TRY(hipEventCreate(&b_));
-            c->ev_pool.emplace_back(a_, b_);
+            if (c->ev_pool.size() >= EV_POOL_MAX) return fail(NM_ESTATE, "timing pool exhausted: call nm_timing_reset");
+            HIP_TRY(ev_pool_grow(c));
         }
-        e0 = c->ev_pool[c->ev_used].first;
-        e1 = c->ev_pool[c->ev_used].second;
+        r.e0 = c->ev_pool[c->ev_used].first;
+        r.e1 = c->ev_pool[c->ev_used].second;
         c->ev_used += 1;
     }
-    if (spec) {
+    CandRec *const d_rec = reinterpret_cast<CandRec *>(r.ds);
+    uint4 *const d_range = reinterpret_cast<uint4 *>(r.ds + p.off_range);
+    const int fold_modpos = p.all_compact ? 1 : 0;
+    switch (p.compile) {
+    case PLAN_COMPILE_NONE: break;                       // nothing resident for this batch
+    case PLAN_COMPILE_SPEC: {
         // counts and the writer's extra output: one clear; the writer (window kernel + children + their programs); timed with the scoring
-        if (!by_kernels) HIP_TRY(hipMemsetAsync(ds + off_counts, 0, clear_bytes, pst));
-        if (timed_launch) HIP_TRY(hipEventRecord(e0, pst));
-        const SpecCompile cc{reinterpret_cast<CandRec *>(ds), reinterpret_cast<const uint32_t *>(ds + off_posof), ds + off_masks,
-                             reinterpret_cast<uint4 *>(ds + off_range), d_prog, pdw, n_prog, (int)np, any_wide, all_compact ? 1 : 0, cf ? 1 : 0};
-        rc = spec->launch(pst, ds + off_xin, ds + off_xout, cc);
+        const SpecSource *spec = r.rq.spec;
+        if (!p.by_kernels) HIP_TRY(hipMemsetAsync(r.ds + p.off_counts, 0, p.clear_bytes, r.pst));
+        if (r.timed_launch) HIP_TRY(hipEventRecord(r.e0, r.pst));
+        const SpecCompile cc{d_rec, reinterpret_cast<const uint32_t *>(r.ds + p.off_posof), r.ds + p.off_masks, d_range, r.d_prog, p.pdw, p.n_prog,
+                             (int)p.np, p.any_wide, fold_modpos, p.cf ? 1 : 0};
+        const int rc = spec->launch(r.pst, r.ds + p.off_xin, r.ds + p.off_xout, cc);
         if (rc) return rc;
-        *spec->h_extra_out = hs + off_xout;
+        *spec->h_extra_out = r.hs + p.off_xout;
+        break;
     }
-    if (n_prog && !spec) {
-        if (cf && n_prog <= 2048 && n_entries <= 8192 && !c->opt_no_inline) {
-            const size_t lds_bytes = (size_t)n_prog * pdw * 4 <= 48 * 1024 ? (size_t)n_prog * pdw * 4 : 0;
-            hipLaunchKernelGGL(compile_common_kernel, dim3(1), dim3(1024), lds_bytes, pst, n_prog, reinterpret_cast<const CandRec *>(ds),
-                               ds + off_masks, d_prog, any_wide, (int)np, all_compact ? 1 : 0, n_entries,
-                               reinterpret_cast<uint4 *>(ds + off_range), pdw, 8u, (uint32_t)(lds_bytes / 4));
+    case PLAN_COMPILE_FUSED: {
+        const size_t lds_bytes = (size_t)p.n_prog * p.pdw * 4 <= 48 * 1024 ? (size_t)p.n_prog * p.pdw * 4 : 0;
+        hipLaunchKernelGGL(compile_common_kernel, dim3(1), dim3(1024), lds_bytes, r.pst, p.n_prog, d_rec, r.ds + p.off_masks, r.d_prog, p.any_wide, (int)p.np,
+                           fold_modpos, p.n_entries, d_range, p.pdw, 8u, (uint32_t)(lds_bytes / 4));
+        HIP_TRY(hipGetLastError());
+        break;
+    }
+    case PLAN_COMPILE_ONLY:
+    case PLAN_COMPILE_THEN_COMMON:
+        hipLaunchKernelGGL(compile_kernel, dim3((p.n_prog + 255) / 256), dim3(256), 0, r.pst, p.n_prog, d_rec, r.ds + p.off_masks, r.d_prog, p.any_wide,
+                           (int)p.np, fold_modpos, p.classes ? (p.cls_head ? 1 : 2) : 0, c_slots);
+        HIP_TRY(hipGetLastError());
+        if (p.compile == PLAN_COMPILE_THEN_COMMON) {
+            hipLaunchKernelGGL(common_kernel, dim3((p.n_entries + 63) / 64), dim3(64), 0, r.pst, p.n_entries, d_range, r.d_prog, p.pdw, p.n_prog, 8u);
             HIP_TRY(hipGetLastError());
-        } else {
-            hipLaunchKernelGGL(compile_kernel, dim3((n_prog + 255) / 256), dim3(256), 0, pst, n_prog,
-                               reinterpret_cast<const CandRec *>(ds), ds + off_masks, d_prog, any_wide, (int)np,
-                               all_compact ? 1 : 0, classes ? (cls_head ? 1 : 2) : 0, c_slots);
-            HIP_TRY(hipGetLastError());
-            if (cf) {
-                hipLaunchKernelGGL(common_kernel, dim3((n_entries + 63) / 64), dim3(64), 0, pst, n_entries,
-                                   reinterpret_cast<uint4 *>(ds + off_range), d_prog, pdw, n_prog, 8u);
-                HIP_TRY(hipGetLastError());
-            }
         }
+        break;
     }
-    if (!inline_prep) {
+    if (!p.inline_prep) {
         HIP_TRY(hipEventRecord(c->copy_done, c->copy_stream));
         // strict order: the host waits for the compiled programs (tens of microseconds, the previous batch is still being
         // scored) and the scoring queue carries no cross-stream barrier packet — 5-6 us less between two launches; with two
         // lanes the host must run ahead instead, so there the stream waits
-        if (laned || c->opt_stream_wait) HIP_TRY(hipStreamWaitEvent(sst, c->copy_done, 0));
+        if (r.laned || c->opt_stream_wait) HIP_TRY(hipStreamWaitEvent(r.sst, c->copy_done, 0));
         else HIP_TRY(hipEventSynchronize(c->copy_done));
     }
 #ifdef NM_SCORE_PROBES
@@ -800,78 +588,173 @@ int score_impl(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, const uint8
 #else
     constexpr int score_probe = 0;                       // (the shipped library has no switch that changes what a call computes)
 #endif
-    if (!spec && !by_kernels && !(score_probe & 1)) HIP_TRY(hipMemsetAsync(out, 0, clear_bytes, sst));
+    if (p.compile != PLAN_COMPILE_SPEC && !p.by_kernels && !(score_probe & 1)) HIP_TRY(hipMemsetAsync(r.out, 0, p.clear_bytes, r.sst));
+    return NM_OK;
+}
+
+// Results out (through the pinned half of the pair, by a kernel or a copy engine), the pair released, the call's bookkeeping, and
+// what the caller gets now: a note for nm_score_batch_end, the counts, or nothing (device counts).
+int score_collect(nm_ctx *c, const ScoreRun &r, nm_ctx::Waiting &wait_slot) {
+    const ScorePlan &p = r.p;
+    if (p.via_stage && p.by_kernels) {
+        const int rc = stage_out(r.sst, r.out, r.hs + p.off_counts, p.clear_bytes);
+        if (rc) return rc;
+    } else if (p.via_stage) HIP_TRY(hipMemcpyAsync(r.hs + p.off_counts, r.out, p.clear_bytes, hipMemcpyDeviceToHost, r.sst));
+    const int rc = release_stage(c, r.sst);
+    if (rc) return rc;
+    c->cur_stage->last_out = r.rq.d_out;
+    c->cur_stage->last_stream = r.sst;
+    c->last_score_stream = r.sst;
+    c->timed = !c->ev_collect && r.timed_launch;
+    c->launches += 1;
+    c->last_wgs = p.last_wgs;
+    c->last_compact = p.all_compact ? p.n_prog : 0;
+    c->last_general = p.all_compact ? 0 : p.n_prog;
+    if (r.rq.defer) {
+        nmdetail::wait_set(c, wait_slot, nm_ctx::Waiting{r.hs + p.off_counts, p.out_bytes, c->cur_stage, true});
+    } else if (p.via_stage) {
+        HIP_TRY(hipEventSynchronize(c->cur_stage->busy));
+        memcpy(r.rq.h_out, r.hs + p.off_counts, p.out_bytes);
+    } else if (r.rq.h_out) {
+        HIP_TRY(hipMemcpyAsync(r.rq.h_out, r.out, p.out_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return NM_OK;
+}
+
+PlanFacts plan_facts(const nm_ctx *c) {
+    PlanFacts f;
+    f.n_bins = c->n_bins;
+    f.bin_nchunks = c->bin_nchunks.data();
+    f.bin_chunk0 = c->bin_chunk0.data();
+    f.bin_ncontigs = c->bin_ncontigs.data();
+    static_assert(NM_MAX_MOD_SLOTS <= 32, "one bit per mod slot");
+    for (int sl = 0; sl < NM_MAX_MOD_SLOTS; ++sl) {
+        f.slot_present |= (c->slots[sl].present ? 1u : 0u) << sl;
+        f.slot_is_c |= (c->slots[sl].canonical == 'C' ? 1u : 0u) << sl;
+    }
+    f.n_segments = c->n_segments;
+    f.seg_chunks = c->seg_chunks;
+    f.n_cus = c->n_cus;
+    f.opt_no_lit = c->opt_no_lit;
+    f.opt_no_cf = c->opt_no_cf;
+    f.opt_no_inline = c->opt_no_inline;
+    f.opt_fine = c->opt_fine;
+    f.opt_split = c->opt_split;
+    return f;
+}
+
+// One scoring call: the batch is planned in the pure steps of nmscore_plan.h, then enqueued here — every HIP call of the scoring
+// path is in this function, score_prepare or score_collect, in the order and on the streams the measured step time rests on.
+int score_impl(nm_ctx *c, const ScoreRequest &rq) {
+    if (!c) return fail(NM_EINVAL, "ctx is NULL");
+    if (!c->dH) return fail(NM_ESTATE, "nm_upload_contigs has not been called");
+    nm_ctx::Waiting &wait_slot = rq.spec ? c->spec_wait[rq.flight] : c->score_wait[rq.flight];
+    if (rq.defer) {
+        if (wait_slot.open) return fail(NM_ESTATE, "nm_score_batch_begin: the previous batch has not been collected (nm_score_batch_end)");
+        nmdetail::wait_set(c, wait_slot, nm_ctx::Waiting{nullptr, 0, nullptr, true});
+    }
+    if (rq.n_cand == 0) return NM_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    // ---- classify, shape, layout
+    const PlanFacts f = plan_facts(c);
+    c->bucket.assign((size_t)NM_MAX_MOD_SLOTS * f.n_bins + 1, 0);          // counting sort by (slot, bin)
+    c->bin_active.assign(f.n_bins, 0);
+    ScorePlan p;
+    if (plan_classify(p, rq, f, c->bucket.data(), c->bin_active.data())) return fail(p.status, "%s", p.err);
+    plan_shape(p, rq, f);
+    plan_layout(p, rq);
+    int rc = ensure_stage(c, p.via_stage ? p.stage_end : p.total, 1);
+    if (rc) return rc;
+    // ---- scoring lane of this call (nm_set_score_lanes): asynchronous device-output batches take the lane of their staging
+    // pair — a pair, its half of the program table and its stream are reused together; every other call runs on the
+    // ctx stream after the second lane has drained (a spec batch: on the stream it was given, the lanes left alone)
+    ScoreRun r{rq, p};
+    r.sst = rq.spec ? static_cast<hipStream_t>(rq.stream) : c->stream;
+    r.laned = c->score_lanes == 2 && rq.d_out && !rq.h_out && !rq.defer;
+    if (!r.laned && !rq.spec) {
+        rc = join_lanes(c);
+        if (rc) return rc;
+    } else if (r.laned && ((c->cur_stage - c->stage) & 1)) {
+        r.sst = c->lane_stream;
+        c->lane_pending = true;
+    }
+    if (r.laned) {
+        // two launches that write the same count table are ordered (memset, kernel) only within one stream: when an
+        // earlier launch in flight wrote d_out from the other lane, this lane waits for it (its staging pair's event)
+        for (auto &st : c->stage)
+            if (&st != c->cur_stage && st.pending && st.last_out == rq.d_out && st.last_stream && st.last_stream != r.sst)
+                HIP_TRY(hipStreamWaitEvent(r.sst, st.busy, 0));
+    }
+    // staged tables travel and are compiled on the copy stream; the scoring stream waits for the compiled programs.  A call
+    // that returns host counts prepares on the scoring stream itself (plan_shape: inline_prep)
+    r.pst = p.inline_prep ? r.sst : c->copy_stream;
+    // ---- fill
+    r.hs = static_cast<uint8_t *>(c->h_stage);
+    r.ds = static_cast<uint8_t *>(c->d_stage);
+    plan_fill(p, rq, f, c->bucket.data(), c->bin_active.data(), r.hs);
+    if (rq.spec && rq.spec->extra_in) rq.spec->fill_host(r.hs + p.off_xin);
+    // ---- device-side program buffer: one part per staging pair, so that compiling the next batches (on the copy stream)
+    // overlaps the scoring kernel of batch k; reuse of a part is gated like its staging pair (ensure_stage)
+    static_assert(nmdetail::CLS_PROG_DW == 32, "a class program takes the room of a narrow 8-plane one");
+    if (c->prog_cap_dw < p.prog_dw) {
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        HIP_TRY(hipStreamSynchronize(c->copy_stream));
+        HIP_TRY(nmdetail::sync_flight_streams(c));
+        rc = join_lanes(c);
+        if (rc) return rc;
+        if (c->d_programs) (void)nmdetail::dev_free(c->d_programs);
+        c->d_programs = nullptr;
+        c->prog_cap_dw = 0;
+        HIP_TRY(nmdetail::dev_malloc(&c->d_programs, p.prog_dw * 2 * 4 * NM_STAGE_RING));
+        c->prog_cap_dw = p.prog_dw * 2;
+    }
+    r.d_prog = c->d_programs + (size_t)(c->cur_stage - c->stage) * c->prog_cap_dw;
+    // ---- output counters: the caller's table, the batch's own pair (spec), or the ctx's table
+    r.out = rq.spec ? reinterpret_cast<unsigned long long *>(r.ds + p.off_counts) : rq.d_out;
+    if (!r.out) {
+        if (c->counts_cap < p.out_rows) {
+            if (c->d_counts) (void)nmdetail::dev_free(c->d_counts);
+            c->d_counts = nullptr;
+            c->counts_cap = 0;
+            HIP_TRY(nmdetail::dev_malloc(&c->d_counts, (size_t)p.out_rows * 2 * sizeof(unsigned long long) * 2));
+            c->counts_cap = (size_t)p.out_rows * 2;
+        }
+        r.out = c->d_counts;
+    }
+    // ---- tables in, compile, clear
+    rc = score_prepare(c, r, f.slot_is_c);
+    if (rc) return rc;
     // ---- launch
+    plan_geometry(p, f);
     ScoreArgs a{};
     a.seq = Planes{c->dH, c->dL, c->dV, c->d_needs_v};
     for (int s = 0; s < NM_MAX_MOD_SLOTS; ++s) {
         const ModSlot &ms = c->slots[s];
         a.st[s] = StatePlanes{ms.planes[0], ms.planes[1], ms.planes[2], ms.planes[3], ms.planes[4], ms.planes[5]};
+        a.slot_is_c[s] = ms.canonical == 'C';
     }
-    a.segments = own_segments ? reinterpret_cast<const uint4 *>(ds + off_segs) : c->d_segments;
-    a.n_segments = own_segments ? (uint32_t)n_active_segs : c->n_segments;
+    a.segments = p.own_segments ? reinterpret_cast<const uint4 *>(r.ds + p.off_segs) : c->d_segments;
+    a.n_segments = p.n_segments;
     a.n_bins = c->n_bins;
-    a.programs = d_prog;
-    a.orig_index = reinterpret_cast<uint32_t *>(ds + off_orig);
-    a.cand_range = reinterpret_cast<uint4 *>(ds + off_range);
-    a.out = out;
+    a.programs = r.d_prog;
+    a.orig_index = reinterpret_cast<uint32_t *>(r.ds + p.off_orig);
+    a.cand_range = reinterpret_cast<uint4 *>(r.ds + p.off_range);
+    a.out = r.out;
     a.chunk_rank = c->d_chunk_rank;
-    a.row_base = reinterpret_cast<const uint64_t *>(ds + off_rows);
-    for (uint32_t i = 0; i < n_active; ++i) a.active_slot[i] = active[i];
-    for (int sl = 0; sl < NM_MAX_MOD_SLOTS; ++sl) a.slot_is_c[sl] = c->slots[sl].canonical == 'C';
-    // workgroups that will find candidates, against what the device runs at once (~6 per CU): below ~2 rounds of
-    // workgroups the last, partly filled round is a large share of the launch -> smaller pieces
-    uint64_t est_wgs = (uint64_t)a.n_segments * n_groups / std::max<uint32_t>(own_segments ? n_active_bins : n_bins, 1);
-    if (light && n_active == 2 && lit) est_wgs = (est_wgs + 1) / 2;   // fused slots: one workgroup serves both
-    const uint64_t resident = (uint64_t)c->n_cus * 6;
-    uint32_t split_log2 = 0;
-    while (split_log2 < 2 && (est_wgs << split_log2) < 2 * resident) ++split_log2;      // measured (tools/gpu_r2f.sh): halves win below ~2 rounds, quarters never
-    if (c->opt_split >= 0) split_log2 = (uint32_t)c->opt_split;
-    a.split_log2 = split_log2;
-    // grid: runs of pieces (8 for the XCD-remapped heavy variants, 1 for the streaming ones); in every run the pieces a
-    // full round of resident workgroups would take LAST are cut finer (down to 4 chunks = one per wave)
-    const bool streaming = light && !c->opt_no_cf;
-    const uint32_t runs = streaming ? 1u : 8u;
-    const uint32_t n_pieces = a.n_segments << split_log2;
-    a.pieces_per_run = (n_pieces + runs - 1) / runs;
-    a.fine_log2 = c->opt_fine >= 0 ? (uint32_t)c->opt_fine : 2u - split_log2;
-    const uint32_t cols = std::max(1u, (streaming && n_active == 2 && lit) ? 1u : n_active);
-    uint32_t tail_pieces = (uint32_t)std::min<uint64_t>(a.pieces_per_run, (resident / cols + runs - 1) / runs);
-    if (a.fine_log2 == 0) tail_pieces = 0;
-    a.j_big = a.pieces_per_run - tail_pieces;
-    const uint32_t gx = (a.j_big + (tail_pieces << a.fine_log2)) * runs;
-    const LaunchShape shape{any_wide, all_compact, lit, light && !c->opt_no_cf, n_active, per_contig, classes};
-    const bool fuse = n_active == 2 && shape.light && lit;
-
-    if (timed_launch && !spec) HIP_TRY(hipEventRecord(e0, sst));
-    if (n_prog) launch_score(a, gx, shape, sst);   // else nothing resident for this batch: the zeroed table is the answer
+    a.row_base = reinterpret_cast<const uint64_t *>(r.ds + p.off_rows);
+    for (uint32_t i = 0; i < p.n_active; ++i) a.active_slot[i] = p.active[i];
+    a.split_log2 = p.split_log2;
+    a.pieces_per_run = p.pieces_per_run;
+    a.fine_log2 = p.fine_log2;
+    a.j_big = p.j_big;
+    const LaunchShape shape{p.any_wide, p.all_compact, p.lit, p.cf, p.fuse, p.per_contig, p.classes};
+    if (r.timed_launch && p.compile != PLAN_COMPILE_SPEC) HIP_TRY(hipEventRecord(r.e0, r.sst));
+    if (p.n_prog) launch_score(a, p.gx, p.gy, shape, r.sst);   // else nothing resident for this batch: the zeroed table is the answer
     HIP_TRY(hipGetLastError());
-    if (timed_launch) HIP_TRY(hipEventRecord(e1, sst));
-    if (by_kernels && (spec || via_stage)) {
-        rc = stage_out(sst, out, hs + off_counts, spec ? stage_end - off_counts : out_bytes);
-        if (rc) return rc;
-    } else if (spec) HIP_TRY(hipMemcpyAsync(hs + off_counts, ds + off_counts, stage_end - off_counts, hipMemcpyDeviceToHost, sst));
-    else if (via_stage) HIP_TRY(hipMemcpyAsync(hs + off_counts, out, out_bytes, hipMemcpyDeviceToHost, sst));
-    rc = release_stage(c, sst);
-    if (rc) return rc;
-    c->cur_stage->last_out = d_out;
-    c->cur_stage->last_stream = sst;
-    c->last_score_stream = sst;
-    c->timed = !c->ev_collect && timed_launch;
-    c->launches += 1;
-    c->last_wgs = (uint64_t)gx * (fuse ? 1 : std::max(n_active, 1u));
-    c->last_compact = all_compact ? n_prog : 0;
-    c->last_general = all_compact ? 0 : n_prog;
-    if (defer) {
-        nmdetail::wait_set(c, wait_slot, nm_ctx::Waiting{hs + off_counts, out_bytes, c->cur_stage, true});
-    } else if (via_stage) {
-        HIP_TRY(hipEventSynchronize(c->cur_stage->busy));
-        memcpy(h_out, hs + off_counts, out_bytes);
-    } else if (h_out) {
-        HIP_TRY(hipMemcpyAsync(h_out, out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return NM_OK;
+    if (r.timed_launch) HIP_TRY(hipEventRecord(r.e1, r.sst));
+    // ---- results out or deferral, bookkeeping
+    return score_collect(c, r, wait_slot);
 }
 
 }  // namespace
@@ -1280,10 +1163,32 @@ static int flight_table(nm_ctx *c, unsigned long long **table, size_t *cap, size
     return NM_OK;
 }
 
+// the candidate arrays every entry point passes on
+static ScoreRequest score_request(uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot, const uint8_t *cand_len = nullptr,
+                                  const uint8_t *cand_modpos = nullptr, const uint32_t *cand_mask_offset = nullptr, const uint8_t *cand_masks = nullptr) {
+    ScoreRequest rq;
+    rq.n_cand = n_cand;
+    rq.bin = cand_bin;
+    rq.slot = cand_mod_slot;
+    rq.len = cand_len;
+    rq.modpos = cand_modpos;
+    rq.mask_off = cand_mask_offset;
+    rq.masks = cand_masks;
+    return rq;
+}
+
 int nmdetail::score_batch_spec_begin(nm_ctx *c, int flight, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot, const SpecSource &spec,
                                      hipStream_t st) {
     if (n_cand && (!cand_bin || !cand_mod_slot)) return fail(NM_EINVAL, "NULL argument");
-    const int rc = score_impl(c, n_cand, cand_bin, cand_mod_slot, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, &spec, st, flight);
+    ScoreRequest rq = score_request(n_cand, cand_bin, cand_mod_slot);
+    rq.defer = true;
+    rq.spec = &spec;
+    rq.spec_mask_stride = spec.mask_stride;
+    rq.spec_extra_in = spec.extra_in;
+    rq.spec_extra_out = spec.extra_out;
+    rq.stream = st;
+    rq.flight = flight;
+    const int rc = score_impl(c, rq);
     if (rc) nmdetail::wait_close(c, c->spec_wait[flight]);
     return rc;
 }
@@ -1295,15 +1200,18 @@ int nmdetail::score_batch_flight_begin(nm_ctx *c, int flight, uint32_t n_cand, c
     if (c->score_wait[flight].open) return fail(NM_ESTATE, "score batch: the previous batch of the flight has not been collected");
     int rc = flight_table(c, &c->d_flight_counts[flight], &c->flight_counts_cap[flight], n_cand, c->stream);
     if (rc) return rc;
-    rc = score_impl(c, n_cand, cand_bin, cand_mod_slot, cand_len, cand_modpos, cand_mask_offset, cand_masks, c->d_flight_counts[flight], nullptr, nullptr, true,
-                    nullptr, nullptr, flight);
+    ScoreRequest rq = score_request(n_cand, cand_bin, cand_mod_slot, cand_len, cand_modpos, cand_mask_offset, cand_masks);
+    rq.d_out = c->d_flight_counts[flight];
+    rq.defer = true;
+    rq.flight = flight;
+    rc = score_impl(c, rq);
     if (rc) nmdetail::wait_close(c, c->score_wait[flight]);
     return rc;
 }
 
-int nmdetail::score_batch_flight_end(nm_ctx *c, int flight, int64_t *out_counts) {
-    if (!c || flight < 0 || flight >= NM_FLIGHTS) return fail(NM_EINVAL, "bad flight");
-    if (!c->score_wait[flight].open) return fail(NM_ESTATE, "score batch end without begin");
+// the collecting half of a deferred batch; not_begun: what the entry point says when there is none
+static int score_batch_end(nm_ctx *c, int flight, int64_t *out_counts, const char *not_begun) {
+    if (!c->score_wait[flight].open) return fail(NM_ESTATE, "%s", not_begun);
     const nm_ctx::Waiting w = c->score_wait[flight];
     nmdetail::WaitCloser closer{c, &c->score_wait[flight], nullptr};          // (the pair stays held until the counts are copied out)
     if (w.bytes == 0) return NM_OK;
@@ -1311,6 +1219,11 @@ int nmdetail::score_batch_flight_end(nm_ctx *c, int flight, int64_t *out_counts)
     HIP_TRY(hipEventSynchronize(w.stage->busy));
     if (out_counts) memcpy(out_counts, w.h, w.bytes);           // NULL: the batch is dropped
     return NM_OK;
+}
+
+int nmdetail::score_batch_flight_end(nm_ctx *c, int flight, int64_t *out_counts) {
+    if (!c || flight < 0 || flight >= NM_FLIGHTS) return fail(NM_EINVAL, "bad flight");
+    return score_batch_end(c, flight, out_counts, "score batch end without begin");
 }
 
 // nmfasta.hip: the contigs picked out of a device-resident packed sequence (any subset, any order, a record more than once)
@@ -1340,7 +1253,9 @@ int nm_score_batch(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, const u
                    const uint8_t *cand_masks, int64_t *out_counts) {
     if (n_cand && (!cand_bin || !cand_mod_slot || !cand_len || !cand_modpos || !cand_mask_offset || !cand_masks || !out_counts))
         return fail(NM_EINVAL, "NULL argument");
-    return score_impl(c, n_cand, cand_bin, cand_mod_slot, cand_len, cand_modpos, cand_mask_offset, cand_masks, nullptr, out_counts);
+    ScoreRequest rq = score_request(n_cand, cand_bin, cand_mod_slot, cand_len, cand_modpos, cand_mask_offset, cand_masks);
+    rq.h_out = out_counts;
+    return score_impl(c, rq);
 }
 
 int nm_score_batch_wide(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot, const uint16_t *cand_len,
@@ -1354,19 +1269,13 @@ int nm_score_batch_wide(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, co
     if (rc) return rc;
     uint64_t mask_bytes = 0;
     uint32_t max_chunks = 0;
+    ScorePlan check;                                                      // (carries the text of a refused motif)
     for (uint32_t k = 0; k < n_cand; ++k) {
-        const uint32_t slot = cand_mod_slot[k], bin = cand_bin[k], len = cand_len[k], mp = cand_modpos[k];
+        const uint32_t slot = cand_mod_slot[k], bin = cand_bin[k], len = cand_len[k];
         if (slot >= NM_MAX_MOD_SLOTS || !c->slots[slot].present) return fail(NM_ESTATE, "candidate %u uses mod slot %u with no pileup uploaded", k, slot);
         if (bin >= c->n_bins) return fail(NM_EINVAL, "candidate %u: bin %u >= n_bins %u", k, bin, c->n_bins);
-        if (len == 0 || len > NM_MAX_WIDE_MOTIF_LEN) return fail(NM_ERANGE, "candidate %u: motif length %u outside 1..%d", k, len, NM_MAX_WIDE_MOTIF_LEN);
-        if (mp >= len) return fail(NM_EINVAL, "candidate %u: mod_position %u outside motif of length %u", k, mp, len);
-        const uint8_t *m = cand_masks + cand_mask_offset[k];
-        uint32_t all_and = 15u;
-        for (uint32_t j = 0; j < len; ++j) {
-            if ((m[j] & 15u) == 0) return fail(NM_EINVAL, "candidate %u: empty base set in the motif", k);
-            all_and &= m[j] & 15u;
-        }
-        if (all_and == 15u) return fail(NM_EINVAL, "candidate %u: motif has no specified position", k);
+        bool literal;
+        if (check_motif(check, k, len, cand_modpos[k], cand_masks + cand_mask_offset[k], NM_MAX_WIDE_MOTIF_LEN, &literal)) return fail(check.status, "%s", check.err);
         mask_bytes = std::max<uint64_t>(mask_bytes, (uint64_t)cand_mask_offset[k] + len);
         max_chunks = std::max(max_chunks, c->bin_nchunks[bin]);
     }
@@ -1426,21 +1335,16 @@ int nm_score_batch_begin(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, c
     if (n_cand && (!cand_bin || !cand_mod_slot || !cand_len || !cand_modpos || !cand_mask_offset || !cand_masks))
         return fail(NM_EINVAL, "NULL argument");
     if (c && c->score_wait[0].open) return fail(NM_ESTATE, "nm_score_batch_begin: the previous batch has not been collected (nm_score_batch_end)");
-    const int rc = score_impl(c, n_cand, cand_bin, cand_mod_slot, cand_len, cand_modpos, cand_mask_offset, cand_masks, nullptr, nullptr, nullptr, true);
+    ScoreRequest rq = score_request(n_cand, cand_bin, cand_mod_slot, cand_len, cand_modpos, cand_mask_offset, cand_masks);
+    rq.defer = true;
+    const int rc = score_impl(c, rq);
     if (rc && c) c->score_wait[0].open = false;      // (a batch that failed half way is not open)
     return rc;
 }
 
-int nm_score_batch_end(nm_ctx *c, int64_t *out_counts) {
+int nm_score_batch_end(nm_ctx *c, int64_t *out_counts) {                 // the flight-0 case of score_batch_flight_end
     if (!c) return fail(NM_EINVAL, "ctx is NULL");
-    if (!c->score_wait[0].open) return fail(NM_ESTATE, "nm_score_batch_end without nm_score_batch_begin");
-    const nm_ctx::Waiting w = c->score_wait[0];
-    c->score_wait[0].open = false;
-    if (w.bytes == 0) return NM_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(w.stage->busy));
-    if (out_counts) memcpy(out_counts, w.h, w.bytes);           // NULL: the batch is dropped
-    return NM_OK;
+    return score_batch_end(c, 0, out_counts, "nm_score_batch_end without nm_score_batch_begin");
 }
 
 int nm_score_batch_device(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot,
@@ -1448,8 +1352,9 @@ int nm_score_batch_device(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, 
                           const uint8_t *cand_masks, int64_t *d_out_counts) {
     if (n_cand && (!cand_bin || !cand_mod_slot || !cand_len || !cand_modpos || !cand_mask_offset || !cand_masks || !d_out_counts))
         return fail(NM_EINVAL, "NULL argument");
-    return score_impl(c, n_cand, cand_bin, cand_mod_slot, cand_len, cand_modpos, cand_mask_offset, cand_masks,
-                      reinterpret_cast<unsigned long long *>(d_out_counts), nullptr);
+    ScoreRequest rq = score_request(n_cand, cand_bin, cand_mod_slot, cand_len, cand_modpos, cand_mask_offset, cand_masks);
+    rq.d_out = reinterpret_cast<unsigned long long *>(d_out_counts);
+    return score_impl(c, rq);
 }
 
 int nm_score_batch_per_contig(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot, const uint8_t *cand_len,
@@ -1458,7 +1363,10 @@ int nm_score_batch_per_contig(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_b
     if (!row_offset || (n_cand && (!cand_bin || !cand_mod_slot || !cand_len || !cand_modpos || !cand_mask_offset || !cand_masks || !out_counts)))
         return fail(NM_EINVAL, "NULL argument");
     if (row_offset[0] != 0) return fail(NM_EINVAL, "row_offset[0] must be 0");
-    return score_impl(c, n_cand, cand_bin, cand_mod_slot, cand_len, cand_modpos, cand_mask_offset, cand_masks, nullptr, out_counts, row_offset);
+    ScoreRequest rq = score_request(n_cand, cand_bin, cand_mod_slot, cand_len, cand_modpos, cand_mask_offset, cand_masks);
+    rq.h_out = out_counts;
+    rq.row_offset = row_offset;
+    return score_impl(c, rq);
 }
 
 int nm_bin_contigs(nm_ctx *c, uint32_t bin, uint32_t *contig_ids, uint32_t capacity, uint32_t *n_contigs) {

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/nmscan.h"
+#include "nmscore_plan.h"
 #include "nmspec.h"
 
 // error sink shared by all translation units (defined in nmscan.hip; the text is what nm_last_error() returns)
@@ -60,13 +61,6 @@ struct Planes {
 struct StatePlanes {
     const uint32_t *M, *U;               // compact (strand implied by base)
     const uint32_t *MP, *UP, *MM, *UM;   // general
-};
-
-// One candidate record as the host stages it (sorted by mod-type slot, then bin).
-struct CandRec {
-    uint32_t mask_off;   // into the staged mask bytes
-    uint32_t orig;       // caller's index of this candidate
-    uint8_t len, modpos, slot, pad;
 };
 
 struct WinTask {
@@ -122,7 +116,8 @@ struct nm_ctx {
     int score_lanes = 1;
     bool lane_pending = false;                        // work may be in flight on lane_stream
     hipStream_t last_score_stream = nullptr;          // where the most recent scoring launch went
-    std::vector<uint32_t> bucket;                     // per-call host scratch, kept to avoid reallocation
+    std::vector<uint32_t> bucket;                     // per-call host scratch of the scoring plan (nmscore_plan.h), kept to avoid reallocation
+    std::vector<uint8_t> bin_active;
     // window engine
     std::vector<nmdetail::WinTask> win_tasks;
     uint32_t *d_win_planes = nullptr, *d_win_alive = nullptr;

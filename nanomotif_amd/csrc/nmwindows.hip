@@ -811,12 +811,11 @@ static int win_batch_begin_impl(nm_ctx *c, uint32_t n_req, const uint32_t *req_t
         memcpy(h + o_kind, req_kind, n_req);
         memcpy(h + o_sets, req_sets, (size_t)n_req * ws);
         if (!spec) return;
-        // range entry of a request's (slot, bin) group in the scoring batch: active index of the slot * n_bins + bin, the active
-        // slots numbered in ascending order (score_impl does the same)
+        // range entry of a request's (slot, bin) group in the scoring batch: active index of the slot * n_bins + bin (nmscore_plan.h)
         bool used[NM_MAX_MOD_SLOTS] = {};
         for (uint32_t r = 0; r < n_req; ++r) used[spec->req_slot[r]] = true;
-        int act[NM_MAX_MOD_SLOTS], na = 0;
-        for (int s = 0; s < NM_MAX_MOD_SLOTS; ++s) act[s] = used[s] ? na++ : -1;
+        int act[NM_MAX_MOD_SLOTS];
+        nmdetail::number_active_slots(used, act);
         uint32_t *h_entry = reinterpret_cast<uint32_t *>(h + o_entry);
         for (uint32_t r = 0; r < n_req; ++r) h_entry[r] = (uint32_t)act[spec->req_slot[r]] * c->n_bins + spec->req_bin[r];
         memcpy(h + o_stask, spec->req_search_task, (size_t)n_req * 4);

@@ -1,0 +1,541 @@
+// Stand-alone check of the scoring plan (nanomotif_amd/csrc/nmscore_plan.h) on the CPU: random and directed batches, every
+// plan compared with a plain restatement written here.  Build: g++ -O2 -std=c++17 driver.cpp -o plan_check; run: ./plan_check [seed]
+// (tests/test_score_plan_host.py does both, a second time with -fsanitize=address,undefined where that links).
+#include <cinttypes>
+#include <cstdarg>
+#include <numeric>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "../../nanomotif_amd/csrc/nmscore_plan.h"
+
+using namespace nmdetail;
+
+namespace {
+
+std::mt19937_64 rng;
+uint32_t rnd(uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rng() % ((uint64_t)hi - lo + 1)); }      // inclusive
+bool chance(double p) { return (rng() >> 11) * (1.0 / 9007199254740992.0) < p; }
+
+long g_checks = 0, g_cases = 0, g_rejected = 0;
+std::string g_case;
+[[noreturn]] void die(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    fprintf(stderr, "plan_check FAILED in case '%s': ", g_case.c_str());
+    vfprintf(stderr, fmt, ap);
+    fprintf(stderr, "\n");
+    va_end(ap);
+    exit(1);
+}
+#define CHECK(cond, ...) do { ++g_checks; if (!(cond)) die(__VA_ARGS__); } while (0)
+
+struct World {                                          // an uploaded assembly as the plan sees it
+    std::vector<uint32_t> nchunks, chunk0, ncontigs;
+    std::vector<PlanU4> static_segs;
+    uint32_t n_chunks = 0;
+    PlanFacts f;
+};
+
+World make_world(uint32_t n_bins, uint32_t max_chunks, uint32_t n_slots, double resident = 0.85, int fixed_chunks = -1) {
+    World w;
+    w.nchunks.resize(n_bins);
+    w.chunk0.assign(n_bins, 0);
+    w.ncontigs.assign(n_bins, 0);
+    w.f.seg_chunks = chance(0.8) ? 16 : rnd(4, 24);
+    uint32_t next = 1;                                  // chunk 0 and the last chunk are pads (nm_upload_contigs)
+    for (uint32_t b = 0; b < n_bins; ++b) {
+        w.nchunks[b] = fixed_chunks >= 0 ? (uint32_t)fixed_chunks : chance(resident) ? rnd(1, max_chunks) : 0;
+        if (!w.nchunks[b]) continue;
+        w.chunk0[b] = next;
+        w.ncontigs[b] = rnd(1, 4);
+        for (uint32_t k = 0; k < w.nchunks[b]; k += w.f.seg_chunks)
+            w.static_segs.push_back(PlanU4{next + k, std::min(w.f.seg_chunks, w.nchunks[b] - k), b, 0});
+        next += w.nchunks[b];
+    }
+    w.n_chunks = next + 1;
+    w.f.n_bins = n_bins;
+    w.f.n_segments = (uint32_t)w.static_segs.size();
+    for (uint32_t s = 0; s < n_slots; ++s) {
+        w.f.slot_present |= 1u << s;
+        if (chance(0.5)) w.f.slot_is_c |= 1u << s;
+    }
+    w.f.n_cus = chance(0.7) ? 256 : rnd(1, 304);
+    return w;
+}
+
+void bind(World &w) {                                   // (the vectors may have moved)
+    w.f.bin_nchunks = w.nchunks.data();
+    w.f.bin_chunk0 = w.chunk0.data();
+    w.f.bin_ncontigs = w.ncontigs.data();
+}
+
+struct Batch {
+    std::vector<uint32_t> bin, off;
+    std::vector<uint8_t> slot, len, mp, masks;
+    std::vector<uint64_t> rows;                         // per-contig batches only
+    bool per_contig = false, defer = false, host_out = true, spec = false;
+    uint32_t stride = 64;
+    size_t extra_in = 0, extra_out = 0;
+    size_t size() const { return bin.size(); }
+};
+
+// kind: 0 literal, 1 with 2-sets, 2 with 3-sets, 3 an empty set, 4 all-N; reach_len: 0 = short, else the reach to sit at
+void add_motif(Batch &b, const World &w, uint32_t bin, uint32_t slot, int kind, uint32_t reach = 0, bool compact = true) {
+    uint32_t len, mp;
+    if (reach) {                                        // a position exactly `reach` from the modified base
+        mp = chance(0.5) ? reach : rnd(0, std::min(reach, 254u - reach));
+        len = mp == reach ? reach + 1 + rnd(0, std::min(reach, 254u - reach)) : mp + reach + 1;
+    } else {
+        len = rnd(1, 14);
+        mp = rnd(0, len - 1);
+    }
+    std::vector<uint8_t> m(len, 15);
+    const uint8_t can = (w.f.slot_is_c >> (slot & 7) & 1u) ? NM_BASE_C : NM_BASE_A;
+    static const uint8_t lits[4] = {1, 2, 4, 8}, two[6] = {3, 5, 6, 9, 10, 12}, three[4] = {7, 11, 13, 14};
+    if (kind != 4) {
+        for (uint32_t j = 0; j < len; ++j)
+            if (chance(len > 20 ? 0.08 : 0.5)) m[j] = lits[rnd(0, 3)];
+        m[0] = lits[rnd(0, 3)];                         // both ends specified: the reach is what was asked for
+        m[len - 1] = lits[rnd(0, 3)];
+        m[mp] = compact ? can : (uint8_t)(can == NM_BASE_A ? NM_BASE_G : NM_BASE_T);
+        const uint32_t at = rnd(0, len - 1);            // (a set on the modified base would undo `compact`: such a motif stays literal)
+        if (kind == 1 && at != mp) m[at] = two[rnd(0, 5)];
+        if (kind == 2 && at != mp) m[at] = three[rnd(0, 3)];
+        if (kind == 3) m[at] = 0;
+    }
+    if (chance(0.2)) for (auto &v : m) v |= (uint8_t)(rnd(0, 15) << 4);      // the high nibble is not part of a set
+    if (chance(0.1)) b.masks.insert(b.masks.end(), rnd(1, 9), 0);            // unreferenced bytes between motifs
+    b.bin.push_back(bin);
+    b.slot.push_back((uint8_t)slot);
+    b.len.push_back((uint8_t)len);
+    b.mp.push_back((uint8_t)mp);
+    b.off.push_back((uint32_t)b.masks.size());
+    b.masks.insert(b.masks.end(), m.begin(), m.end());
+}
+
+void add_rows(Batch &b, const World &w) {
+    b.per_contig = true;
+    b.rows.assign(b.size() + 1, 0);
+    for (size_t k = 0; k < b.size(); ++k) b.rows[k + 1] = b.rows[k] + (b.bin[k] < w.f.n_bins ? w.ncontigs[b.bin[k]] : 0);
+}
+
+ScoreRequest request_of(const Batch &b) {
+    static int64_t host_sink;
+    static const int spec_tag = 0;
+    ScoreRequest rq;
+    rq.n_cand = (uint32_t)b.size();
+    rq.bin = b.bin.data();
+    rq.slot = b.slot.data();
+    if (!b.spec) { rq.len = b.len.data(); rq.modpos = b.mp.data(); rq.mask_off = b.off.data(); rq.masks = b.masks.data(); }
+    if (b.per_contig) rq.row_offset = b.rows.data();
+    rq.defer = b.defer;
+    rq.h_out = b.host_out && !b.defer && !b.spec ? &host_sink : nullptr;
+    if (b.spec) {
+        rq.spec = reinterpret_cast<const SpecSource *>(&spec_tag);           // (opaque to the plan)
+        rq.spec_mask_stride = b.stride;
+        rq.spec_extra_in = b.extra_in;
+        rq.spec_extra_out = b.extra_out;
+        rq.defer = true;
+    }
+    return rq;
+}
+
+// the answer of the validation, candidate by candidate: {status, candidate}
+std::pair<int, uint32_t> brute_validate(const Batch &b, const World &w) {
+    for (uint32_t k = 0; k < b.size(); ++k) {
+        if (b.slot[k] >= NM_MAX_MOD_SLOTS || !(w.f.slot_present >> b.slot[k] & 1u)) return {NM_ESTATE, k};
+        if (b.bin[k] >= w.f.n_bins) return {NM_EINVAL, k};
+        if (w.nchunks[b.bin[k]] == 0 || b.spec) continue;
+        const int len = b.len[k], mp = b.mp[k];
+        if (len < 1 || len > NM_MAX_MOTIF_LEN) return {NM_ERANGE, k};
+        if (mp >= len) return {NM_EINVAL, k};
+        bool specified = false;
+        for (int j = 0; j < len; ++j) {
+            if ((b.masks[b.off[k] + j] & 15) == 0) return {NM_EINVAL, k};
+            specified |= (b.masks[b.off[k] + j] & 15) != 15;
+        }
+        if (!specified) return {NM_EINVAL, k};
+        if (mp > 95 || len - 1 - mp > 95) return {NM_ERANGE, k};
+    }
+    if (b.per_contig)
+        for (uint32_t k = 0; k < b.size(); ++k)
+            if (b.rows[k + 1] - b.rows[k] != w.ncontigs[b.bin[k]]) return {NM_EINVAL, k};
+    return {NM_OK, 0};
+}
+
+// One workgroup's chunks, restated from the block decode of score_kernel (nmscan_device.h:996-1025): cf = the K::CF numbering
+// (a single run of pieces) or the XCD-remapped one (eight runs).  false: the workgroup leaves without a piece.
+bool decode_block(const ScorePlan &p, bool cf, uint32_t block, const PlanU4 *segments, uint32_t *first, uint32_t *count) {
+    const uint32_t x = cf ? 0u : block % 8, j = cf ? block : block / 8;
+    uint32_t piece, sub = 0, n_sub = 1;
+    if (j < p.j_big) piece = x * p.pieces_per_run + j;
+    else {
+        const uint32_t k = j - p.j_big;
+        piece = x * p.pieces_per_run + p.j_big + (k >> p.fine_log2);
+        sub = k & ((1u << p.fine_log2) - 1);
+        n_sub = 1u << p.fine_log2;
+        if (p.j_big + (k >> p.fine_log2) >= p.pieces_per_run) return false;
+    }
+    const uint32_t seg = piece >> p.split_log2;
+    if (seg >= p.n_segments) return false;
+    uint32_t sx = segments[seg].x, sy = segments[seg].y;
+    if (p.split_log2) {
+        const uint32_t len = (sy + (1u << p.split_log2) - 1) >> p.split_log2;
+        const uint32_t at = (piece & ((1u << p.split_log2) - 1)) * len;
+        if (at >= sy) return false;
+        sx += at;
+        sy = std::min(len, sy - at);
+    }
+    if (n_sub > 1) {
+        const uint32_t len = (sy + n_sub - 1) / n_sub;
+        const uint32_t at = sub * len;
+        if (at >= sy) return false;
+        sx += at;
+        sy = std::min(len, sy - at);
+    }
+    *first = sx;
+    *count = sy;
+    return true;
+}
+
+std::vector<uint32_t> g_bucket;
+std::vector<uint8_t> g_bin_active, g_stage, g_visits;
+
+bool env_zero(const char *name) { const char *e = getenv(name); return e && atoi(e) == 0; }
+
+// plan the batch as score_impl does and compare every step with its restatement; returns the plan
+ScorePlan run_case(const char *name, World &w, const Batch &b) {
+    g_case = name;
+    ++g_cases;
+    bind(w);
+    const PlanFacts &f = w.f;
+    const ScoreRequest rq = request_of(b);
+    const uint32_t n_bins = f.n_bins, n = rq.n_cand;
+    g_bucket.assign((size_t)NM_MAX_MOD_SLOTS * n_bins + 1, 0);
+    g_bin_active.assign(n_bins, 0);
+    ScorePlan p;
+    const int rc = plan_classify(p, rq, f, g_bucket.data(), g_bin_active.data());
+    // ---- validation
+    const auto want = brute_validate(b, w);
+    CHECK(rc == want.first && p.status == rc, "status %d (%s), the brute force says %d at candidate %u", rc, p.err, want.first, want.second);
+    if (rc != NM_OK) {
+        unsigned k = ~0u;
+        CHECK(sscanf(p.err, "candidate %u", &k) == 1 && k == want.second, "message '%s' names another candidate than %u", p.err, want.second);
+        ++g_rejected;
+        return p;
+    }
+    // ---- the batch's class
+    std::vector<uint32_t> order;                        // resident candidates, stable by (slot, bin)
+    for (uint32_t k = 0; k < n; ++k) if (w.nchunks[b.bin[k]]) order.push_back(k);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return b.slot[x] != b.slot[y] ? b.slot[x] < b.slot[y] : b.bin[x] < b.bin[y]; });
+    int wide = 0;
+    bool compact = true, literal = true, slot_used[NM_MAX_MOD_SLOTS] = {};
+    std::vector<uint8_t> bin_used(n_bins, 0);
+    uint64_t lo = ~0ull, hi = 0;
+    for (uint32_t k : order) {
+        slot_used[b.slot[k]] = true;
+        bin_used[b.bin[k]] = 1;
+        if (b.spec) { lo = 0; hi = std::max<uint64_t>(hi, (uint64_t)(k + 1) * b.stride); continue; }
+        const int reach = std::max<int>(b.mp[k], b.len[k] - 1 - b.mp[k]);
+        wide = std::max(wide, reach >= 64 ? 2 : reach >= 32 ? 1 : 0);
+        for (int j = 0; j < b.len[k]; ++j) {
+            const int v = b.masks[b.off[k] + j] & 15, bits = __builtin_popcount(v);
+            if (bits == 2 || bits == 3) literal = false;
+        }
+        if ((b.masks[b.off[k] + b.mp[k]] & 15) != ((f.slot_is_c >> b.slot[k] & 1u) ? NM_BASE_C : NM_BASE_A)) compact = false;
+        lo = std::min<uint64_t>(lo, b.off[k]);
+        hi = std::max<uint64_t>(hi, (uint64_t)b.off[k] + b.len[k]);
+    }
+    if (order.empty()) lo = hi = 0;
+    CHECK(p.n_prog == order.size(), "n_prog %u, %zu candidates are resident", p.n_prog, order.size());
+    CHECK(p.any_wide == wide && p.all_compact == compact && p.all_literal == literal, "class (wide %d compact %d literal %d), expected (%d %d %d)",
+          p.any_wide, p.all_compact, p.all_literal, wide, compact, literal);
+    CHECK(p.mask_lo == lo && p.mask_hi == hi, "mask bytes [%" PRIu64 ", %" PRIu64 "), expected [%" PRIu64 ", %" PRIu64 ")", p.mask_lo, p.mask_hi, lo, hi);
+    uint32_t n_active = 0, n_act_bins = 0, n_groups = 0;
+    size_t n_act_segs = 0;
+    for (int s = 0; s < NM_MAX_MOD_SLOTS; ++s) {
+        CHECK(p.slot_to_active[s] == (slot_used[s] ? (int)n_active : -1), "slot %d numbered %d", s, p.slot_to_active[s]);
+        if (slot_used[s]) { CHECK(p.active[n_active] == (uint32_t)s, "active[%u] = %u, expected %d", n_active, p.active[n_active], s); ++n_active; }
+    }
+    for (uint32_t bb = 0; bb < n_bins; ++bb) {
+        CHECK(g_bin_active[bb] == bin_used[bb], "bin %u active %d, expected %d", bb, g_bin_active[bb], bin_used[bb]);
+        if (bin_used[bb]) { ++n_act_bins; n_act_segs += (w.nchunks[bb] + f.seg_chunks - 1) / f.seg_chunks; }
+    }
+    for (size_t i = 0; i < order.size(); ++i)
+        if (i == 0 || b.slot[order[i]] != b.slot[order[i - 1]] || b.bin[order[i]] != b.bin[order[i - 1]]) ++n_groups;
+    CHECK(p.n_active == n_active && p.n_active_bins == n_act_bins && p.n_active_segs == n_act_segs && p.n_groups == n_groups,
+          "active slots %u bins %u segments %zu groups %u, expected %u %u %zu %u", p.n_active, p.n_active_bins, p.n_active_segs, p.n_groups, n_active,
+          n_act_bins, n_act_segs, n_groups);
+    CHECK(p.out_rows == (b.per_contig ? b.rows[n] : n), "out_rows %" PRIu64, p.out_rows);
+    // ---- shape
+    plan_shape(p, rq, f);
+    const bool lit = literal && compact && !wide && !f.opt_no_lit && !b.per_contig;
+    const bool light = !b.per_contig && order.size() <= 6 * (size_t)n_groups, cf = light && !f.opt_no_cf;
+    const bool classes = !b.spec && !lit && !wide && compact && !cf && !env_zero("NM_SCORE_CLASSES");
+    const bool own = !order.empty() && 4 * n_act_segs <= 3 * (size_t)f.n_segments && !getenv("NM_ALL_SEGMENTS");
+    const uint32_t n_entries = std::max(n_active, 1u) * n_bins, np = lit ? 4 : 8, pdw = np * (wide == 0 ? 4 : wide == 1 ? 8 : 12);
+    CHECK(p.lit == lit && p.light == light && p.cf == cf && p.classes == classes && p.fuse == (n_active == 2 && cf && lit) && p.own_segments == own,
+          "shape lit %d light %d cf %d classes %d fuse %d own %d, expected %d %d %d %d %d %d", p.lit, p.light, p.cf, p.classes, p.fuse, p.own_segments, lit,
+          light, cf, classes, n_active == 2 && cf && lit, own);
+    CHECK(p.cls_head == !env_zero("NM_SCORE_HEAD"), "cls_head %d", p.cls_head);
+    CHECK(p.np == np && p.pdw == pdw && p.n_entries == n_entries, "np %u pdw %u entries %u, expected %u %u %u", p.np, p.pdw, p.n_entries, np, pdw, n_entries);
+    CHECK(p.prog_dw == (std::max<size_t>(order.size(), 1) + (cf ? n_entries : 0)) * pdw, "program room %zu dwords", p.prog_dw);
+    const PlanCompile compile = b.spec ? PLAN_COMPILE_SPEC : order.empty() ? PLAN_COMPILE_NONE
+                                : !cf ? PLAN_COMPILE_ONLY
+                                : order.size() <= 2048 && n_entries <= 8192 && !f.opt_no_inline ? PLAN_COMPILE_FUSED : PLAN_COMPILE_THEN_COMMON;
+    CHECK(p.compile == compile, "compile path %d, expected %d", p.compile, compile);
+    const size_t out_bytes = (size_t)p.out_rows * 16;
+    CHECK(p.via_stage == (rq.defer || (rq.h_out && out_bytes <= ((size_t)4 << 20))), "via_stage %d for %zu count bytes", p.via_stage, out_bytes);
+    CHECK(p.inline_prep == ((rq.h_out || rq.defer) && !f.opt_no_inline), "inline_prep %d", p.inline_prep);
+    // ---- layout: regions 16-byte aligned, in order, disjoint, ending at the total
+    plan_layout(p, rq);
+    struct Region { const char *what; size_t at, bytes; };
+    std::vector<Region> regions = {{"records", 0, order.size() * sizeof(CandRec)}, {"orig_index", p.off_orig, order.size() * 4},
+                                   {"masks", p.off_masks, (size_t)(hi - lo)}, {"ranges", p.off_range, (size_t)n_entries * 16}};
+    if (b.per_contig) regions.push_back({"row bases", p.off_rows, order.size() * 8});
+    if (own) regions.push_back({"segments", p.off_segs, n_act_segs * 16});
+    if (b.spec) { regions.push_back({"pos_of", p.off_posof, (size_t)n * 4}); regions.push_back({"extra in", p.off_xin, b.extra_in}); }
+    size_t end = 0;
+    for (const Region &r : regions) {
+        CHECK(r.at % 16 == 0 && r.at >= end && r.at < end + 16, "%s at %zu: the region before it ends at %zu", r.what, r.at, end);
+        end = r.at + r.bytes;
+    }
+    CHECK(p.total == end, "total %zu, the last region ends at %zu", p.total, end);
+    CHECK(p.range_bytes == (size_t)n_entries * 16 && p.out_bytes == out_bytes, "range bytes %zu, count bytes %zu", p.range_bytes, p.out_bytes);
+    CHECK(p.off_counts % 16 == 0 && p.off_counts >= p.total && p.off_counts < p.total + 16, "counts at %zu behind a total of %zu", p.off_counts, p.total);
+    if (b.spec) {
+        CHECK(p.off_xout % 16 == 0 && p.off_xout >= p.off_counts + out_bytes && p.off_xout < p.off_counts + out_bytes + 16, "extra out at %zu", p.off_xout);
+        CHECK(p.stage_end == p.off_xout + b.extra_out && p.clear_bytes == p.stage_end - p.off_counts, "stage end %zu, clear %zu", p.stage_end, p.clear_bytes);
+    } else CHECK(p.stage_end == p.off_counts + out_bytes && p.clear_bytes == out_bytes, "stage end %zu, clear %zu", p.stage_end, p.clear_bytes);
+    CHECK(p.by_kernels == (p.inline_prep && p.total <= ((size_t)4 << 20) && (p.via_stage || !rq.h_out) && !getenv("NM_STAGE_COPIES")),
+          "by_kernels %d for %zu staged bytes", p.by_kernels, p.total);
+    // ---- fill
+    g_stage.assign(p.total + 16, 0xA5);
+    uint8_t *hs = g_stage.data();
+    plan_fill(p, rq, f, g_bucket.data(), g_bin_active.data(), hs);
+    for (size_t i = 0; i < 16; ++i) CHECK(hs[p.total + i] == 0xA5, "fill wrote behind the total (%zu + %zu)", p.total, i);
+    const CandRec *rec = reinterpret_cast<const CandRec *>(hs);
+    const uint32_t *orig = reinterpret_cast<const uint32_t *>(hs + p.off_orig);
+    for (size_t i = 0; i < order.size(); ++i) {
+        const uint32_t k = order[i];
+        CHECK(rec[i].orig == k && orig[i] == k && rec[i].slot == b.slot[k], "sorted position %zu holds candidate %u, the stable sort puts %u there", i, rec[i].orig, k);
+        if (b.spec) {
+            CHECK(rec[i].mask_off == k * b.stride && reinterpret_cast<const uint32_t *>(hs + p.off_posof)[k] == i, "spec record %zu", i);
+            continue;
+        }
+        CHECK(rec[i].len == b.len[k] && rec[i].modpos == b.mp[k], "record %zu: len %u modpos %u", i, rec[i].len, rec[i].modpos);
+        CHECK((uint64_t)rec[i].mask_off + b.len[k] <= hi - lo && memcmp(hs + p.off_masks + rec[i].mask_off, b.masks.data() + b.off[k], b.len[k]) == 0,
+              "record %zu: its staged mask bytes are not the candidate's", i);
+        if (b.per_contig) CHECK(reinterpret_cast<const uint64_t *>(hs + p.off_rows)[i] == b.rows[k], "row base of sorted candidate %zu", i);
+    }
+    const PlanU4 *range = reinterpret_cast<const PlanU4 *>(hs + p.off_range);
+    {
+        size_t at = 0;
+        for (uint32_t a = 0; a < std::max(n_active, 1u); ++a)
+            for (uint32_t bb = 0; bb < n_bins; ++bb) {
+                size_t cnt = 0;
+                while (n_active && at + cnt < order.size() && b.slot[order[at + cnt]] == p.active[a] && b.bin[order[at + cnt]] == bb) ++cnt;
+                const PlanU4 &r = range[(size_t)a * n_bins + bb];
+                if (cnt) CHECK(r.x == at && r.y == cnt && r.z == 0xFFFFFFFFu && r.w == 0, "range (%u, %u) = {%u, %u, %u, %u}, the sort has %zu from %zu", a, bb, r.x, r.y, r.z, r.w, cnt, at);
+                else CHECK(r.x == 0 && r.y == 0 && r.z == 0 && r.w == 0, "range (%u, %u) of an empty group is not zero", a, bb);
+                at += cnt;
+            }
+        CHECK(at == order.size(), "the ranges hold %zu candidates of %zu", at, order.size());
+    }
+    // ---- the table the launch walks: the batch's own holds exactly the chunks of the active bins
+    const PlanU4 *segments = own ? reinterpret_cast<const PlanU4 *>(hs + p.off_segs) : w.static_segs.data();
+    CHECK(p.n_segments == (own ? n_act_segs : f.n_segments), "n_segments %u", p.n_segments);
+    g_visits.assign(w.n_chunks, 0);
+    std::vector<uint8_t> in_table(w.n_chunks, 0);
+    for (uint32_t s = 0; s < p.n_segments; ++s) {
+        const PlanU4 &sg = segments[s];
+        CHECK(sg.y >= 1 && sg.y <= f.seg_chunks && sg.z < n_bins && sg.x >= w.chunk0[sg.z] && sg.x + sg.y <= w.chunk0[sg.z] + w.nchunks[sg.z],
+              "segment %u = {%u, %u, %u} leaves its bin", s, sg.x, sg.y, sg.z);
+        for (uint32_t c = 0; c < sg.y; ++c) { CHECK(!in_table[sg.x + c], "chunk %u is in two segments", sg.x + c); in_table[sg.x + c] = 1; }
+    }
+    if (own)
+        for (uint32_t bb = 0; bb < n_bins; ++bb)
+            for (uint32_t c = 0; c < w.nchunks[bb]; ++c)
+                CHECK(in_table[w.chunk0[bb] + c] == bin_used[bb], "chunk %u of bin %u: in the own table %d, bin active %d", w.chunk0[bb] + c, bb, in_table[w.chunk0[bb] + c], bin_used[bb]);
+    // ---- geometry: every chunk of every segment is visited exactly once, nothing else is
+    plan_geometry(p, f);
+    const uint32_t split = f.opt_split >= 0 ? (uint32_t)f.opt_split : p.split_log2;
+    CHECK(p.split_log2 == split && p.split_log2 <= 2 && p.fine_log2 == (f.opt_fine >= 0 ? (uint32_t)f.opt_fine : 2 - split), "split %u fine %u", p.split_log2, p.fine_log2);
+    CHECK(p.gy == ((n_active == 2 && cf && lit) ? 1u : std::max(n_active, 1u)) && p.last_wgs == (uint64_t)p.gx * p.gy, "gy %u, workgroups %" PRIu64, p.gy, p.last_wgs);
+    CHECK(p.gx % (cf ? 1 : 8) == 0 && p.j_big <= p.pieces_per_run, "gx %u j_big %u pieces_per_run %u", p.gx, p.j_big, p.pieces_per_run);
+    for (uint32_t block = 0; block < p.gx; ++block) {
+        uint32_t first = 0, count = 0;
+        if (!decode_block(p, cf, block, segments, &first, &count)) continue;
+        CHECK(count >= 1 && (size_t)first + count <= w.n_chunks, "workgroup %u walks chunks [%u, +%u)", block, first, count);
+        for (uint32_t c = 0; c < count; ++c) g_visits[first + c] += 1;
+    }
+    for (uint32_t c = 0; c < w.n_chunks; ++c)
+        CHECK(g_visits[c] == in_table[c], "chunk %u is visited %d times (in the table: %d); gx %u split %u fine %u j_big %u pieces_per_run %u segments %u", c, g_visits[c],
+              in_table[c], p.gx, p.split_log2, p.fine_log2, p.j_big, p.pieces_per_run, p.n_segments);
+    return p;
+}
+
+void set_env(const char *name, const char *value) { if (value) setenv(name, value, 1); else unsetenv(name); }
+
+void random_case(int i) {
+    const uint32_t n_bins = chance(0.3) ? rnd(1, 8) : rnd(1, 400), n_slots = rnd(1, 8);
+    World w = make_world(n_bins, chance(0.5) ? 40 : 6, n_slots);
+    w.f.opt_no_lit = chance(0.1); w.f.opt_no_cf = chance(0.1); w.f.opt_no_inline = chance(0.1);
+    w.f.opt_split = (int)rnd(0, 5) - 3; if (w.f.opt_split < -1) w.f.opt_split = -1;
+    w.f.opt_fine = (int)rnd(0, 5) - 3;  if (w.f.opt_fine < -1) w.f.opt_fine = -1;
+    set_env("NM_ALL_SEGMENTS", chance(0.1) ? "1" : nullptr);
+    set_env("NM_STAGE_COPIES", chance(0.1) ? "1" : nullptr);
+    set_env("NM_SCORE_CLASSES", chance(0.15) ? "0" : nullptr);
+    set_env("NM_SCORE_HEAD", chance(0.15) ? "0" : nullptr);
+    Batch b;
+    const uint32_t n = chance(0.05) ? 0 : chance(0.15) ? rnd(1, 5000) : rnd(1, 300);
+    const uint32_t use_bins = chance(0.5) ? n_bins : rnd(1, n_bins), use_slots = rnd(1, n_slots);
+    const int style = (int)rnd(0, 4);                    // 0 literal compact, 1 with sets, 2 general, 3 wide, 4 anything
+    static const uint32_t borders[6] = {31, 32, 63, 64, 95, 95};
+    for (uint32_t k = 0; k < n; ++k) {
+        int kind = style == 0 ? 0 : (int)rnd(0, 2);
+        const bool compact = style == 0 || style == 1 || (style != 2 ? chance(0.9) : chance(0.5));
+        const uint32_t reach = (style == 3 && chance(0.3)) || (style == 4 && chance(0.05)) ? borders[rnd(0, 5)] : 0;
+        add_motif(b, w, rnd(0, use_bins - 1), rnd(0, use_slots - 1), kind, reach, compact);
+    }
+    if (n && chance(0.25)) {                             // one candidate the validation must name
+        const uint32_t k = rnd(0, n - 1);
+        Batch one;
+        switch (rnd(0, 7)) {
+        case 0: b.slot[k] = (uint8_t)(chance(0.5) ? n_slots : rnd(8, 255)); if (b.slot[k] < 8 && (w.f.slot_present >> b.slot[k] & 1u)) b.slot[k] = 200; break;
+        case 1: b.bin[k] = n_bins + rnd(0, 3); break;
+        case 2: b.len[k] = chance(0.5) ? 0 : (uint8_t)rnd(192, 255); break;
+        case 3: b.mp[k] = (uint8_t)(b.len[k] + rnd(0, 3)); break;
+        case 4: add_motif(one, w, b.bin[k], b.slot[k], 3); break;
+        case 5: add_motif(one, w, b.bin[k], b.slot[k], 4); break;
+        case 6: add_motif(one, w, b.bin[k], b.slot[k], 0, 96); break;
+        case 7: add_motif(one, w, b.bin[k], b.slot[k], 0, 120); break;
+        }
+        if (one.size()) {
+            b.len[k] = one.len[0]; b.mp[k] = one.mp[0];
+            b.off[k] = (uint32_t)b.masks.size();
+            b.masks.insert(b.masks.end(), one.masks.begin() + one.off[0], one.masks.end());
+        }
+        if (b.len[k] > 14) b.masks.insert(b.masks.end(), 260, 15);          // (a forged length reads on: keep it inside the pool)
+    }
+    const int mode = (int)rnd(0, 9);                      // host counts, deferred, device counts, per-contig, spec
+    if (mode == 5) b.defer = true;
+    if (mode == 6) b.host_out = false;
+    if (mode == 7) {
+        add_rows(b, w);
+        if (n && chance(0.15)) { const uint32_t k = rnd(1, n); for (uint32_t q = k; q <= n; ++q) b.rows[q] += 1; }
+    }
+    if (mode == 8) { b.spec = true; b.stride = 64 * rnd(1, 3); b.extra_in = rnd(0, 5000); b.extra_out = rnd(0, 5000); }
+    run_case(("random " + std::to_string(i)).c_str(), w, b);
+}
+
+void clear_env() { for (const char *e : {"NM_ALL_SEGMENTS", "NM_STAGE_COPIES", "NM_SCORE_CLASSES", "NM_SCORE_HEAD"}) unsetenv(e); }
+
+// n candidates dealt round the groups (slot s, bin b), s < n_slots, b < use_bins
+Batch dealt(const World &w, uint32_t n, uint32_t use_bins, uint32_t n_slots, int kind) {
+    Batch b;
+    for (uint32_t k = 0; k < n; ++k) add_motif(b, w, k % use_bins, (k / use_bins) % n_slots, kind);
+    return b;
+}
+
+void directed_cases() {
+    clear_env();
+    {   // exactly 6 and 7 candidates per group: the light / heavy crossover
+        World w = make_world(10, 20, 2, 1.0);
+        for (uint32_t per : {6u, 7u}) {
+            const ScorePlan p = run_case("6 | 7 per group", w, dealt(w, per * 20, 10, 2, 1));
+            CHECK(p.light == (per == 6) && p.cf == p.light && p.classes == !p.light, "%u per group: light %d classes %d", per, p.light, p.classes);
+        }
+        const ScorePlan p = run_case("6 per group + 1", w, dealt(w, 121, 10, 2, 1));
+        CHECK(!p.light, "121 candidates in 20 groups are light");
+    }
+    {   // n_prog 2048 | 2049: the single-launch compile
+        World w = make_world(400, 3, 1, 1.0);
+        for (uint32_t n : {2048u, 2049u}) {
+            const ScorePlan p = run_case("n_prog 2048 | 2049", w, dealt(w, n, 400, 1, 0));
+            CHECK(p.cf && p.compile == (n == 2048 ? PLAN_COMPILE_FUSED : PLAN_COMPILE_THEN_COMMON), "%u light candidates compile by path %d", n, p.compile);
+        }
+    }
+    {   // n_entries 8192 | 8193
+        World w2 = make_world(4096, 1, 2, 1.0), w3 = make_world(2731, 1, 3, 1.0);
+        ScorePlan p = run_case("n_entries 8192", w2, dealt(w2, 2000, 1000, 2, 0));
+        CHECK(p.n_entries == 8192 && p.compile == PLAN_COMPILE_FUSED, "entries %u path %d", p.n_entries, p.compile);
+        p = run_case("n_entries 8193", w3, dealt(w3, 2001, 667, 3, 0));
+        CHECK(p.n_entries == 8193 && p.compile == PLAN_COMPILE_THEN_COMMON, "entries %u path %d", p.n_entries, p.compile);
+    }
+    for (uint32_t n : {8u, 16u, 400u}) {   // active segments at 4a = 3n and one more
+        World w = make_world(n, 1, 2, 1.0, 1);
+        const uint32_t a = 3 * n / 4;
+        ScorePlan p = run_case("4a = 3n", w, dealt(w, 3 * a, a, 1, 1));
+        CHECK(p.own_segments && p.n_segments == a, "%u of %u segments: own %d", a, n, p.own_segments);
+        p = run_case("4a = 3n + 4", w, dealt(w, 3 * (a + 1), a + 1, 1, 1));
+        CHECK(!p.own_segments && p.n_segments == n, "%u of %u segments: own %d", a + 1, n, p.own_segments);
+        setenv("NM_ALL_SEGMENTS", "1", 1);
+        p = run_case("4a = 3n, NM_ALL_SEGMENTS", w, dealt(w, 3 * a, a, 1, 1));
+        CHECK(!p.own_segments, "NM_ALL_SEGMENTS=1 and the batch's own table");
+        clear_env();
+    }
+    {   // staged bytes at 4 MiB and 16 bytes beyond: pad the mask pool until the total lands there
+        World w = make_world(1, 1, 1, 1.0);
+        for (size_t target : {(size_t)4 << 20, ((size_t)4 << 20) + 16}) {
+            Batch b = dealt(w, 1000, 1, 1, 0);
+            bind(w);
+            ScorePlan probe = run_case("staged bytes, probe", w, b);
+            b.masks.insert(b.masks.end(), target - probe.total, 15);
+            b.off.back() = (uint32_t)(b.masks.size() - b.len.back());        // the last candidate's motif moves to the end of the pool
+            for (uint32_t j = 0; j < b.len.back(); ++j) b.masks[b.off.back() + j] = j == b.mp.back() ? ((w.f.slot_is_c & 1u) ? NM_BASE_C : NM_BASE_A) : 15;
+            const ScorePlan p = run_case("staged bytes 4 MiB | + 16", w, b);
+            CHECK(p.total == target && p.by_kernels == (target == (size_t)4 << 20), "total %zu (wanted %zu), by_kernels %d", p.total, target, p.by_kernels);
+        }
+    }
+    {   // count bytes at 4 MiB and 16 bytes beyond
+        World w = make_world(1, 1, 1, 1.0);
+        Batch b = dealt(w, 10, 1, 1, 0);
+        for (uint32_t n : {262144u, 262145u}) {
+            Batch big;
+            for (uint32_t k = 0; k < n; ++k) { big.bin.push_back(0); big.slot.push_back(0); big.len.push_back(b.len[k % 10]); big.mp.push_back(b.mp[k % 10]); big.off.push_back(b.off[k % 10]); }
+            big.masks = b.masks;
+            const ScorePlan p = run_case("count bytes 4 MiB | + 16", w, big);
+            CHECK(p.out_bytes == (size_t)n * 16 && p.via_stage == (n == 262144) && !p.by_kernels, "%u candidates: via_stage %d by_kernels %d", n, p.via_stage, p.by_kernels);
+            big.defer = true;
+            const ScorePlan q = run_case("count bytes, deferred", w, big);
+            CHECK(q.via_stage, "a deferred batch comes back through the pair");
+        }
+    }
+    for (int split = -1; split <= 2; ++split)           // every NM_SPLIT x NM_FINE setting, small and large assemblies, light and heavy
+        for (int fine = -1; fine <= 2; ++fine)
+            for (uint32_t n_bins : {1u, 3u, 60u, 400u})
+                for (uint32_t per : {1u, 9u}) {
+                    World w = make_world(n_bins, 40, 2, 0.9);
+                    w.f.opt_split = split;
+                    w.f.opt_fine = fine;
+                    run_case("NM_SPLIT x NM_FINE", w, dealt(w, per * 2 * n_bins, n_bins, 2, 1));
+                    run_case("NM_SPLIT x NM_FINE, few bins", w, dealt(w, per * 2, 1, 2, 0));
+                }
+    for (uint32_t slots : {1u, 2u})                      // one and two active slots, with and without lit
+        for (int kind : {0, 1}) {
+            World w = make_world(12, 20, 2, 1.0);
+            const ScorePlan p = run_case("slots x lit", w, dealt(w, 3 * 12 * slots, 12, slots, kind));
+            CHECK(p.n_active == slots && p.lit == (kind == 0) && p.fuse == (slots == 2 && kind == 0) && p.gy == (p.fuse ? 1u : slots), "slots %u kind %d: lit %d fuse %d gy %u",
+                  slots, kind, p.lit, p.fuse, p.gy);
+            w.f.opt_no_lit = true;
+            const ScorePlan q = run_case("slots x lit, NM_NO_LIT", w, dealt(w, 3 * 12 * slots, 12, slots, kind));
+            CHECK(!q.lit && !q.fuse && q.np == 8, "NM_NO_LIT and a literal tile");
+        }
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 0) : 20240521ull;
+    const int n_random = argc > 2 ? atoi(argv[2]) : 3000;
+    rng.seed(seed);
+    directed_cases();
+    const long directed = g_cases;
+    for (int i = 0; i < n_random; ++i) random_case(i);
+    clear_env();
+    printf("plan_check ok: seed %" PRIu64 ", %ld directed + %d random batches (%ld rejected by the validation), %ld checks\n", seed, directed, n_random, g_rejected, g_checks);
+    return 0;
+}
