@@ -662,6 +662,32 @@ int nm_motif_fractions_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_
                              const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t n_bins,
                              uint64_t *counts);
 
+/* ---- MOTIF METHYLATION BY LOCAL GC CONTENT: the sites of a motif counted apart by the G + C around them ------------------------------
+ * Reference: none (its known-issues page names "high systematic 5mC noise in high GC% regions" and advises to check by hand).  A true
+ * methyltransferase motif is methylated whatever its surroundings; a noise motif where the local GC is high, and then so is the bin's
+ * background (the one-letter candidates "every A" / "every C").
+ *
+ * CANDIDATES, OCCURRENCES and their STATE (mod / nomod / nocall) are nm_motif_sites_count's: own modified base at '+' coordinate p,
+ *   occurrence strand s, the state read in cand_mod_slot on strand s at p.
+ * WINDOW of a site: the W = 2 half + 1 positions [p - half, p + half] of its contig, 0 <= half <= NM_GC_MAX_HALF.  g = the number of
+ *   G or C among the window's letters (the same on either strand), 0..W.  A site whose window leaves the contig or holds a letter that
+ *   is not A, C, G or T has no g: it is an EDGE site.  No floating point takes part; the caller rebins.
+ * ROW = (candidate, contig of its bin): contigs in nm_bin_contigs order from row cand_row0[k]; cand_row0[n_cand] = the rows of the
+ *   table, and cand_row0[k + 1] - cand_row0[k] must cover the contigs of the candidate's bin (the prefix of the bins' contig counts
+ *   does).  counts = int64[rows][2 (occurrence strand)][3 (mod, nomod, nocall)][W + 2]: the sites per g = 0..W, then the edge
+ *   sites; summed over the last axis it is the row of nm_motif_sites_count.  The caller's table need not be zeroed; rows no
+ *   candidate's contigs take hold 0.
+ * Launches: at most 3 (one per reach width) whatever the batch and half.  The work per site does not depend on W: the windowed sums
+ *   are built once per chunk from bit planes (csrc/nmgc.hip).
+ * NM_EINVAL for NULLs, half > NM_GC_MAX_HALF, a bad bin and rows that do not cover a bin — each checked before any device is touched,
+ * in the order of the other exports (bin, slot, program, rows, work items); NM_ESTATE without an assembly or for a slot without an
+ * uploaded pileup (per-strand planes); NM_ERANGE for a motif beyond NM_MAX_MOTIF_LEN / the reach limit and for 2^32 rows or work items.
+ * n_cand = 0 is NM_OK.  A refusal leaves the ctx usable. */
+#define NM_GC_MAX_HALF 31
+int nm_motif_gc_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot, const uint8_t *cand_len,
+                      const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t half,
+                      const uint64_t *cand_row0 /* [n_cand + 1] */, int64_t *counts);
+
 /* ---- per-contig READ methylation of motifs: the table binnary starts from -------------------------
  * Reference: nanomotif/main.py:142-193 — `contig_methylation = methylation_pattern(pileup, assembly, motifs,
  * min_valid_read_coverage, min_valid_cov_to_diff_fraction = 0.8, output_type = Median | WeightedMean)` from the

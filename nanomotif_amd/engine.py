@@ -46,6 +46,8 @@ FRACTIONS_BUDGET_BYTES = 256 << 20             # default size of the table of on
 UNEXPLAINED_DTYPE =np.dtype([("set", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])   # ScanEngine.unexplained_sites
 
 
+GC_MAX_HALF = 31                               # NM_GC_MAX_HALF: positions a GC window reaches either side of the modified base
+GC_BUDGET_BYTES = 256 << 20                    # default size of the table of one library call of ScanEngine.motif_gc
 KMER_MAX_FLANKS = 10                           # NM_KMER_MAX_FLANKS: counted positions of a k-mer shape ...
 KMER_MAX_OFFSET = 31                           # ... each within NM_KMER_MAX_OFFSET of the modified base
 KMER_BUDGET_BYTES = 256 << 20                  # default size of the tables of one library call of ScanEngine.kmer_methylation
@@ -1336,6 +1338,39 @@ class ScanEngine:
             _lib.check(self.lib.nm_motif_fractions_count(self.ctx, *self._batch_args(sub), nb, _ptr(table, C.c_uint64)))
             for j in range(k, e):
                 yield candidates[j], names[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
+
+    # ------------------------------------------------------------------ motif methylation by local GC content (nm_motif_gc_count)
+    def motif_gc(self, candidates, half=31, max_bytes=None):
+        """Generator over the sites of ``candidates`` (sequence of (Motif, mod_type, bin), or a CandidateBatch with slots from
+        ``slot_of_mod``, as ``motif_site_counts`` takes them) counted apart by the GC content around them (nm_motif_gc_count).  A site
+        is an occurrence of ``motif_site_counts`` with its state; its window is the W = 2 half + 1 positions centred on the modified
+        base, g the number of G or C among them.  Yields one item per candidate, in call order: (contig names in ``bin_contigs`` order,
+        int64[n_contigs, 2 (occurrence strand), 3 (mod, nomod, nocall), W + 2]) — the sites per g = 0..W and, last, the EDGE sites
+        whose window leaves the contig or holds a letter that is not A, C, G or T.  Summed over the last axis it is the row of
+        ``motif_site_counts``.  ``half``: 0..31.  Consecutive candidates share one library call while their tables fit ``max_bytes``
+        (default ``GC_BUDGET_BYTES``); a group always holds at least one candidate.  What is yielded does not depend on ``max_bytes``."""
+        half = int(half)
+        if not 0 <= half <= GC_MAX_HALF:
+            raise ValueError(f"half {half} outside 0..{GC_MAX_HALF}")
+        limit = GC_BUDGET_BYTES if max_bytes is None else int(max_bytes)
+        if limit < 1:
+            raise ValueError("max_bytes must be at least 1")
+        b = self._as_batch(candidates)
+        return self._gc_groups(b, half, limit)
+
+    def _gc_groups(self, b: CandidateBatch, half: int, limit: int):
+        bins = [int(x) for x in b.bins]
+        names = {bid: self.bin_contigs(bid) for bid in sorted(set(bins))}
+        width = 2 * half + 3
+        row_bytes = 6 * width * 8
+        for k, e, _ in _budget_groups([len(names[bid]) * row_bytes for bid in bins], limit):
+            rows = np.zeros(e - k + 1, dtype=np.uint64)
+            np.cumsum([len(names[bins[j]]) for j in range(k, e)], out=rows[1:])
+            table = np.zeros((max(int(rows[-1]), 1), 2, 3, width), dtype=np.int64)
+            sub = b.slice(k, e)
+            _lib.check(self.lib.nm_motif_gc_count(self.ctx, *self._batch_args(sub), half, _ptr(rows, C.c_uint64), _ptr(table, C.c_int64)))
+            for j in range(k, e):
+                yield names[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
 
     # ------------------------------------------------------------------ coverage of a set of motifs (nm_motif_coverage_*)
     def _coverage_args(self, sets):
