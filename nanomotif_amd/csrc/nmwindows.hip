@@ -313,8 +313,8 @@ __global__ __launch_bounds__(256) void bg_counts_kernel(Planes s, const uint32_t
             uint32_t k = sample_rank[begin + i];
             if (pad) k += base_popc(s, g0, pad, b);
             const uint64_t centre = select_kth(s, nullptr, b, rank + (size_t)c0 * RANK_PER_CHUNK, c0, nblk, k);
-            if (centre == ~0ull || centre < g0 + pad) {
-                atomicOr(err, 4u);                       // rank beyond the contig's valid starts
+            if (centre == ~0ull || centre < g0 + pad || centre + pad >= g0 + contig_len[ci]) {
+                atomicOr(err, 4u);                       // rank beyond the contig's valid starts (the base may stand in the last pad positions too)
                 on = false;
             } else {
                 fh = plane_field3(s.H, centre - pad, W);

@@ -209,20 +209,25 @@ def test_background_counts_from_runs_equal_counts_from_samples():
 
 
 @pytest.mark.parametrize("freq,per_bin", [(0.01, False), (0.05, False), (0.01, True)])
-def test_device_draws_equal_host_draws(freq, per_bin, monkeypatch):
+def test_device_draws_equal_host_draws(freq, per_bin, monkeypatch, capfd):
     """nm_plan_windows consumes the generator streams of all tasks on the device (bg_draw_kernel: one wave per stream over
     ONE sequence of MT19937 outputs) when they start from the same state: background PSSMs, window counts and the state
     the interpreter's generator is left in must equal the host-thread replay (NM_HOST_DRAWS=1) exactly.  freq 0.01: the
     set branch of random.sample; freq 0.05: samples so large that n <= setsize for most contigs, the pool branch;
-    per_bin: the bgzip task order, where the tasks of a bin share one stream."""
+    per_bin: the bgzip task order, where the tasks of a bin share one stream.  Which path drew is read from the NM_PLAN_TIMING line of
+    each leg: without it both legs may take the host path and the comparison says nothing (a pool call with k > 4096 sends the whole
+    plan there — at freq 0.05 every contig above 82 kbp with few enough valid starts, so that case has 1000 contigs of at most 54 kbp)."""
     import random
+    import re
     from nanomotif_amd import synth
     from nanomotif_amd.e2e_synth import load_and_filter
     from nanomotif_amd.engine import ScanEngine
     from nanomotif_amd.main import device_window_pipeline
     from nanomotif_amd.pileup import MOD_TYPES
     import torch
-    mg = synth.make_metagenome(synth.SynthSpec(n_contigs=400, total_bp=8_000_000, n_bins=40, mod_types=("a", "m"), seed=5))
+    mg = synth.make_metagenome(synth.SynthSpec(n_contigs=1000 if freq == 0.05 else 400, total_bp=8_000_000, n_bins=40, mod_types=("a", "m"),
+                                               seed=5))
+    monkeypatch.setenv("NM_PLAN_TIMING", "1")
     results = []
     for host in (True, False):
         if host:
@@ -245,7 +250,10 @@ def test_device_draws_equal_host_draws(freq, per_bin, monkeypatch):
                     tasks.append(((b, mt), names, mt))
         assert len(tasks) >= 32
         random.seed(99)
+        capfd.readouterr()
         pssms = extractor.plan_all(tasks, seed=1, one_stream_per_bin=per_bin)
+        lines = [ln for ln in capfd.readouterr().err.splitlines() if "[nm_plan_windows]" in ln]
+        assert len(lines) == 1 and re.search(r"\((device|host) draws\)", lines[0]).group(1) == ("host" if host else "device"), lines
         results.append((pssms, random.getstate(), dict(store.totals)))
         eng.close()
     (p_host, s_host, t_host), (p_dev, s_dev, t_dev) = results
