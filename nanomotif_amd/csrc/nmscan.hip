@@ -634,6 +634,11 @@ PlanFacts plan_facts(const nm_ctx *c) {
         f.slot_is_c |= (c->slots[sl].canonical == 'C' ? 1u : 0u) << sl;
     }
     f.n_segments = c->n_segments;
+    for (int w = 0; w < 2; ++w) {
+        f.list_start[w] = c->list_start[w].data();
+        f.list_len[w] = c->list_len[w].data();
+        f.list_segments[w] = c->n_list_segments[w];
+    }
     f.seg_chunks = c->seg_chunks;
     f.n_cus = c->n_cus;
     f.opt_no_lit = c->opt_no_lit;
@@ -734,7 +739,9 @@ int score_impl(nm_ctx *c, const ScoreRequest &rq) {
         a.st[s] = StatePlanes{ms.planes[0], ms.planes[1], ms.planes[2], ms.planes[3], ms.planes[4], ms.planes[5]};
         a.slot_is_c[s] = ms.canonical == 'C';
     }
-    a.segments = p.own_segments ? reinterpret_cast<const uint4 *>(r.ds + p.off_segs) : c->d_segments;
+    a.segments = p.own_segments ? reinterpret_cast<const uint4 *>(r.ds + p.off_segs) : p.use_list ? c->d_list_segments[p.pack] : c->d_segments;
+    a.work_list = c->d_work_list[p.pack];
+    a.strip_rows = c->d_strip_rows;
     a.n_segments = p.n_segments;
     a.n_bins = c->n_bins;
     a.programs = r.d_prog;
@@ -840,8 +847,17 @@ int nm_ctx_create(int device, nm_ctx **out) {
 static void free_assembly(nm_ctx *c) {
     drop_ingest_rows(c);
     nmdetail::free_readstats(c);
-    void *ptrs[] = {c->dH /* owns L and V too */, c->d_needs_v, c->d_contig_chunk, c->d_contig_len, c->d_segments, c->d_chunk_rank};
+    void *ptrs[] = {c->dH /* owns L and V too */, c->d_needs_v, c->d_contig_chunk, c->d_contig_len, c->d_segments, c->d_chunk_rank,
+                    c->d_work_list[0] /* owns both lists, the strips and the list segment tables */};
     c->d_chunk_rank = nullptr;
+    for (int w = 0; w < 2; ++w) {
+        c->d_work_list[w] = nullptr;
+        c->d_list_segments[w] = nullptr;
+        c->n_list_segments[w] = 0;
+        c->list_start[w].clear();
+        c->list_len[w].clear();
+    }
+    c->d_strip_rows = nullptr;
     for (void *p : ptrs)
         if (p) (void)nmdetail::dev_free(p);
     c->dH = c->dL = c->dV = nullptr;
@@ -1053,6 +1069,34 @@ static int upload_contigs_impl(nm_ctx *c, uint32_t n_contigs, const uint64_t *of
     HIP_TRY(hipMemcpyAsync(&other, c->d_other, sizeof other, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->other_letters = other;
+    {   // the work lists of the heavy kernels, plain and with the contigs' tails packed (nmscore_worklist.h), in one block:
+        // plain list | packed list | strips of the packed rows | (16-byte aligned) segments of the plain list | of the packed list
+        std::vector<uint8_t> needs_v(c->n_chunks);
+        HIP_TRY(hipMemcpy(needs_v.data(), c->d_needs_v, c->n_chunks, hipMemcpyDeviceToHost));
+        WorkList wl[2];
+        for (int w = 0; w < 2; ++w)
+            build_work_list(wl[w], w == 1, n_bins, n_contigs, order.data(), c->contig_bin.data(), c->contig_len.data(), c->contig_chunk.data(), needs_v.data(),
+                            c->n_chunks, c->seg_chunks);
+        const size_t o_list[2] = {0, wl[0].entries.size()}, o_strips = o_list[1] + wl[1].entries.size();
+        const size_t o_segs0 = (o_strips + wl[1].strip_rows.size() + 3) & ~(size_t)3, o_segs1 = o_segs0 + wl[0].segs.size() * 4;
+        const size_t o_segs[2] = {o_segs0, o_segs1}, total = o_segs1 + wl[1].segs.size() * 4;
+        std::vector<uint32_t> blob(std::max<size_t>(total, 4), 0);
+        for (int w = 0; w < 2; ++w) {
+            std::copy(wl[w].entries.begin(), wl[w].entries.end(), blob.begin() + o_list[w]);
+            if (!wl[w].segs.empty()) memcpy(blob.data() + o_segs[w], wl[w].segs.data(), wl[w].segs.size() * sizeof(PlanU4));
+        }
+        std::copy(wl[1].strip_rows.begin(), wl[1].strip_rows.end(), blob.begin() + o_strips);
+        HIP_TRY(nmdetail::dev_malloc(&c->d_work_list[0], blob.size() * 4));
+        HIP_TRY(hipMemcpy(c->d_work_list[0], blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+        c->d_work_list[1] = c->d_work_list[0] + o_list[1];
+        c->d_strip_rows = c->d_work_list[0] + o_strips;
+        for (int w = 0; w < 2; ++w) {
+            c->d_list_segments[w] = reinterpret_cast<uint4 *>(c->d_work_list[0] + o_segs[w]);
+            c->n_list_segments[w] = (uint32_t)wl[w].segs.size();
+            c->list_start[w] = std::move(wl[w].bin_start);
+            c->list_len[w] = std::move(wl[w].bin_len);
+        }
+    }
     guard.keep = true;
     return NM_OK;
 }

@@ -57,9 +57,27 @@ struct RawChunk {
     bool need_v;                                           // wave-uniform
 
     __device__ __forceinline__ void load(const Planes &seq, const StatePlanes (&stp)[K::NS], uint32_t chunk, int lane) {
-        constexpr int GN = K::GN, GP = K::GP;
         need_v = ((cu8p)seq.needs_v)[chunk] != 0;          // scalar load, issued first
-        const size_t base = (size_t)chunk * CHUNK_WORDS + (size_t)lane * T_WORDS;
+        load_at(seq, stp, (size_t)chunk * CHUNK_WORDS + (size_t)lane * T_WORDS);
+    }
+    // One entry of a work list (nmscore_worklist.h; the heavy variants that are not per-contig): a chunk with its needs_v bit, or
+    // a packed row, whose lanes take the strips strip_rows gives them — the partly filled last chunks of the bin's contigs, always
+    // with V.  Everything a lane uses hangs on its own base, so the walk, the counters and the flush do not see the difference.  A
+    // lane without a strip reads words 3 .. 10 of chunk 0, the zero pad in front of the space in every plane: V = 0 keeps it out
+    // of every count, as it keeps padding out (no branch, no lane switched off around the loads).
+    __device__ __forceinline__ void load_entry(const Planes &seq, const StatePlanes (&stp)[K::NS], uint32_t entry, const uint32_t *strip_rows, int lane) {
+        if (entry & WORK_PACKED) {                         // wave-uniform
+            const uint32_t w = strip_rows[(size_t)(entry & ~WORK_PACKED) * WORK_STRIPS + lane];
+            need_v = true;
+            load_at(seq, stp, (size_t)(w == WORK_NO_STRIP ? (uint32_t)T_WORDS : w));
+        } else {
+            need_v = (entry & WORK_NEED_V) != 0;
+            load_at(seq, stp, (size_t)(entry & (WORK_NEED_V - 1)) * CHUNK_WORDS + (size_t)lane * T_WORDS);
+        }
+    }
+    // base: the lane's first word in every plane; need_v is set
+    __device__ __forceinline__ void load_at(const Planes &seq, const StatePlanes (&stp)[K::NS], const size_t base) {
+        constexpr int GN = K::GN, GP = K::GP;
 #pragma unroll
         for (int j = 0; j < K::NS; ++j) {
             const uint32_t *src[4] = {K::COMPACT ? stp[j].M : stp[j].MP, K::COMPACT ? stp[j].U : stp[j].UP, stp[j].MM, stp[j].UM};
@@ -636,7 +654,7 @@ namespace nmdetail {
 struct ScoreArgs {
     Planes seq;
     StatePlanes st[NM_MAX_MOD_SLOTS];
-    const uint4 *segments;      // {first chunk, n chunks, bin, 0}
+    const uint4 *segments;      // {first chunk, n chunks, bin, 0}; a batch that walks a work list: {first entry, n entries, bin, 0}
     uint32_t n_segments;
     uint32_t split_log2;        // every segment is cut into 1 << split_log2 pieces
     uint32_t pieces_per_run, j_big, fine_log2;   // per run of pieces: the first j_big go whole, the rest in 1 << fine_log2 parts
@@ -649,6 +667,8 @@ struct ScoreArgs {
     const uint64_t *row_base;   // [n_prog] sorted order (per-contig mode)
     uint32_t active_slot[NM_MAX_MOD_SLOTS];
     uint32_t slot_is_c[NM_MAX_MOD_SLOTS];   // canonical base of the slot is C (else A)
+    const uint32_t *work_list;  // heavy variants that are not per-contig: the entries the segments index (nmscore_worklist.h),
+    const uint32_t *strip_rows; // and the 64 strips of every packed row
 };
 
 // the CLS variants (Variant<1, 1, true, 1, false, false, PC, true>): instantiated by nmscore_classes.hip
@@ -954,13 +974,15 @@ __device__ __forceinline__ void score_piece(const ScoreArgs &a, const uint4 sg, 
         flush_rows(rows_hi, 0);
         pass0 = H;
     }
+    constexpr bool LIST = !K::CF && !K::PC;          // sg is a range of work-list entries (one scalar load each, where the needs_v byte was)
     for (; pass0 < most; pass0 += H) {
         const uint32_t rows_hi = NS * min(H, most - pass0);
         clear_rows(rows_hi);
         for (uint32_t ck = wave; ck < sg.y; ck += 4) {
             RawChunk<K> cur;
-            cur.load(a.seq, stp, sg.x + ck, lane);
-            score_chunk(cur, pass0, sg.x + ck);
+            if constexpr (LIST) cur.load_entry(a.seq, stp, ((cu32p)a.work_list)[sg.x + ck], a.strip_rows, lane);
+            else cur.load(a.seq, stp, sg.x + ck, lane);
+            score_chunk(cur, pass0, LIST ? 0u : sg.x + ck);
         }
         flush_rows(rows_hi, pass0);
     }
@@ -985,44 +1007,25 @@ __device__ __forceinline__ void score_piece(const ScoreArgs &a, const uint4 sg, 
 template <class K>
 __global__ NM_SCORE_BOUNDS void score_kernel(ScoreArgs a) {
     __shared__ uint32_t lds_acc[BMAX * 2 * 64];
-    // XCD-aware remap: blocks b and b+8 share an XCD (round-robin dispatch), give every XCD a contiguous run
-    // of segments so candidate programs and counters of one bin stay in one L2.
-    // (a light batch streams: there the remap costs 3 % of the read rate, tools/stream_pattern.hip)
-    const uint32_t lanes_x = K::CF ? 1u : 8u;                  // runs of pieces: one per XCD, or a single one
-    const uint32_t x = K::CF ? 0u : blockIdx.x % 8, j = K::CF ? blockIdx.x : blockIdx.x / 8;
-    // Pieces: a segment (16 chunks), or a half / quarter of one for assemblies that fill the device for less than two
-    // rounds of workgroups (split_log2).  The workgroups dispatched LAST (j >= j_big in every run) take pieces cut
-    // finer still (fine_log2): the last, partly filled round of workgroups then lasts a quarter as long.
-    uint32_t piece, sub = 0, n_sub = 1;
-    if (j < a.j_big) piece = x * a.pieces_per_run + j;
+    // the workgroup's piece of the segment table (nmscore_plan.h: plan_block_piece and plan_cut_piece, shared with the host check —
+    // the XCD-aware runs, the split and the finer cut of the pieces dispatched last)
+    const PlanGrid grid{a.n_segments, a.split_log2, a.pieces_per_run, a.j_big, a.fine_log2};
+    uint32_t piece, sub, n_sub;
+    if (!plan_block_piece(grid, K::CF, blockIdx.x, &piece, &sub, &n_sub)) return;
+    // a heavy variant reads its segment through the constant address space (a scalar load: the workgroup's first dependent read, the
+    // candidate range of the segment's bin, starts from an SGPR); a streaming CF variant keeps the vector load it had
+    // (profiles/r23/tail_pack.md: neither choice is worth more than the run-to-run spread)
+    typedef const uint4 __attribute__((address_space(4))) *cu4p;
+    uint4 sg;
+    if constexpr (K::CF) sg = a.segments[piece >> a.split_log2];
     else {
-        const uint32_t k = j - a.j_big;
-        piece = x * a.pieces_per_run + a.j_big + (k >> a.fine_log2);
-        sub = k & ((1u << a.fine_log2) - 1);
-        n_sub = 1u << a.fine_log2;
-        if (a.j_big + (k >> a.fine_log2) >= a.pieces_per_run) return;
+        const cu4p seg = (cu4p)a.segments + (piece >> a.split_log2);
+        sg.x = seg->x; sg.y = seg->y; sg.z = seg->z; sg.w = 0;
     }
-    (void)lanes_x;
-    const uint32_t seg = piece >> a.split_log2;
-    if (seg >= a.n_segments) return;
-    uint4 sg = a.segments[seg];
     sg.x = __builtin_amdgcn_readfirstlane(sg.x);   // everything below is wave-uniform: keep it in SGPRs
     sg.y = __builtin_amdgcn_readfirstlane(sg.y);
     sg.z = __builtin_amdgcn_readfirstlane(sg.z);
-    if (a.split_log2) {
-        const uint32_t len = (sg.y + (1u << a.split_log2) - 1) >> a.split_log2;
-        const uint32_t at = (piece & ((1u << a.split_log2) - 1)) * len;
-        if (at >= sg.y) return;
-        sg.x += at;
-        sg.y = min(len, sg.y - at);
-    }
-    if (n_sub > 1) {
-        const uint32_t len = (sg.y + n_sub - 1) / n_sub;
-        const uint32_t at = sub * len;
-        if (at >= sg.y) return;
-        sg.x += at;
-        sg.y = min(len, sg.y - at);
-    }
+    if (!plan_cut_piece(grid, piece, sub, n_sub, &sg.x, &sg.y)) return;
     NM_SLOT_SETUP
     score_piece<K>(a, sg, stp, is_c, lds_acc, lane, wave);
 }

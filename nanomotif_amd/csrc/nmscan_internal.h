@@ -16,6 +16,7 @@
 
 #include "../../include/nmscan.h"
 #include "nmscore_plan.h"
+#include "nmscore_worklist.h"
 #include "nmspec.h"
 
 // error sink shared by all translation units (defined in nmscan.hip; the text is what nm_last_error() returns)
@@ -153,6 +154,12 @@ struct nm_ctx {
     uint64_t *d_contig_len = nullptr;
     uint4 *d_segments = nullptr;
     uint32_t n_segments = 0;
+    // work lists of the heavy kernels (nmscore_worklist.h), [0] plain, [1] contig tails packed: one allocation (d_work_list[0] owns
+    // it) holding both lists, the packed rows' strips and both static segment tables over list positions
+    uint32_t *d_work_list[2] = {nullptr, nullptr}, *d_strip_rows = nullptr;
+    uint4 *d_list_segments[2] = {nullptr, nullptr};
+    uint32_t n_list_segments[2] = {0, 0};
+    std::vector<uint32_t> list_start[2], list_len[2];
     nmdetail::ModSlot slots[NM_MAX_MOD_SLOTS];
     nmdetail::ReadStats readstats[NM_MAX_MOD_SLOTS];   // nm_readstats_upload (per-contig read methylation, nmmeth.hip)
     uint32_t *d_chunk_contig = nullptr;                // per chunk: its contig, ~0 for pad chunks (built on first use)

@@ -54,6 +54,10 @@ struct PlanFacts {
     uint32_t n_segments = 0, seg_chunks = 16, n_cus = 256;
     bool opt_no_lit = false, opt_no_cf = false, opt_no_inline = false;
     int opt_fine = -1, opt_split = -1;
+    // the work lists of the heavy kernels (nmscore_worklist.h), [0] plain, [1] contig tails packed: per bin its first entry and its
+    // entries, and the segments of the static table over list positions.  NULL: no lists, the chunk table serves every batch
+    const uint32_t *list_start[2] = {nullptr, nullptr}, *list_len[2] = {nullptr, nullptr};
+    uint32_t list_segments[2] = {0, 0};
 };
 
 enum PlanCompile { PLAN_COMPILE_NONE, PLAN_COMPILE_FUSED, PLAN_COMPILE_ONLY, PLAN_COMPILE_THEN_COMMON, PLAN_COMPILE_SPEC };
@@ -70,6 +74,7 @@ struct ScorePlan {
     int slot_to_active[NM_MAX_MOD_SLOTS] = {};
     uint32_t n_active_bins = 0, n_groups = 0;
     size_t n_active_segs = 0;
+    bool use_list = false, pack = false;                // the batch walks a work list (heavy, not per-contig), the one with packed tails
     uint64_t out_rows = 0;
     // ---- shape
     bool lit = false, light = false, cf = false, classes = false, cls_head = true, fuse = false;
@@ -88,6 +93,65 @@ struct ScorePlan {
 };
 
 inline size_t plan_align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+#if defined(__HIPCC__)
+#define NM_PLAN_HD __host__ __device__ __forceinline__
+#else
+#define NM_PLAN_HD inline
+#endif
+
+// The grid of a launch as score_kernel reads it (plan_geometry decides it).
+struct PlanGrid { uint32_t n_segments, split_log2, pieces_per_run, j_big, fine_log2; };
+
+// Workgroup `block` of the x dimension -> its piece of work, in the two steps score_kernel takes around its read of the segment
+// table.  The grid is `runs` runs of pieces (8: the heavy variants — blocks b and b + 8 share an XCD under round-robin dispatch, so
+// every XCD gets a contiguous run of segments and the programs and counters of one bin stay in one L2; 1: the streaming CF variants,
+// where the remap costs 3 % of the read rate, tools/stream_pattern.hip).  A piece is a segment, or a half / quarter of one for
+// assemblies that fill the device for less than two rounds of workgroups (split_log2); the workgroups dispatched LAST (j >= j_big
+// in every run) take pieces cut finer still (fine_log2): the last, partly filled round of workgroups then lasts a quarter as long.
+// plan_block_piece: the piece, and which part of it (sub of n_sub); false: the workgroup has none and leaves.
+NM_PLAN_HD bool plan_block_piece(const PlanGrid &g, bool cf, uint32_t block, uint32_t *piece, uint32_t *sub, uint32_t *n_sub) {
+    const uint32_t x = cf ? 0u : block % 8, j = cf ? block : block / 8;
+    *sub = 0;
+    *n_sub = 1;
+    if (j < g.j_big) *piece = x * g.pieces_per_run + j;
+    else {
+        const uint32_t k = j - g.j_big;
+        *piece = x * g.pieces_per_run + g.j_big + (k >> g.fine_log2);
+        *sub = k & ((1u << g.fine_log2) - 1);
+        *n_sub = 1u << g.fine_log2;
+        if (g.j_big + (k >> g.fine_log2) >= g.pieces_per_run) return false;
+    }
+    return (*piece >> g.split_log2) < g.n_segments;    // its segment: piece >> split_log2
+}
+// plan_cut_piece: the piece's share [*first, *first + *count) of its segment's entries (in: the whole segment); false: an empty share.
+NM_PLAN_HD bool plan_cut_piece(const PlanGrid &g, uint32_t piece, uint32_t sub, uint32_t n_sub, uint32_t *first, uint32_t *count) {
+    if (g.split_log2) {
+        const uint32_t len = (*count + (1u << g.split_log2) - 1) >> g.split_log2;
+        const uint32_t at = (piece & ((1u << g.split_log2) - 1)) * len;
+        if (at >= *count) return false;
+        *first += at;
+        *count = len < *count - at ? len : *count - at;
+    }
+    if (n_sub > 1) {
+        const uint32_t len = (*count + n_sub - 1) / n_sub;
+        const uint32_t at = sub * len;
+        if (at >= *count) return false;
+        *first += at;
+        *count = len < *count - at ? len : *count - at;
+    }
+    return true;
+}
+// Both steps around a table in host memory: what tools/plan_check/driver.cpp walks to show that a planned grid reaches every entry
+// of its table (chunks of the chunk table, positions of a work list) exactly once.
+inline bool plan_decode_block(const PlanGrid &g, bool cf, uint32_t block, const PlanU4 *segments, uint32_t *seg, uint32_t *first, uint32_t *count) {
+    uint32_t piece, sub, n_sub;
+    if (!plan_block_piece(g, cf, block, &piece, &sub, &n_sub)) return false;
+    *seg = piece >> g.split_log2;
+    *first = segments[*seg].x;
+    *count = segments[*seg].y;
+    return plan_cut_piece(g, piece, sub, n_sub, first, count);
+}
 
 inline int plan_fail(ScorePlan &p, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
 inline int plan_fail(ScorePlan &p, int code, const char *fmt, ...) {
@@ -127,6 +191,9 @@ inline uint32_t number_active_slots(const bool used[NM_MAX_MOD_SLOTS], int slot_
     }
     return n;
 }
+
+// light: <= 6 candidates per (slot, bin) group on average (plan_shape)
+inline bool plan_is_light(const ScorePlan &p) { return (uint64_t)p.n_prog <= 6ull * p.n_groups && !p.per_contig; }
 
 // ---- 1. one pass over the candidates: validate, classify the batch, count per (slot, bin) bucket.
 // bucket: NM_MAX_MOD_SLOTS * n_bins + 1 zeroed words, entry slot * n_bins + bin + 1 counts the group; bin_active: n_bins zeroed bytes.
@@ -173,7 +240,12 @@ inline int plan_classify(ScorePlan &p, const ScoreRequest &rq, const PlanFacts &
             if (rq.row_offset[k + 1] - rq.row_offset[k] != f.bin_ncontigs[rq.bin[k]])
                 return plan_fail(p, NM_EINVAL, "candidate %u: %llu output rows for a bin of %u resident contigs", k,
                                  (unsigned long long)(rq.row_offset[k + 1] - rq.row_offset[k]), f.bin_ncontigs[rq.bin[k]]);
-    // the bins the batch has candidates for, their segments, and the (slot, bin) groups
+    // the bins the batch has candidates for, their segments, and the (slot, bin) groups.  A heavy batch that is not per-contig walks
+    // a work list (nmscore_worklist.h), the one with packed tails unless NM_SCORE_PACK_TAILS=0 (read at every call, like
+    // NM_SCORE_CLASSES: same-process A/B, tests/test_gpu_score_tail_pack.py); its segments are cut over list positions
+    const char *pack_env = getenv("NM_SCORE_PACK_TAILS");
+    const int which = pack_env && atoi(pack_env) == 0 ? 0 : 1;
+    size_t list_segs = 0;
     for (uint32_t b = 0; b < n_bins; ++b) {
         uint32_t groups = 0;
         for (uint32_t i = 0; i < p.n_active; ++i) groups += bucket[(size_t)p.active[i] * n_bins + b + 1] > 0;
@@ -182,7 +254,11 @@ inline int plan_classify(ScorePlan &p, const ScoreRequest &rq, const PlanFacts &
         bin_active[b] = 1;
         p.n_active_bins += 1;
         p.n_active_segs += (f.bin_nchunks[b] + f.seg_chunks - 1) / f.seg_chunks;
+        if (f.list_len[which]) list_segs += (f.list_len[which][b] + f.seg_chunks - 1) / f.seg_chunks;
     }
+    p.use_list = f.list_len[which] && !p.per_contig && !(plan_is_light(p) && !f.opt_no_cf);
+    p.pack = p.use_list && which == 1;
+    if (p.use_list) p.n_active_segs = list_segs;
     return NM_OK;
 }
 
@@ -193,7 +269,7 @@ inline void plan_shape(ScorePlan &p, const ScoreRequest &rq, const PlanFacts &f)
     p.lit = p.all_literal && p.all_compact && !p.any_wide && !f.opt_no_lit && !p.per_contig;   // literal-only tiles exist for the narrow compact kernels
     p.np = p.lit ? 4u : 8u;
     p.pdw = 2u * (2u + 2u * (uint32_t)p.any_wide) * p.np;          // dwords per program: [strand][word-group][plane]
-    p.light = (uint64_t)p.n_prog <= 6ull * p.n_groups && !p.per_contig;
+    p.light = plan_is_light(p);
     p.cf = p.light && !f.opt_no_cf;
     p.fuse = p.n_active == 2 && p.cf && p.lit;          // (fusing two slots on the 8-plane tile needs 128 VGPRs)
     // IUPAC classes: exactly the batches that launch Variant<1, 1, true, 1, false, false, PC> take the class-plane twin of
@@ -207,8 +283,9 @@ inline void plan_shape(ScorePlan &p, const ScoreRequest &rq, const PlanFacts &f)
     // The static segment table covers every bin; a batch whose candidates sit in a few bins only — the long tail of the
     // search: a handful of tasks still open among hundreds of bins — would launch thousands of workgroups that find no
     // candidate range and leave.  Such a batch brings its own table: the segments of the bins it has candidates for.
-    p.own_segments = p.n_prog && p.n_active_segs * 4 <= (size_t)f.n_segments * 3 && getenv("NM_ALL_SEGMENTS") == nullptr;
-    p.n_segments = p.own_segments ? (uint32_t)p.n_active_segs : f.n_segments;
+    const uint32_t static_segments = p.use_list ? f.list_segments[p.pack] : f.n_segments;
+    p.own_segments = p.n_prog && p.n_active_segs * 4 <= (size_t)static_segments * 3 && getenv("NM_ALL_SEGMENTS") == nullptr;
+    p.n_segments = p.own_segments ? (uint32_t)p.n_active_segs : static_segments;
     p.n_entries = std::max(p.n_active, 1u) * f.n_bins;
     // a light batch appends one common program per (slot, bin) entry
     p.prog_dw = ((size_t)std::max(p.n_prog, 1u) + (p.cf ? p.n_entries : 0)) * p.pdw;
@@ -260,11 +337,12 @@ inline void plan_fill(const ScorePlan &p, const ScoreRequest &rq, const PlanFact
     memset(h_range, 0, p.range_bytes);
     if (p.own_segments) {
         PlanU4 *h_segs = reinterpret_cast<PlanU4 *>(hs + p.off_segs);
+        const uint32_t *first = p.use_list ? f.list_start[p.pack] : f.bin_chunk0, *count = p.use_list ? f.list_len[p.pack] : f.bin_nchunks;
         size_t at = 0;
         for (uint32_t b = 0; b < n_bins; ++b)
             if (bin_active[b])
-                for (uint32_t k = 0; k < f.bin_nchunks[b]; k += f.seg_chunks)
-                    h_segs[at++] = PlanU4{f.bin_chunk0[b] + k, std::min<uint32_t>(f.seg_chunks, f.bin_nchunks[b] - k), b, 0};
+                for (uint32_t k = 0; k < count[b]; k += f.seg_chunks)
+                    h_segs[at++] = PlanU4{first[b] + k, std::min<uint32_t>(f.seg_chunks, count[b] - k), b, 0};
     }
     const size_t n_bucket = (size_t)NM_MAX_MOD_SLOTS * n_bins + 1;
     for (size_t i = 1; i < n_bucket; ++i) bucket[i] += bucket[i - 1];

@@ -1,5 +1,6 @@
 // Stand-alone check of the scoring plan (nanomotif_amd/csrc/nmscore_plan.h) on the CPU: random and directed batches, every
-// plan compared with a plain restatement written here.  Build: g++ -O2 -std=c++17 driver.cpp -o plan_check; run: ./plan_check [seed]
+// plan compared with a plain restatement written here, the work lists of the heavy kernels (nmscore_worklist.h) included: the grid
+// of every planned batch reaches every strip of sequence of every active bin exactly once.  Build: g++ -O2 -std=c++17 driver.cpp -o plan_check; run: ./plan_check [seed]
 // (tests/test_score_plan_host.py does both, a second time with -fsanitize=address,undefined where that links).
 #include <cinttypes>
 #include <cstdarg>
@@ -9,6 +10,7 @@
 #include <vector>
 
 #include "../../nanomotif_amd/csrc/nmscore_plan.h"
+#include "../../nanomotif_amd/csrc/nmscore_worklist.h"
 
 using namespace nmdetail;
 
@@ -36,7 +38,37 @@ struct World {                                          // an uploaded assembly 
     std::vector<PlanU4> static_segs;
     uint32_t n_chunks = 0;
     PlanFacts f;
+    // the contigs behind the chunks and the work lists built from them (nmscore_worklist.h); lists = false: an engine without lists
+    std::vector<uint32_t> contig_bin, contig_chunk;
+    std::vector<uint64_t> contig_len;
+    WorkList wl[2];
+    bool lists = true;
 };
+
+// a contig of exactly `chunks` chunks (its 96 bp of gap included)
+uint64_t contig_of_chunks(uint32_t chunks) {
+    const uint64_t hi = (uint64_t)chunks * 8192 - 96, lo = chunks > 1 ? hi - 8191 : 1;
+    return chance(0.15) ? hi : chance(0.15) ? (hi / 8192) * 8192 + (chunks > 1 || hi >= 8192 ? 0 : 1) : lo + rng() % (hi - lo + 1);
+}
+
+void add_contig(World &w, uint32_t bin, uint64_t len, uint32_t chunk) {
+    w.contig_bin.push_back(bin);
+    w.contig_len.push_back(len);
+    w.contig_chunk.push_back(chunk);
+}
+
+// needs_v as the geometry alone decides it (no N in the sequence): a contig's first chunk, and every chunk whose own positions or
+// the 96 behind it are not all inside the contig
+void build_lists(World &w) {
+    std::vector<uint8_t> needs_v(w.n_chunks, 1);
+    for (size_t i = 0; i < w.contig_len.size(); ++i)
+        for (uint64_t q = 1; (q + 1) * 8192 + 96 <= w.contig_len[i]; ++q) needs_v[w.contig_chunk[i] + q] = 0;
+    std::vector<uint32_t> order(w.contig_bin.size());
+    std::iota(order.begin(), order.end(), 0u);          // (the worlds are made bin by bin)
+    for (int pack = 0; pack < 2; ++pack)
+        build_work_list(w.wl[pack], pack == 1, w.f.n_bins, (uint32_t)order.size(), order.data(), w.contig_bin.data(), w.contig_len.data(), w.contig_chunk.data(),
+                        needs_v.data(), w.n_chunks, w.f.seg_chunks);
+}
 
 World make_world(uint32_t n_bins, uint32_t max_chunks, uint32_t n_slots, double resident = 0.85, int fixed_chunks = -1) {
     World w;
@@ -49,7 +81,13 @@ World make_world(uint32_t n_bins, uint32_t max_chunks, uint32_t n_slots, double 
         w.nchunks[b] = fixed_chunks >= 0 ? (uint32_t)fixed_chunks : chance(resident) ? rnd(1, max_chunks) : 0;
         if (!w.nchunks[b]) continue;
         w.chunk0[b] = next;
-        w.ncontigs[b] = rnd(1, 4);
+        w.ncontigs[b] = rnd(1, std::min(4u, w.nchunks[b]));
+        for (uint32_t k = 0, left = w.nchunks[b], at = next; k < w.ncontigs[b]; ++k) {        // the bin's chunks dealt to its contigs
+            const uint32_t mine = k + 1 == w.ncontigs[b] ? left : rnd(1, left - (w.ncontigs[b] - 1 - k));
+            add_contig(w, b, contig_of_chunks(mine), at);
+            at += mine;
+            left -= mine;
+        }
         for (uint32_t k = 0; k < w.nchunks[b]; k += w.f.seg_chunks)
             w.static_segs.push_back(PlanU4{next + k, std::min(w.f.seg_chunks, w.nchunks[b] - k), b, 0});
         next += w.nchunks[b];
@@ -62,6 +100,35 @@ World make_world(uint32_t n_bins, uint32_t max_chunks, uint32_t n_slots, double 
         if (chance(0.5)) w.f.slot_is_c |= 1u << s;
     }
     w.f.n_cus = chance(0.7) ? 256 : rnd(1, 304);
+    build_lists(w);
+    return w;
+}
+
+// bins given contig by contig: lengths[b] = the contigs of bin b
+World make_world_of(const std::vector<std::vector<uint64_t>> &lengths, uint32_t seg_chunks, uint32_t n_slots) {
+    World w;
+    const uint32_t n_bins = (uint32_t)lengths.size();
+    w.nchunks.assign(n_bins, 0);
+    w.chunk0.assign(n_bins, 0);
+    w.ncontigs.assign(n_bins, 0);
+    w.f.seg_chunks = seg_chunks;
+    uint32_t next = 1;
+    for (uint32_t b = 0; b < n_bins; ++b) {
+        if (!lengths[b].empty()) w.chunk0[b] = next;
+        for (uint64_t len : lengths[b]) {
+            const uint32_t nch = (uint32_t)((len + 96 + 8191) / 8192);
+            add_contig(w, b, len, next);
+            next += nch;
+            w.nchunks[b] += nch;
+            w.ncontigs[b] += 1;
+        }
+        for (uint32_t k = 0; k < w.nchunks[b]; k += seg_chunks) w.static_segs.push_back(PlanU4{w.chunk0[b] + k, std::min(seg_chunks, w.nchunks[b] - k), b, 0});
+    }
+    w.n_chunks = next + 1;
+    w.f.n_bins = n_bins;
+    w.f.n_segments = (uint32_t)w.static_segs.size();
+    for (uint32_t s = 0; s < n_slots; ++s) w.f.slot_present |= 1u << s;
+    build_lists(w);
     return w;
 }
 
@@ -69,6 +136,11 @@ void bind(World &w) {                                   // (the vectors may have
     w.f.bin_nchunks = w.nchunks.data();
     w.f.bin_chunk0 = w.chunk0.data();
     w.f.bin_ncontigs = w.ncontigs.data();
+    for (int pack = 0; pack < 2; ++pack) {
+        w.f.list_start[pack] = w.lists ? w.wl[pack].bin_start.data() : nullptr;
+        w.f.list_len[pack] = w.lists ? w.wl[pack].bin_len.data() : nullptr;
+        w.f.list_segments[pack] = w.lists ? (uint32_t)w.wl[pack].segs.size() : 0;
+    }
 }
 
 struct Batch {
@@ -165,39 +237,11 @@ std::pair<int, uint32_t> brute_validate(const Batch &b, const World &w) {
     return {NM_OK, 0};
 }
 
-// One workgroup's chunks, restated from the block decode of score_kernel (nmscan_device.h:996-1025): cf = the K::CF numbering
-// (a single run of pieces) or the XCD-remapped one (eight runs).  false: the workgroup leaves without a piece.
+// One workgroup's piece of the table: plan_decode_block (nmscore_plan.h), composed of the two functions score_kernel calls.
 bool decode_block(const ScorePlan &p, bool cf, uint32_t block, const PlanU4 *segments, uint32_t *first, uint32_t *count) {
-    const uint32_t x = cf ? 0u : block % 8, j = cf ? block : block / 8;
-    uint32_t piece, sub = 0, n_sub = 1;
-    if (j < p.j_big) piece = x * p.pieces_per_run + j;
-    else {
-        const uint32_t k = j - p.j_big;
-        piece = x * p.pieces_per_run + p.j_big + (k >> p.fine_log2);
-        sub = k & ((1u << p.fine_log2) - 1);
-        n_sub = 1u << p.fine_log2;
-        if (p.j_big + (k >> p.fine_log2) >= p.pieces_per_run) return false;
-    }
-    const uint32_t seg = piece >> p.split_log2;
-    if (seg >= p.n_segments) return false;
-    uint32_t sx = segments[seg].x, sy = segments[seg].y;
-    if (p.split_log2) {
-        const uint32_t len = (sy + (1u << p.split_log2) - 1) >> p.split_log2;
-        const uint32_t at = (piece & ((1u << p.split_log2) - 1)) * len;
-        if (at >= sy) return false;
-        sx += at;
-        sy = std::min(len, sy - at);
-    }
-    if (n_sub > 1) {
-        const uint32_t len = (sy + n_sub - 1) / n_sub;
-        const uint32_t at = sub * len;
-        if (at >= sy) return false;
-        sx += at;
-        sy = std::min(len, sy - at);
-    }
-    *first = sx;
-    *count = sy;
-    return true;
+    const PlanGrid g{p.n_segments, p.split_log2, p.pieces_per_run, p.j_big, p.fine_log2};
+    uint32_t seg = 0;
+    return plan_decode_block(g, cf, block, segments, &seg, first, count);
 }
 
 std::vector<uint32_t> g_bucket;
@@ -254,7 +298,9 @@ ScorePlan run_case(const char *name, World &w, const Batch &b) {
           p.any_wide, p.all_compact, p.all_literal, wide, compact, literal);
     CHECK(p.mask_lo == lo && p.mask_hi == hi, "mask bytes [%" PRIu64 ", %" PRIu64 "), expected [%" PRIu64 ", %" PRIu64 ")", p.mask_lo, p.mask_hi, lo, hi);
     uint32_t n_active = 0, n_act_bins = 0, n_groups = 0;
-    size_t n_act_segs = 0;
+    size_t n_act_segs = 0, n_act_list_segs = 0;
+    const int pack = env_zero("NM_SCORE_PACK_TAILS") ? 0 : 1;
+    const WorkList &wl = w.wl[pack];
     for (int s = 0; s < NM_MAX_MOD_SLOTS; ++s) {
         CHECK(p.slot_to_active[s] == (slot_used[s] ? (int)n_active : -1), "slot %d numbered %d", s, p.slot_to_active[s]);
         if (slot_used[s]) { CHECK(p.active[n_active] == (uint32_t)s, "active[%u] = %u, expected %d", n_active, p.active[n_active], s); ++n_active; }
@@ -262,9 +308,15 @@ ScorePlan run_case(const char *name, World &w, const Batch &b) {
     for (uint32_t bb = 0; bb < n_bins; ++bb) {
         CHECK(g_bin_active[bb] == bin_used[bb], "bin %u active %d, expected %d", bb, g_bin_active[bb], bin_used[bb]);
         if (bin_used[bb]) { ++n_act_bins; n_act_segs += (w.nchunks[bb] + f.seg_chunks - 1) / f.seg_chunks; }
+        if (bin_used[bb] && w.lists) n_act_list_segs += (wl.bin_len[bb] + f.seg_chunks - 1) / f.seg_chunks;
     }
     for (size_t i = 0; i < order.size(); ++i)
         if (i == 0 || b.slot[order[i]] != b.slot[order[i - 1]] || b.bin[order[i]] != b.bin[order[i - 1]]) ++n_groups;
+    // a heavy batch that is not per-contig walks the work list: its segments are counted over list positions
+    const bool use_list = w.lists && !b.per_contig && !(order.size() <= 6 * (size_t)n_groups && !f.opt_no_cf);
+    CHECK(p.use_list == use_list && p.pack == (use_list && pack == 1), "use_list %d pack %d, expected %d %d", p.use_list, p.pack, use_list, use_list && pack == 1);
+    if (use_list) n_act_segs = n_act_list_segs;
+    const size_t n_static = use_list ? wl.segs.size() : f.n_segments;
     CHECK(p.n_active == n_active && p.n_active_bins == n_act_bins && p.n_active_segs == n_act_segs && p.n_groups == n_groups,
           "active slots %u bins %u segments %zu groups %u, expected %u %u %zu %u", p.n_active, p.n_active_bins, p.n_active_segs, p.n_groups, n_active,
           n_act_bins, n_act_segs, n_groups);
@@ -274,7 +326,7 @@ ScorePlan run_case(const char *name, World &w, const Batch &b) {
     const bool lit = literal && compact && !wide && !f.opt_no_lit && !b.per_contig;
     const bool light = !b.per_contig && order.size() <= 6 * (size_t)n_groups, cf = light && !f.opt_no_cf;
     const bool classes = !b.spec && !lit && !wide && compact && !cf && !env_zero("NM_SCORE_CLASSES");
-    const bool own = !order.empty() && 4 * n_act_segs <= 3 * (size_t)f.n_segments && !getenv("NM_ALL_SEGMENTS");
+    const bool own = !order.empty() && 4 * n_act_segs <= 3 * n_static && !getenv("NM_ALL_SEGMENTS");
     const uint32_t n_entries = std::max(n_active, 1u) * n_bins, np = lit ? 4 : 8, pdw = np * (wide == 0 ? 4 : wide == 1 ? 8 : 12);
     CHECK(p.lit == lit && p.light == light && p.cf == cf && p.classes == classes && p.fuse == (n_active == 2 && cf && lit) && p.own_segments == own,
           "shape lit %d light %d cf %d classes %d fuse %d own %d, expected %d %d %d %d %d %d", p.lit, p.light, p.cf, p.classes, p.fuse, p.own_segments, lit,
@@ -344,22 +396,24 @@ ScorePlan run_case(const char *name, World &w, const Batch &b) {
             }
         CHECK(at == order.size(), "the ranges hold %zu candidates of %zu", at, order.size());
     }
-    // ---- the table the launch walks: the batch's own holds exactly the chunks of the active bins
-    const PlanU4 *segments = own ? reinterpret_cast<const PlanU4 *>(hs + p.off_segs) : w.static_segs.data();
-    CHECK(p.n_segments == (own ? n_act_segs : f.n_segments), "n_segments %u", p.n_segments);
-    g_visits.assign(w.n_chunks, 0);
-    std::vector<uint8_t> in_table(w.n_chunks, 0);
+    // ---- the table the launch walks, over chunks or over the positions of the work list: the batch's own holds exactly the
+    // entries of the active bins
+    const PlanU4 *segments = own ? reinterpret_cast<const PlanU4 *>(hs + p.off_segs) : use_list ? wl.segs.data() : w.static_segs.data();
+    CHECK(p.n_segments == (own ? n_act_segs : n_static), "n_segments %u", p.n_segments);
+    const uint32_t *first_of = use_list ? wl.bin_start.data() : w.chunk0.data(), *count_of = use_list ? wl.bin_len.data() : w.nchunks.data();
+    const size_t n_items = use_list ? wl.entries.size() : w.n_chunks;
+    g_visits.assign(n_items, 0);
+    std::vector<uint8_t> in_table(n_items, 0);
     for (uint32_t s = 0; s < p.n_segments; ++s) {
         const PlanU4 &sg = segments[s];
-        CHECK(sg.y >= 1 && sg.y <= f.seg_chunks && sg.z < n_bins && sg.x >= w.chunk0[sg.z] && sg.x + sg.y <= w.chunk0[sg.z] + w.nchunks[sg.z],
+        CHECK(sg.y >= 1 && sg.y <= f.seg_chunks && sg.z < n_bins && sg.x >= first_of[sg.z] && sg.x + sg.y <= first_of[sg.z] + count_of[sg.z],
               "segment %u = {%u, %u, %u} leaves its bin", s, sg.x, sg.y, sg.z);
-        for (uint32_t c = 0; c < sg.y; ++c) { CHECK(!in_table[sg.x + c], "chunk %u is in two segments", sg.x + c); in_table[sg.x + c] = 1; }
+        for (uint32_t c = 0; c < sg.y; ++c) { CHECK(!in_table[sg.x + c], "item %u is in two segments", sg.x + c); in_table[sg.x + c] = 1; }
     }
-    if (own)
-        for (uint32_t bb = 0; bb < n_bins; ++bb)
-            for (uint32_t c = 0; c < w.nchunks[bb]; ++c)
-                CHECK(in_table[w.chunk0[bb] + c] == bin_used[bb], "chunk %u of bin %u: in the own table %d, bin active %d", w.chunk0[bb] + c, bb, in_table[w.chunk0[bb] + c], bin_used[bb]);
-    // ---- geometry: every chunk of every segment is visited exactly once, nothing else is
+    for (uint32_t bb = 0; bb < n_bins; ++bb)
+        for (uint32_t c = 0; c < count_of[bb]; ++c)
+            CHECK(in_table[first_of[bb] + c] == (own ? bin_used[bb] : 1), "item %u of bin %u: in the table %d, bin active %d", first_of[bb] + c, bb, in_table[first_of[bb] + c], bin_used[bb]);
+    // ---- geometry: every chunk (every list entry) of every segment is visited exactly once, nothing else is
     plan_geometry(p, f);
     const uint32_t split = f.opt_split >= 0 ? (uint32_t)f.opt_split : p.split_log2;
     CHECK(p.split_log2 == split && p.split_log2 <= 2 && p.fine_log2 == (f.opt_fine >= 0 ? (uint32_t)f.opt_fine : 2 - split), "split %u fine %u", p.split_log2, p.fine_log2);
@@ -368,12 +422,35 @@ ScorePlan run_case(const char *name, World &w, const Batch &b) {
     for (uint32_t block = 0; block < p.gx; ++block) {
         uint32_t first = 0, count = 0;
         if (!decode_block(p, cf, block, segments, &first, &count)) continue;
-        CHECK(count >= 1 && (size_t)first + count <= w.n_chunks, "workgroup %u walks chunks [%u, +%u)", block, first, count);
+        CHECK(count >= 1 && (size_t)first + count <= n_items, "workgroup %u walks items [%u, +%u)", block, first, count);
         for (uint32_t c = 0; c < count; ++c) g_visits[first + c] += 1;
     }
-    for (uint32_t c = 0; c < w.n_chunks; ++c)
-        CHECK(g_visits[c] == in_table[c], "chunk %u is visited %d times (in the table: %d); gx %u split %u fine %u j_big %u pieces_per_run %u segments %u", c, g_visits[c],
+    for (size_t c = 0; c < n_items; ++c)
+        CHECK(g_visits[c] == in_table[c], "item %zu is visited %d times (in the table: %d); gx %u split %u fine %u j_big %u pieces_per_run %u segments %u", c, g_visits[c],
               in_table[c], p.gx, p.split_log2, p.fine_log2, p.j_big, p.pieces_per_run, p.n_segments);
+    // ---- and through the list: every strip of an active bin that holds sequence is reached by exactly one lane of one visited entry
+    if (use_list) {
+        std::vector<uint8_t> strip_hits((size_t)w.n_chunks * 64, 0);
+        for (size_t e = 0; e < n_items; ++e) {
+            if (!g_visits[e]) continue;
+            const uint32_t entry = wl.entries[e];
+            for (uint32_t lane = 0; lane < 64; ++lane) {
+                uint32_t word = (entry & (WORK_NEED_V - 1)) * 256 + lane * 4;
+                if (entry & WORK_PACKED) {
+                    word = wl.strip_rows[(size_t)(entry & ~WORK_PACKED) * 64 + lane];
+                    if (word == WORK_NO_STRIP) continue;
+                }
+                CHECK(word % 4 == 0 && word / 4 < strip_hits.size(), "entry %zu lane %u reads word %u", e, lane, word);
+                strip_hits[word / 4] += 1;
+            }
+        }
+        for (size_t i = 0; i < w.contig_len.size(); ++i) {
+            const bool active = !own || bin_used[w.contig_bin[i]];
+            for (uint64_t st = 0; st * 128 < w.contig_len[i]; ++st)
+                CHECK(strip_hits[(size_t)w.contig_chunk[i] * 64 + st] == (active ? 1 : 0), "strip %" PRIu64 " of contig %zu is walked %d times", st, i,
+                      strip_hits[(size_t)w.contig_chunk[i] * 64 + st]);
+        }
+    }
     return p;
 }
 
@@ -389,6 +466,8 @@ void random_case(int i) {
     set_env("NM_STAGE_COPIES", chance(0.1) ? "1" : nullptr);
     set_env("NM_SCORE_CLASSES", chance(0.15) ? "0" : nullptr);
     set_env("NM_SCORE_HEAD", chance(0.15) ? "0" : nullptr);
+    set_env("NM_SCORE_PACK_TAILS", chance(0.3) ? "0" : nullptr);
+    w.lists = chance(0.85);
     Batch b;
     const uint32_t n = chance(0.05) ? 0 : chance(0.15) ? rnd(1, 5000) : rnd(1, 300);
     const uint32_t use_bins = chance(0.5) ? n_bins : rnd(1, n_bins), use_slots = rnd(1, n_slots);
@@ -431,7 +510,7 @@ void random_case(int i) {
     run_case(("random " + std::to_string(i)).c_str(), w, b);
 }
 
-void clear_env() { for (const char *e : {"NM_ALL_SEGMENTS", "NM_STAGE_COPIES", "NM_SCORE_CLASSES", "NM_SCORE_HEAD"}) unsetenv(e); }
+void clear_env() { for (const char *e : {"NM_ALL_SEGMENTS", "NM_STAGE_COPIES", "NM_SCORE_CLASSES", "NM_SCORE_HEAD", "NM_SCORE_PACK_TAILS"}) unsetenv(e); }
 
 // n candidates dealt round the groups (slot s, bin b), s < n_slots, b < use_bins
 Batch dealt(const World &w, uint32_t n, uint32_t use_bins, uint32_t n_slots, int kind) {
@@ -514,6 +593,27 @@ void directed_cases() {
                     run_case("NM_SPLIT x NM_FINE", w, dealt(w, per * 2 * n_bins, n_bins, 2, 1));
                     run_case("NM_SPLIT x NM_FINE, few bins", w, dealt(w, per * 2, 1, 2, 0));
                 }
+    {   // tails packed: a bin of 17 chunks in two contigs is two segments of chunks and of the plain list, one of the packed list (15
+        // full chunks and one row); light and per-contig batches keep the chunk table whatever the switch says
+        World w = make_world_of({{10 * 8192 + 3000, 5 * 8192 + 4000}, {20 * 8192 + 100}, {300, 500, 700}, {}}, 16, 2);
+        Batch heavy;
+        for (uint32_t k = 0; k < 28; ++k) add_motif(heavy, w, k % 4 == 3 ? 0 : k % 4, 0, 1);
+        ScorePlan p = run_case("tails packed", w, heavy);
+        CHECK(p.use_list && p.pack && !p.own_segments && p.n_segments == 1 + 2 + 1, "packed list: use_list %d pack %d segments %u", p.use_list, p.pack, p.n_segments);
+        setenv("NM_SCORE_PACK_TAILS", "0", 1);
+        p = run_case("tails packed, NM_SCORE_PACK_TAILS=0", w, heavy);
+        CHECK(p.use_list && !p.pack && p.n_segments == 2 + 2 + 1, "plain list: use_list %d pack %d segments %u", p.use_list, p.pack, p.n_segments);
+        clear_env();
+        Batch rows = heavy;
+        add_rows(rows, w);
+        p = run_case("tails packed, per-contig", w, rows);
+        CHECK(!p.use_list && p.n_segments == 2 + 2 + 1, "per-contig: use_list %d segments %u", p.use_list, p.n_segments);
+        p = run_case("tails packed, light", w, dealt(w, 6, 3, 1, 1));
+        CHECK(!p.use_list && p.cf, "light: use_list %d", p.use_list);
+        w.lists = false;
+        p = run_case("no lists", w, heavy);
+        CHECK(!p.use_list && p.n_segments == 2 + 2 + 1, "no lists: use_list %d segments %u", p.use_list, p.n_segments);
+    }
     for (uint32_t slots : {1u, 2u})                      // one and two active slots, with and without lit
         for (int kind : {0, 1}) {
             World w = make_world(12, 20, 2, 1.0);
