@@ -799,8 +799,21 @@ static int ingest_impl(nm_ctx *c, uint64_t n_rows, const uint32_t *contig_id, co
     ING_ALLOC(d_order, ((size_t)c->n_contigs + 1) * 4);
     ING_ALLOC(d_scalars, 32);          // n_kept, n_classified (this part), population of the methylated / unmethylated general planes (all parts)
     const dim3 blk(256);
-    const dim3 walk((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_rows + 255) / 256, 256 * 32)));      // waves walk contiguous row ranges
+    // NM_INGEST_WALK_BLOCKS=<k>: at most k workgroups walk the rows (and the candidate list), read at call time.  A call of up to
+    // 2 097 152 rows gives every wave exactly 64 rows — one trip of every loop below; with k = 1 four waves walk a quarter of
+    // the rows each, the way a wave walks tens of thousands of rows of a 1e9-row pileup (tests/test_gpu_ingest_geometry.py).
+    // Unset, empty or not a positive integer: no limit.  It never raises the number of workgroups.
+    uint64_t walk_cap = ~0ull;
+    if (const char *s = getenv("NM_INGEST_WALK_BLOCKS")) {
+        char *end = nullptr;
+        const unsigned long long v = (*s >= '0' && *s <= '9') ? strtoull(s, &end, 10) : 0;
+        if (v > 0 && end && *end == 0) walk_cap = v;
+    }
+    const dim3 walk((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>((n_rows + 255) / 256, 256 * 32), walk_cap)));      // waves walk contiguous row ranges
     const uint32_t n_waves = walk.x * 4;
+    const auto per_wave = [](uint64_t n, uint64_t waves) { return (((n + waves - 1) / waves) + 63) & ~(uint64_t)63; };      // wave_row_range
+    const char *path = "no rows";                  // NM_INGEST_TIMING: which classification path ran
+    uint32_t list_waves = 0;
     unsigned int *d_wave_cand = nullptr, *d_wave_n = nullptr;
     unsigned long long *d_wave_first = nullptr, *d_packed_first = nullptr;
     ING_ALLOC(d_wave_cand, (size_t)n_waves * 4);
@@ -834,10 +847,11 @@ static int ingest_impl(nm_ctx *c, uint64_t n_rows, const uint32_t *contig_id, co
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
             if (e != hipSuccess) { nmdetail::busy_end(c); cleanup(); invalidate(); return fail(NM_EHIP, "ingest failed: %s", hipGetErrorString(e)); }
             use_list = order_flags == 0;
-            mark();                                // [3] counting pass done (the host waits for the row order and the candidate count)
         }
+        mark();                                    // [3] counting pass done (list path: the host has waited for the row order and the candidate count)
         CandList lists[2] = {};
         if (use_list) {
+            path = "list";
             for (int k = 0; k < 2; ++k) {
                 ING_ALLOC(lists[k].key, (size_t)(cap + 2) * 8);
                 ING_ALLOC(lists[k].fbits, (size_t)(cap + 2) * 8);
@@ -853,11 +867,13 @@ static int ingest_impl(nm_ctx *c, uint64_t n_rows, const uint32_t *contig_id, co
             ING_ALLOC(lists[1].range, (size_t)std::max(c->n_contigs, 1u) * 16);
             e = hipMemsetAsync(lists[1].range, 0, (size_t)std::max(c->n_contigs, 1u) * 16, c->stream);
             if (e != hipSuccess) { nmdetail::busy_end(c); cleanup(); invalidate(); return fail(NM_EHIP, "memset failed: %s", hipGetErrorString(e)); }
-            const dim3 over_list((unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>((cap + 255) / 256, 8192)));
+            const dim3 over_list((unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>(std::min<unsigned long long>((cap + 255) / 256, 8192), walk_cap)));
+            list_waves = over_list.x * 4;
             hipLaunchKernelGGL(ingest_ranges_kernel, over_list, blk, 0, c->stream, lists[1], d_packed_first + n_waves);
             hipLaunchKernelGGL(ingest_judge_kernel, over_list, blk, 0, c->stream, lists[1], d_packed_first + n_waves, 8, high, c->d_contig_chunk, sl, d_kept,
                                d_scalars, d_scalars + 1);
         } else {
+            path = "dense";                        // (stores or atomics: the kernel's own condition, from the flags copied back below)
             ING_ALLOC(d_dense, npos * 8 * 2);
             e = hipMemsetAsync(d_dense, 0, npos * 8 * 2, c->stream);
             if (e != hipSuccess) { nmdetail::busy_end(c); cleanup(); invalidate(); return fail(NM_EHIP, "memset failed: %s", hipGetErrorString(e)); }
@@ -867,6 +883,8 @@ static int ingest_impl(nm_ctx *c, uint64_t n_rows, const uint32_t *contig_id, co
                                c->d_contig_chunk, d_dense_off, d_dense, d_dense + npos, 8, 0.7, low, high, sl, d_order, d_kept, d_scalars, d_scalars + 1,
                                nullptr, CandList{}, nullptr, c->d_err);
         }
+    } else {
+        mark();                                    // [3] no counting pass
     }
 #undef ING_ALLOC
     // population of the general planes (all parts so far): the confident rows, and the duplicate check — every
@@ -891,15 +909,24 @@ static int ingest_impl(nm_ctx *c, uint64_t n_rows, const uint32_t *contig_id, co
     e = hipMemcpyAsync(scal, d_scalars, 32, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&err, c->d_err, 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(part_kept.data(), d_kept, n_groups * 4, hipMemcpyDeviceToHost, c->stream);
+    unsigned int order_end = 0;                    // NM_INGEST_TIMING only: the flags ingest_decide_kernel read, the entries of the packed list
+    unsigned long long list_entries = 0;
+    if (timing && e == hipSuccess) e = hipMemcpyAsync(&order_end, d_order, 4, hipMemcpyDeviceToHost, c->stream);
+    if (timing && list_waves && e == hipSuccess) e = hipMemcpyAsync(&list_entries, d_packed_first + n_waves, 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     mark();                                        // [5] the device is done
     cleanup();
     mark();                                        // [6] scratch given back
-    if (timing && n_marks == 7)
+    if (timing && n_marks == 7) {
+        char geometry[160];
+        if (!strcmp(path, "dense")) path = order_end == 0 && low < 0.7 ? "dense stores" : "dense atomics";      // `sorted` of ingest_decide_kernel
+        int at = snprintf(geometry, sizeof geometry, ", path %s, walk %u waves x %llu rows", path, n_waves, (unsigned long long)per_wave(n_rows, n_waves));
+        if (list_waves) snprintf(geometry + at, sizeof geometry - (size_t)at, ", list %u waves x %llu entries", list_waves, (unsigned long long)per_wave(list_entries, list_waves));
         fprintf(stderr, "[nm_ingest] %llu rows: waiting for earlier work %.2f ms, allocations %.2f ms, clears + counting pass + wait %.2f ms, "
-                        "queueing the rest %.2f ms, waiting for it %.2f ms, freeing scratch %.2f ms\n", (unsigned long long)n_rows,
+                        "queueing the rest %.2f ms, waiting for it %.2f ms, freeing scratch %.2f ms%s\n", (unsigned long long)n_rows,
                 (t_marks[1] - t_marks[0]) * 1e3, (t_marks[2] - t_marks[1]) * 1e3, (t_marks[3] - t_marks[2]) * 1e3, (t_marks[4] - t_marks[3]) * 1e3,
-                (t_marks[5] - t_marks[4]) * 1e3, (t_marks[6] - t_marks[5]) * 1e3);
+                (t_marks[5] - t_marks[4]) * 1e3, (t_marks[6] - t_marks[5]) * 1e3, geometry);
+    }
     if (e != hipSuccess) { invalidate(); return fail(NM_EHIP, "ingest failed: %s", hipGetErrorString(e)); }
     if (err & 1u) { invalidate(); return fail(NM_EINVAL, "pileup row with contig_id / position / mod code outside the uploaded assembly"); }
     if (err & 8u) { invalidate(); return fail(NM_EINVAL, "pileup row of a contig that is not listed in part_contigs"); }

@@ -1,8 +1,10 @@
 """Fuzz of the device pre-filters (nm_ingest_pileup: coverage, per-(contig, mod code) frequency, adjacency; classification) ON
 THE GPU BOX against oracle/pileup.py on random adversarial tables: fractions on the thresholds and tied inside adjacency
 windows, coverage on the bound, groups on the frequency bounds (50 / 51 modified rows, ratio near 1e-4), NaN fractions, up to
-14 mod codes, rows in modkit's order or shuffled (whole table / contig runs interleaved), contigs missing from the engine.
+14 mod codes, rows in modkit's order or shuffled (whole table / contig runs interleaved), contigs missing from the engine, and
+NM_INGEST_WALK_BLOCKS unset / 1 / 2 / 5 (unset: 64 rows a wave whatever the table's size; else a wave walks many rows).
 usage: python3 tools/ingest_fuzz.py [first_seed [n_seeds]]"""
+import os
 import sys
 import time
 
@@ -63,6 +65,10 @@ def one(seed):
         order = np.concatenate(runs)
     t = {k: v[order] for k, v in t.items()}
     exp = op.prefilter({k: v.copy() for k, v in t.items()})
+    blocks = int(rng.choice([0, 1, 2, 5]))                                    # workgroups that walk the rows (0: as many as the rows ask for)
+    os.environ.pop("NM_INGEST_WALK_BLOCKS", None)
+    if blocks:
+        os.environ["NM_INGEST_WALK_BLOCKS"] = str(blocks)
     eng = ScanEngine(0)
     try:
         absent = set(rng.choice(n_contigs, size=int(rng.integers(0, max(1, n_contigs // 2))), replace=False).tolist()) if n_contigs > 2 else set()
@@ -83,7 +89,8 @@ def one(seed):
         assert sorted(zip(cc.tolist(), cp.tolist(), cs.tolist(), cm.tolist())) == want, (seed, "confident rows", len(cc), len(want))
     finally:
         eng.close()
-    return f"{len(t['position'])} rows, {n_contigs} contigs ({len(mine)} resident), {n_codes} codes, order {('modkit', 'shuffled', 'runs moved')[how]}: kept {int(keep.sum())}, confident {len(want)}"
+        os.environ.pop("NM_INGEST_WALK_BLOCKS", None)
+    return f"{len(t['position'])} rows, {n_contigs} contigs ({len(mine)} resident), {n_codes} codes, order {('modkit', 'shuffled', 'runs moved')[how]}, walk blocks {blocks or 'unset'}: kept {int(keep.sum())}, confident {len(want)}"
 
 
 if __name__ == "__main__":
