@@ -688,6 +688,36 @@ int nm_motif_gc_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, co
                       const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t half,
                       const uint64_t *cand_row0 /* [n_cand + 1] */, int64_t *counts);
 
+/* ---- MOTIF OVERLAP: the sites a motif shares with other motifs of its bin, and the sites it has alone ------------------------------
+ * Reference: none on sites (remove_sub_motifs / merge_motifs of postprocess.py settle nesting by the motifs' spelling).  What decides
+ * whether a parent motif or its child is the real one is the methylation of the parent OUTSIDE the child: a set difference on the
+ * occurrence sets, which no marginal count gives and, when children overlap each other, no inclusion-exclusion either.
+ *
+ * CANDIDATES, OCCURRENCES and their STATE (mod / nomod / nocall) are nm_motif_sites_count's.  A SITE is (contig, '+' coordinate of
+ *   the modified base, occurrence strand); two motifs SHARE a site when both have it.  The state belongs to the position and the mod
+ *   slot, so a shared site has one state.
+ * PARTNERS of candidate k: the motifs [cand_partner_offset[k], cand_partner_offset[k + 1]) of the part_* arrays, spelled like
+ *   candidates; they are read in k's bin and mod slot.  P_k = their number, at most NM_OVERLAP_MAX_PARTNERS.  cand_partner_offset[0]
+ *   must be 0 and the prefix ascend.  The part_* arrays may be NULL when no candidate has a partner.
+ * ROWS: candidate k takes (P_k + 2) x n_contigs(bin) rows from cand_row0[k] (cand_row0[n_cand] = the rows of the table,
+ *   cand_row0[k + 1] - cand_row0[k] must cover them).  Row cand_row0[k] + block * n_contigs + contig rank (nm_bin_contigs order) holds
+ *   fwd mod, fwd nomod, fwd nocall, rev mod, rev nomod, rev nocall of
+ *     block 0          k's own sites (its row of nm_motif_sites_count)
+ *     block 1 + q      the sites k shares with its q-th partner
+ *     block P_k + 1    the rest: k's sites that NO partner has (P_k = 0: block 0 again)
+ *   The caller's table need not be zeroed.
+ * A candidate runs at the widest reach class among itself and its partners.  Launches: at most 3 whatever the batch.
+ * Refusals, each before any device is touched and in this order per candidate: bin (NM_EINVAL), mod slot (NM_ESTATE), the partner
+ * prefix, P_k and a NULL partner array (NM_EINVAL), the partners' programs in order (NM_ERANGE for a length outside
+ * 1..NM_MAX_MOTIF_LEN or beyond the reach limit), the candidate's own program, rows (NM_EINVAL; NM_ERANGE from 2^32), work items.
+ * NM_EINVAL for NULLs and a NULL ctx; NM_ESTATE without an assembly.  n_cand = 0 is NM_OK.  A refusal leaves the ctx usable. */
+#define NM_OVERLAP_MAX_PARTNERS 4095
+int nm_motif_overlap_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot, const uint8_t *cand_len,
+                           const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks,
+                           const uint32_t *cand_partner_offset /* [n_cand + 1] */, const uint8_t *part_len, const uint8_t *part_modpos,
+                           const uint32_t *part_mask_offset, const uint8_t *part_masks, const uint64_t *cand_row0 /* [n_cand + 1] */,
+                           int64_t *counts /* [rows][6] */);
+
 /* ---- per-contig READ methylation of motifs: the table binnary starts from -------------------------
  * Reference: nanomotif/main.py:142-193 — `contig_methylation = methylation_pattern(pileup, assembly, motifs,
  * min_valid_read_coverage, min_valid_cov_to_diff_fraction = 0.8, output_type = Median | WeightedMean)` from the

@@ -31,6 +31,7 @@ SYMBOLS = [
     "nm_tracks_windows", "nm_motif_tracks_count",
     "nm_motif_fractions_count",
     "nm_motif_gc_count",
+    "nm_motif_overlap_count",
 ]
 
 class SearchParams(C.Structure):
@@ -169,6 +170,7 @@ def _load_locked():
     lib.nm_motif_tracks_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, u32p]
     lib.nm_motif_fractions_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p]
     lib.nm_motif_gc_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, i64p]
+    lib.nm_motif_overlap_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, u32p, u8p, u8p, u32p, u8p, u64p, i64p]
     lib.nm_motif_sites_text.argtypes = [C.c_uint64, u32p, u32p, u8p, C.c_uint32, u64p, C.c_char_p, u64p, C.c_uint32, C.c_char_p, u64p, p,
                                         C.c_uint64, u64p]
     lib.nm_readstats_upload.argtypes = [p, C.c_uint32, C.c_uint64, p, p, p, p, p, p, C.c_int32, C.c_double, C.c_int, u64p]

@@ -1,6 +1,6 @@
 """Command line of the MI355X build: the ``motif_discovery`` sub-command with the reference's arguments
 (nanomotif/argparser.py:13-136), plus ``--device`` for the GPU to use, the project's own ``motif_sites`` / ``motif_coverage`` /
-``motif_compare`` / ``motif_strands`` / ``motif_profile`` / ``motif_tracks`` / ``motif_fractions`` / ``motif_context`` / ``motif_gc`` on a finished ``bin-motifs.tsv``, ``motif_kmers`` (which needs none), and the binnary sub-commands ``detect_contamination`` and
+``motif_compare`` / ``motif_strands`` / ``motif_profile`` / ``motif_tracks`` / ``motif_fractions`` / ``motif_context`` / ``motif_gc`` / ``motif_overlap`` on a finished ``bin-motifs.tsv``, ``motif_kmers`` (which needs none), and the binnary sub-commands ``detect_contamination`` and
 ``include_contigs`` with the reference's flags (argparser.py:139-236).  MTase-linker is out of scope."""
 import argparse
 
@@ -13,7 +13,7 @@ def create_parser():
                                      formatter_class=formatter)
     parser.add_argument("--version", action="version", version="%(prog)s {}".format(__version__))
     sub = parser.add_subparsers(help="-- Command descriptions --", dest="command", title="commands",
-                                metavar="{motif_discovery, motif_sites, motif_coverage, motif_compare, motif_strands, motif_profile, motif_tracks, motif_fractions, motif_context, motif_gc, motif_kmers, detect_contamination, include_contigs, check_installation}")
+                                metavar="{motif_discovery, motif_sites, motif_coverage, motif_compare, motif_strands, motif_profile, motif_tracks, motif_fractions, motif_context, motif_gc, motif_overlap, motif_kmers, detect_contamination, include_contigs, check_installation}")
     p = sub.add_parser("motif_discovery", help="Finds motifs directly on bin level in provided assembly", add_help=False)
     p.add_argument("assembly", type=str, help="path to the assembly file.")
     p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
@@ -59,6 +59,7 @@ def create_parser():
     add_motif_fractions_parser(sub)
     add_motif_context_parser(sub)
     add_motif_gc_parser(sub)
+    add_motif_overlap_parser(sub)
     add_motif_kmers_parser(sub)
     add_binnary_parsers(sub)
     sub.add_parser("check_installation", help="Run motif_discovery on a small synthetic data set", add_help=True)
@@ -403,6 +404,43 @@ def add_motif_gc_parser(sub):
                    help="|trend_z_within| from which a motif can be flagged gc_dependent. Default: %(default)s")
     o.add_argument("--min_delta", type=float, default=0.2,
                    help="|frac_mod of the high-GC third - frac_mod of the low-GC third| from which a motif can be flagged gc_dependent. Default: %(default)s")
+    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
+                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
+    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
+                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
+    o.add_argument("--threshold_valid_coverage", type=int, default=5,
+                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
+    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
+    gen = p.add_argument_group("general arguments")
+    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
+    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
+    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
+    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
+
+
+def add_motif_overlap_parser(sub):
+    """motif_overlap: the sites the motifs of one bin share, which motif is nested in which, and how methylated a motif is outside the
+    motifs nested in it (the reference settles nesting by the motifs' spelling, postprocess.py).  Arguments are those of motif_sites:
+    same ingest."""
+    p = sub.add_parser("motif_overlap", help="Reports shared sites and nesting between the motifs of each bin of bin-motifs.tsv files", add_help=False)
+    p.add_argument("assembly", type=str, help="path to the assembly file.")
+    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
+    gm = p.add_argument_group("contig bin arguments, use one of:")
+    g = gm.add_mutually_exclusive_group(required=True)
+    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
+    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
+    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
+    gm.add_argument("--extension", type=str, default=".fasta",
+                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
+    o = p.add_argument_group("Options")
+    o.add_argument("--bin_motifs", type=str, nargs="+", required=True, help="Path(s) to the bin-motifs.tsv whose motifs are compared (motif_discovery's output)")
+    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
+    o.add_argument("--all_pairs", action="store_true", help="Also write the pairs of motifs that share no site")
+    o.add_argument("--min_called", type=int, default=20, help="Called sites a motif, or a part of one, needs to be judged. Default: %(default)s")
+    o.add_argument("--max_outside", type=float, default=0.3,
+                   help="Fraction of methylation outside its children up to which a motif can be flagged carried_by_children. Default: %(default)s")
+    o.add_argument("--min_frac", type=float, default=0.7,
+                   help="Fraction of methylation from which a part of a motif counts as methylated (carried_by_children, submotif). Default: %(default)s")
     o.add_argument("--methylation_threshold_low", type=float, default=0.30,
                    help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
     o.add_argument("--methylation_threshold_high", type=float, default=0.70,

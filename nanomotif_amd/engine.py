@@ -48,6 +48,9 @@ UNEXPLAINED_DTYPE =np.dtype([("set", np.uint32), ("contig", np.uint32), ("pos", 
 
 GC_MAX_HALF = 31                               # NM_GC_MAX_HALF: positions a GC window reaches either side of the modified base
 GC_BUDGET_BYTES = 256 << 20                    # default size of the table of one library call of ScanEngine.motif_gc
+OVERLAP_MAX_PARTNERS = 4095                    # NM_OVERLAP_MAX_PARTNERS: partner motifs of one candidate of ScanEngine.motif_overlap
+OVERLAP_ROW_BYTES = 48                         # one (block, contig) row of nm_motif_overlap_count: 2 strands x 3 states, int64
+OVERLAP_BUDGET_BYTES = 256 << 20               # default size of the table of one library call of ScanEngine.motif_overlap
 KMER_MAX_FLANKS = 10                           # NM_KMER_MAX_FLANKS: counted positions of a k-mer shape ...
 KMER_MAX_OFFSET = 31                           # ... each within NM_KMER_MAX_OFFSET of the modified base
 KMER_BUDGET_BYTES = 256 << 20                  # default size of the tables of one library call of ScanEngine.kmer_methylation
@@ -1371,6 +1374,55 @@ class ScanEngine:
             _lib.check(self.lib.nm_motif_gc_count(self.ctx, *self._batch_args(sub), half, _ptr(rows, C.c_uint64), _ptr(table, C.c_int64)))
             for j in range(k, e):
                 yield names[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
+
+    # ------------------------------------------------------------------ shared sites of a motif and its partners (nm_motif_overlap_count)
+    def motif_overlap(self, candidates, partners, max_bytes=None):
+        """Generator over the sites ``candidates`` (sequence of (Motif, mod_type, bin), or a CandidateBatch with slots from
+        ``slot_of_mod``, as ``motif_site_counts`` takes them) share with their partners (nm_motif_overlap_count).  ``partners[k]``: a
+        list of Motif, read in candidate k's bin and mod slot; at most ``OVERLAP_MAX_PARTNERS``.  A site is an occurrence of
+        ``motif_site_counts`` with its state; two motifs share a site when both have that (contig, position, strand).  Yields one
+        item per candidate, in call order: (contig names in ``bin_contigs`` order, int64[P_k + 2, n_contigs, 2 (occurrence strand),
+        3 (mod, nomod, nocall)]) — block 0 the candidate's own sites (its ``motif_site_counts`` rows), block 1 + q the sites it
+        shares with its q-th partner, the last block the REST: its sites no partner has (without partners: block 0 again).
+        Consecutive candidates share one library call while their tables fit ``max_bytes`` (default ``OVERLAP_BUDGET_BYTES``); a
+        group always holds at least one candidate.  What is yielded does not depend on ``max_bytes``."""
+        limit = OVERLAP_BUDGET_BYTES if max_bytes is None else int(max_bytes)
+        if limit < 1:
+            raise ValueError("max_bytes must be at least 1")
+        b = self._as_batch(candidates)
+        partners = [list(p) for p in partners]
+        if len(partners) != len(b):
+            raise ValueError(f"{len(b)} candidates but {len(partners)} partner lists")
+        worst = max((len(p) for p in partners), default=0)
+        if worst > OVERLAP_MAX_PARTNERS:
+            raise ValueError(f"a candidate has {worst} partners, above OVERLAP_MAX_PARTNERS = {OVERLAP_MAX_PARTNERS}")
+        return self._overlap_groups(b, partners, limit)
+
+    def _overlap_groups(self, b: CandidateBatch, partners: list, limit: int):
+        bins = [int(x) for x in b.bins]
+        names = {bid: self.bin_contigs(bid) for bid in sorted(set(bins))}
+        blocks = [len(p) + 2 for p in partners]
+        part0 = np.zeros(len(b) + 1, dtype=np.int64)
+        np.cumsum([len(p) for p in partners], out=part0[1:])
+        flat = [(m, 0, 0) for p in partners for m in p]
+        pb = self.make_batch(flat, slot_of=lambda mt: 0) if flat else None
+        for k, e, _ in _budget_groups([blocks[j] * len(names[bins[j]]) * OVERLAP_ROW_BYTES for j in range(len(b))], limit):
+            rows = np.zeros(e - k + 1, dtype=np.uint64)
+            np.cumsum([blocks[j] * len(names[bins[j]]) for j in range(k, e)], out=rows[1:])
+            table = np.zeros((max(int(rows[-1]), 1), 2, 3), dtype=np.int64)
+            sub = b.slice(k, e)
+            q0, q1 = int(part0[k]), int(part0[e])
+            off = (part0[k:e + 1] - q0).astype(np.uint32)
+            if q1 > q0:
+                ps = pb.slice(q0, q1)
+                pargs = (_ptr(ps.lens, C.c_uint8), _ptr(ps.modpos, C.c_uint8), _ptr(ps.offsets, C.c_uint32), _ptr(ps.masks, C.c_uint8))
+            else:
+                pargs = (None, None, None, None)
+            _lib.check(self.lib.nm_motif_overlap_count(self.ctx, *self._batch_args(sub), _ptr(off, C.c_uint32), *pargs, _ptr(rows, C.c_uint64),
+                                                       _ptr(table, C.c_int64)))
+            for j in range(k, e):
+                n = len(names[bins[j]])
+                yield names[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])].reshape(blocks[j], n, 2, 3)
 
     # ------------------------------------------------------------------ coverage of a set of motifs (nm_motif_coverage_*)
     def _coverage_args(self, sets):
