@@ -115,11 +115,12 @@ __global__ void state_kernel(uint64_t n_rows, const uint32_t *__restrict__ conti
 __global__ void compile_kernel(uint32_t n_prog, const CandRec *__restrict__ rec, const uint8_t *__restrict__ masks,
                                uint32_t *__restrict__ programs, int wide, int np, int fold_modpos, int classes, uint32_t c_slots) {
     // classes: write the class layout of the CLS variants (nmscan_device.h; wide, np and fold_modpos do not apply), 1 with the
-    // fused head of a walk, 2 with every literal left in its word (NM_SCORE_HEAD=0);
+    // fused head of a walk, 2 with every literal left in its word (NM_SCORE_HEAD=0), plus 4 x the tail descriptors to write
+    // (CLS_TAIL_LITERALS | CLS_TAIL_CLASS, NM_SCORE_TAIL);
     // c_slots: bit s = mod slot s has canonical base C (the compiler swaps the base sets of such a candidate)
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_prog) return;
-    if (classes) compile_one_classes(k, rec, masks, programs, c_slots, classes == 1);
+    if (classes) compile_one_classes(k, rec, masks, programs, c_slots, (classes & 3) == 1, classes >> 2);
     else compile_one(k, rec, masks, programs, wide, np, fold_modpos);
 }
 
@@ -566,7 +567,7 @@ int score_prepare(nm_ctx *c, ScoreRun &r, uint32_t c_slots) {       // c_slots: 
     case PLAN_COMPILE_ONLY:
     case PLAN_COMPILE_THEN_COMMON:
         hipLaunchKernelGGL(compile_kernel, dim3((p.n_prog + 255) / 256), dim3(256), 0, r.pst, p.n_prog, d_rec, r.ds + p.off_masks, r.d_prog, p.any_wide,
-                           (int)p.np, fold_modpos, p.classes ? (p.cls_head ? 1 : 2) : 0, c_slots);
+                           (int)p.np, fold_modpos, p.classes ? (p.cls_head ? 1 : 2) | p.cls_tail << 2 : 0, c_slots);
         HIP_TRY(hipGetLastError());
         if (p.compile == PLAN_COMPILE_THEN_COMMON) {
             hipLaunchKernelGGL(common_kernel, dim3((p.n_entries + 63) / 64), dim3(64), 0, r.pst, p.n_entries, d_range, r.d_prog, p.pdw, p.n_prog, 8u);

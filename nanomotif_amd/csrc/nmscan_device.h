@@ -233,9 +233,17 @@ struct JointWalk {
 // r1 < r2); 36..43: a single literal w; 44: no literal, the walk starts with plain moves.  lit_left: a literal word is still
 // not empty (clear: the eight literal words are skipped behind one test).  A shift is never 0 here (the modified position
 // is folded and the offsets lie in [-31, 31]), so the head has no unshifted form.
+// tail: 39 % of the candidates of a search have exactly ONE class constraint, and the walk reads it from the summary, not
+// from behind the quad guards and the word tests: bit 25 says so, the constraint's word is then the one set bit among summary
+// bits 0..19 (one s_ff1), its r sits in bits 26..30 and the reverse shift is one s_sub; the class word keeps its bit and is
+// not read.  (Descriptors for one or two left-over literals beside the head's shifts were built and measured too: they did
+// not separate from the words in time and are not here, profiles/r25/tail_descriptors.md.)
 constexpr int CLS_PROG_DW = 32, CLS_SUMMARY_DW = 8, CLS_WORDS_DW = 9, CLS_HEAD_DW = 29, CLS_HEAD_FWD_DW = 30, CLS_HEAD_REV_DW = 31;
 constexpr int CLS_QUAD_BIT = 20;                // summary: bit CLS_QUAD_BIT + q is set iff one of class words 4 q .. 4 q + 3 is not empty
 constexpr int CLS_LIT_WORDS = 8, CLS_HEAD_SINGLE = 36, CLS_HEAD_NONE = 44, CLS_HEADS = 45;
+constexpr int CLS_CLASS_WORDS = 20;
+constexpr int CLS_ONE_CLASS_BIT = 25, CLS_ONE_CLASS_R_BIT = 26;                        // summary
+constexpr int CLS_TAIL_CLASS = 2;                                  // NM_SCORE_TAIL: the bit that asks for the lone-class descriptor (bit 0 named the literal ones)
 // (w1, w2) -> id; w2 < 0: a single head; w1 < 0 as well: none
 constexpr int cls_head_id(int w1, int w2) {
     return w1 < 0 ? CLS_HEAD_NONE : w2 < 0 ? CLS_HEAD_SINGLE + w1 : w1 * CLS_LIT_WORDS - w1 * (w1 - 1) / 2 + (w2 - w1);
@@ -300,6 +308,18 @@ constexpr bool cls_head_mirror_ok() {
     return true;
 }
 static_assert(cls_head_mirror_ok(), "mirror of a head word: plane 3 - p at word-group 2 GN - 1 - g");
+// the lone class as the walk reads it back, beside the word and quad bits; every (word, r), r = 0 excluded as for the head
+constexpr bool cls_tail_ok() {
+    for (int c = 0; c < CLS_CLASS_WORDS; ++c)
+        for (uint32_t r = 1; r < 32; ++r) {
+            const uint32_t s = 1u << c | 1u << (CLS_QUAD_BIT + c / 4) | 1u << CLS_ONE_CLASS_BIT | r << CLS_ONE_CLASS_R_BIT;
+            int low = 0;
+            while (!((s >> low) & 1u)) ++low;                                         // s_ff1
+            if (low != c || ((s >> CLS_ONE_CLASS_R_BIT) & 31u) != r || !((s >> (CLS_QUAD_BIT + c / 4)) & 1u)) return false;
+        }
+    return CLS_QUAD_BIT + (CLS_CLASS_WORDS + 3) / 4 <= CLS_ONE_CLASS_BIT && CLS_ONE_CLASS_R_BIT + 5 <= 32;
+}
+static_assert(cls_tail_ok(), "the lone-class descriptor: every (word, shift) round-trips beside the summary's word and quad bits");
 
 // Planes is-A / C / G / T, H, L, X (and V when BV) of the code (H, L ^ cm); cm is the wave-uniform flip of the slot, all
 // ones for canonical base C, so for a C slot the planes read is-C / A / T / G, H, ~L, ~X.  pack_kernel writes H and L as
@@ -362,6 +382,31 @@ struct ClassWalk {
         constexpr int GR = R0 ? 2 * K::GN - G : 2 * K::GN - 1 - G;
         and_one<G, P>(tile, accf, r);
         and_one<GR, cls_mirror(P)>(tile, accr, R0 ? 0u : 32u - r);
+    }
+    // a constraint from a tail descriptor: both strands' shifts come with it
+    template <int G, int P>
+    __device__ __forceinline__ void and_in(const TileT &tile, uint32_t r, uint32_t rr) {
+        and_one<G, P>(tile, accf, r);
+        and_one<2 * K::GN - 1 - G, cls_mirror(P)>(tile, accr, rr);
+    }
+    // the leaf of class word c (0..19, counted from dword 9): compares and branches, wave-uniform.
+    // Each case passes its accumulators through a comment of its own (pin): left alike, the compiler sinks the ANDs of all
+    // cases into one block behind the switch and every leaf hands it eight shifted words in eight more registers.
+    template <int I>
+    __device__ __forceinline__ void pin() {
+        static_assert(T_WORDS == 4, "eight accumulator words");
+        asm("; leaf %8" : "+v"(accf[0]), "+v"(accf[1]), "+v"(accf[2]), "+v"(accf[3]), "+v"(accr[0]), "+v"(accr[1]), "+v"(accr[2]), "+v"(accr[3]) : "n"(I));
+    }
+    __device__ __forceinline__ void class_leaf(uint32_t c, const TileT &tile, uint32_t r, uint32_t rr) {
+#define NM_LEAF_CASE(i) case i: and_in<(i) / 10, 4 + (i) % 10>(tile, r, rr); pin<i>(); break;
+#define NM_LEAF_CASES5(i) NM_LEAF_CASE(i) NM_LEAF_CASE(i + 1) NM_LEAF_CASE(i + 2) NM_LEAF_CASE(i + 3) NM_LEAF_CASE(i + 4)
+        switch (c) {
+            NM_LEAF_CASES5(0) NM_LEAF_CASES5(5) NM_LEAF_CASES5(10) NM_LEAF_CASES5(15)
+            default: __builtin_unreachable();
+        }
+#undef NM_LEAF_CASES5
+#undef NM_LEAF_CASE
+        static_assert(CLS_CLASS_WORDS == 20, "one case per class word");
     }
     template <int G, int P>
     __device__ __forceinline__ void word(uint32_t mm, const TileT &tile) {
@@ -429,7 +474,12 @@ struct ClassWalk {
             word<1, 0>(m[4], tile); word<1, 1>(m[5], tile); word<1, 2>(m[6], tile); word<1, 3>(m[7], tile);
         }
         if (m[CLS_SUMMARY_DW]) {                                        // wave-uniform: 20 class words skipped at once
-            quad<0>(m, tile); quad<1>(m, tile); quad<2>(m, tile); quad<3>(m, tile); quad<4>(m, tile);
+            if (m[CLS_SUMMARY_DW] & (1u << CLS_ONE_CLASS_BIT)) {        // exactly one class constraint: its word is the lowest set bit
+                const uint32_t r = m[CLS_SUMMARY_DW] >> CLS_ONE_CLASS_R_BIT;
+                class_leaf((uint32_t)__builtin_ctz(m[CLS_SUMMARY_DW]), tile, r, 32u - r);
+            } else {
+                quad<0>(m, tile); quad<1>(m, tile); quad<2>(m, tile); quad<3>(m, tile); quad<4>(m, tile);
+            }
         }
     }
 };
@@ -534,13 +584,15 @@ __device__ __forceinline__ void compile_one(uint32_t k, const CandRec *__restric
 // The class layout (CLS variants: narrow, compact, so the modified position is folded and offsets lie in [-31, 31]): the
 // forward half only, one constraint per set of one, two or three bases, and the summary dword (layout: ClassWalk).
 // use_head: the first two literals become the head of the walk; without it every literal stays in its word (id 44).
+// tail: CLS_TAIL_CLASS set: a lone class constraint is flagged in the summary; clear: it is found through its quad.
 __device__ __forceinline__ void compile_one_classes(uint32_t k, const CandRec *__restrict__ rec, const uint8_t *__restrict__ masks,
-                                                    uint32_t *__restrict__ programs, uint32_t c_slots, bool use_head) {
+                                                    uint32_t *__restrict__ programs, uint32_t c_slots, bool use_head, int tail) {
     uint32_t *prog = programs + (size_t)k * CLS_PROG_DW;
     for (int i = 0; i < CLS_PROG_DW; ++i) prog[i] = 0;
     const CandRec c = rec[k];
     const uint8_t *m = masks + c.mask_off;
     const bool swap = ((c_slots >> c.slot) & 1u) != 0;                      // c_slots: bit s = mod slot s has canonical base C
+    uint32_t n_cls = 0, cls_r = 0;
     for (int j = 0; j < c.len; ++j) {
         uint32_t set = m[j] & 15u;
         if (set == 15u || j == c.modpos) continue;
@@ -550,8 +602,13 @@ __device__ __forceinline__ void compile_one_classes(uint32_t k, const CandRec *_
         if (g < 0 || g > 1) continue;                   // (the host sends no such offset to a narrow variant)
         const int p = cls_word_of_set(set);
         prog[cls_dword(g, p)] |= 1u << ((uint32_t)d & 31u);
-        if (p >= 4) prog[CLS_SUMMARY_DW] |= 1u << (10 * g + p - 4) | 1u << (CLS_QUAD_BIT + (10 * g + p - 4) / 4);
+        if (p >= 4) {
+            prog[CLS_SUMMARY_DW] |= 1u << (10 * g + p - 4) | 1u << (CLS_QUAD_BIT + (10 * g + p - 4) / 4);
+            n_cls += 1;
+            cls_r = (uint32_t)d & 31u;
+        }
     }
+    if (n_cls == 1 && (tail & CLS_TAIL_CLASS)) prog[CLS_SUMMARY_DW] |= 1u << CLS_ONE_CLASS_BIT | cls_r << CLS_ONE_CLASS_R_BIT;
     // the head: after the swap, the first two literal constraints in walk order leave their words
     int w1 = -1, w2 = -1;
     uint32_t r1 = 0, r2 = 0, left = 0;
@@ -939,7 +996,11 @@ __device__ __forceinline__ void score_piece(const ScoreArgs &a, const uint4 sg, 
     auto flush_rows = [&](uint32_t rows_hi, uint32_t pass0) {
         if (K::PC) return;
         __syncthreads();
-        for (uint32_t idx = threadIdx.x; idx < rows_hi * 8; idx += 256) {
+        uint32_t first_idx = threadIdx.x;
+        // the class kernels sit at their 80 registers: hoisted out of the segment loop, the row and the address a thread
+        // flushes to stay live through every walk and go to scratch; behind this they are worked out here, once a flush
+        if constexpr (K::CLS) asm volatile("" : "+v"(first_idx));
+        for (uint32_t idx = first_idx; idx < rows_hi * 8; idx += 256) {
             const uint32_t i = idx >> 2, q = idx & 3;               // i = counter row: (k * NS + j) * 2 + which
             const uint32_t j = (i >> 1) % NS, k = (i >> 1) / NS;
             uint32_t s = 0;

@@ -78,6 +78,7 @@ struct ScorePlan {
     uint64_t out_rows = 0;
     // ---- shape
     bool lit = false, light = false, cf = false, classes = false, cls_head = true, fuse = false;
+    int cls_tail = 3;                                   // tail descriptors the class compiler writes: 1 literals, 2 the lone class
     bool own_segments = false, via_stage = false, inline_prep = false, by_kernels = false;
     PlanCompile compile = PLAN_COMPILE_NONE;
     uint32_t np = 8, pdw = 0, n_entries = 0;
@@ -276,9 +277,12 @@ inline void plan_shape(ScorePlan &p, const ScoreRequest &rq, const PlanFacts &f)
     // that variant and the class program layout (the same 32 dwords per program).  NM_SCORE_CLASSES=0, read at every call,
     // keeps them on the 8-plane path (same-process A/B, tests/test_gpu_iupac_classes.py).  NM_SCORE_HEAD=0, read at every
     // call as well, compiles class programs without a head: every walk starts with plain moves and all literals stay in
-    // their words (tests/test_gpu_head_pair.py).
-    const char *cls_env = getenv("NM_SCORE_CLASSES"), *head_env = getenv("NM_SCORE_HEAD");
+    // their words (tests/test_gpu_head_pair.py).  NM_SCORE_TAIL, read at every call too, says which tail descriptors the
+    // compiler writes: unset both, 0 none (what is left behind the head is walked from the words), 1 the literal descriptors
+    // only, 2 the lone-class descriptor only (tests/test_gpu_tail_descriptors.py).  One device build: only programs differ.
+    const char *cls_env = getenv("NM_SCORE_CLASSES"), *head_env = getenv("NM_SCORE_HEAD"), *tail_env = getenv("NM_SCORE_TAIL");
     p.cls_head = !(head_env && atoi(head_env) == 0);
+    p.cls_tail = tail_env ? atoi(tail_env) & 3 : 3;
     p.classes = !rq.spec && !p.lit && !p.any_wide && p.all_compact && !p.cf && !(cls_env && atoi(cls_env) == 0);
     // The static segment table covers every bin; a batch whose candidates sit in a few bins only — the long tail of the
     // search: a handful of tasks still open among hundreds of bins — would launch thousands of workgroups that find no

@@ -332,6 +332,8 @@ ScorePlan run_case(const char *name, World &w, const Batch &b) {
           "shape lit %d light %d cf %d classes %d fuse %d own %d, expected %d %d %d %d %d %d", p.lit, p.light, p.cf, p.classes, p.fuse, p.own_segments, lit,
           light, cf, classes, n_active == 2 && cf && lit, own);
     CHECK(p.cls_head == !env_zero("NM_SCORE_HEAD"), "cls_head %d", p.cls_head);
+    const char *tail = getenv("NM_SCORE_TAIL");                                      // unset: both kinds of tail descriptor; 0, 1, 2
+    CHECK(p.cls_tail == (tail ? tail[0] - '0' : 3), "cls_tail %d", p.cls_tail);
     CHECK(p.np == np && p.pdw == pdw && p.n_entries == n_entries, "np %u pdw %u entries %u, expected %u %u %u", p.np, p.pdw, p.n_entries, np, pdw, n_entries);
     CHECK(p.prog_dw == (std::max<size_t>(order.size(), 1) + (cf ? n_entries : 0)) * pdw, "program room %zu dwords", p.prog_dw);
     const PlanCompile compile = b.spec ? PLAN_COMPILE_SPEC : order.empty() ? PLAN_COMPILE_NONE
@@ -466,6 +468,7 @@ void random_case(int i) {
     set_env("NM_STAGE_COPIES", chance(0.1) ? "1" : nullptr);
     set_env("NM_SCORE_CLASSES", chance(0.15) ? "0" : nullptr);
     set_env("NM_SCORE_HEAD", chance(0.15) ? "0" : nullptr);
+    { static const char *const tails[3] = {"0", "1", "2"}; set_env("NM_SCORE_TAIL", chance(0.3) ? tails[rnd(0, 2)] : nullptr); }
     set_env("NM_SCORE_PACK_TAILS", chance(0.3) ? "0" : nullptr);
     w.lists = chance(0.85);
     Batch b;
@@ -510,7 +513,7 @@ void random_case(int i) {
     run_case(("random " + std::to_string(i)).c_str(), w, b);
 }
 
-void clear_env() { for (const char *e : {"NM_ALL_SEGMENTS", "NM_STAGE_COPIES", "NM_SCORE_CLASSES", "NM_SCORE_HEAD", "NM_SCORE_PACK_TAILS"}) unsetenv(e); }
+void clear_env() { for (const char *e : {"NM_ALL_SEGMENTS", "NM_STAGE_COPIES", "NM_SCORE_CLASSES", "NM_SCORE_HEAD", "NM_SCORE_TAIL", "NM_SCORE_PACK_TAILS"}) unsetenv(e); }
 
 // n candidates dealt round the groups (slot s, bin b), s < n_slots, b < use_bins
 Batch dealt(const World &w, uint32_t n, uint32_t use_bins, uint32_t n_slots, int kind) {
