@@ -662,6 +662,50 @@ int nm_motif_fractions_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_
                              const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t n_bins,
                              uint64_t *counts);
 
+/* ---- PER-SITE READ COUNTS at motif sites: n_valid_cov and n_modified of the pileup record under every occurrence ----------------------
+ * Reference: none.  nm_motif_sites gives an occurrence's thresholded state, nm_motif_fractions_count reduces the sites' read fractions to a
+ * histogram; this pair writes the values themselves — what `modkit motif bed` + `bedtools intersect` against the bedMethyl file yield.
+ *
+ * CANDIDATES, OCCURRENCES and SITES are nm_motif_fractions_count's: cand_rs_slot names a READ-STATISTICS slot; strand 0 = the stripped
+ *   motif on '+' read against '+' records at the modified base, strand 1 = its reverse complement on '-' against '-' records; a SITE is an
+ *   occurrence whose modified base carries a kept record, a BARE occurrence one without.  select: NM_PILEUP_SITE, NM_PILEUP_BARE or both —
+ *   which of the two become records.
+ * nm_motif_pileup_count: contig_counts = int64[row_offset[n_cand]][4] in the row layout of nm_motif_sites_count (one row per candidate
+ *   and resident contig of its bin, nm_bin_contigs order; row_offset[0] = 0): fwd site, fwd bare, rev site, rev bare; all four whatever
+ *   select says.  Columns 0 + 2 are the histogram sums of nm_motif_fractions_count, columns 0 + 1 and 2 + 3 its occurrences.
+ *   cand_total[k] = records candidate k has under select.  The caller's table need not be zeroed.
+ * nm_motif_pileup_sites: count + prefix + fill.  A record = (contig id, contig-local 0-based position of the modified base,
+ *   code = (NM_PILEUP_MINUS on '-') | (NM_PILEUP_CODE_BARE for a bare occurrence), n_valid_cov, n_modified); a bare occurrence carries
+ *   0 / 0.  ORDER, cand_offset, windows by first_record / capacity / *n_written exactly as in nm_motif_sites: candidate-major, contigs in
+ *   nm_bin_contigs order, ascending position, '+' before '-'; written are exactly the records whose rank lies in [first_record,
+ *   first_record + capacity), to site_*[rank - first_record].  Nothing is truncated silently.
+ * Launches: at most 3 (count, one per reach width) + scan + gather + 3 (fill) whatever the batch holds.
+ * NM_EINVAL for NULLs, an empty select or bits above NM_PILEUP_BARE, and a bad bin; NM_ESTATE without an assembly or for a slot without
+ * read statistics; NM_ERANGE for 2^32 rows or work items and for a motif beyond NM_MAX_MOTIF_LEN / the reach limit as in nm_motif_sites.
+ * A candidate wrong in several ways is refused as nm_motif_fractions_count refuses it.  n_cand = 0 is NM_OK.  A refusal leaves the ctx
+ * usable. */
+#define NM_PILEUP_SITE 1u           /* select: occurrences with a kept record */
+#define NM_PILEUP_BARE 2u           /* select: occurrences without one */
+#define NM_PILEUP_CODE_BARE 1u      /* bit 0 of a record's code: a bare occurrence */
+#define NM_PILEUP_MINUS 4u          /* strand bit of a record's code */
+int nm_motif_pileup_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_rs_slot, const uint8_t *cand_len,
+                          const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t select,
+                          const uint64_t *row_offset, uint64_t *cand_total, int64_t *contig_counts);
+int nm_motif_pileup_sites(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_rs_slot, const uint8_t *cand_len,
+                          const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t select,
+                          uint64_t first_record, uint64_t capacity, uint32_t *site_contig, uint32_t *site_pos, uint8_t *site_code,
+                          uint32_t *site_valid, uint32_t *site_mod, uint64_t *cand_offset, uint64_t *n_written);
+/* The records of a span as the lines of motif-pileup.bed (host code, no device needed):
+ *   contig \t start \t start + 1 \t name \t n_valid_cov \t strand \t n_modified \t percent_modified \t bin \n
+ * percent_modified = 100 n_modified / n_valid_cov with two decimals, rounded half up in integers: (20000 n_modified + n_valid_cov) /
+ * (2 n_valid_cov) hundredths — no floating point takes part; empty for a bare occurrence.  Runs, names, size query (out == NULL),
+ * NM_ERANGE on a short buffer, NM_POST_THREADS and thread-independent bytes exactly as nm_motif_sites_text; NM_EINVAL for a contig >=
+ * n_contigs, a code that is none of the four, and a site whose n_valid_cov is 0 or below its n_modified. */
+int nm_motif_pileup_text(uint64_t n_records, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code,
+                         const uint32_t *site_valid, const uint32_t *site_mod, uint32_t n_seg, const uint64_t *seg_begin,
+                         const char *seg_text, const uint64_t *seg_text_off, uint32_t n_contigs, const char *contig_text,
+                         const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes);
+
 /* ---- MOTIF METHYLATION BY LOCAL GC CONTENT: the sites of a motif counted apart by the G + C around them ------------------------------
  * Reference: none (its known-issues page names "high systematic 5mC noise in high GC% regions" and advises to check by hand).  A true
  * methyltransferase motif is methylated whatever its surroundings; a noise motif where the local GC is high, and then so is the bin's

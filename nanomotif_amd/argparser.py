@@ -1,6 +1,6 @@
 """Command line of the MI355X build: the ``motif_discovery`` sub-command with the reference's arguments
 (nanomotif/argparser.py:13-136), plus ``--device`` for the GPU to use, the project's own ``motif_sites`` / ``motif_coverage`` /
-``motif_compare`` / ``motif_strands`` / ``motif_profile`` / ``motif_tracks`` / ``motif_fractions`` / ``motif_context`` / ``motif_gc`` / ``motif_overlap`` on a finished ``bin-motifs.tsv``, ``motif_kmers`` (which needs none), and the binnary sub-commands ``detect_contamination`` and
+``motif_compare`` / ``motif_strands`` / ``motif_profile`` / ``motif_tracks`` / ``motif_fractions`` / ``motif_pileup`` / ``motif_context`` / ``motif_gc`` / ``motif_overlap`` on a finished ``bin-motifs.tsv``, ``motif_kmers`` (which needs none), and the binnary sub-commands ``detect_contamination`` and
 ``include_contigs`` with the reference's flags (argparser.py:139-236).  MTase-linker is out of scope."""
 import argparse
 
@@ -13,7 +13,7 @@ def create_parser():
                                      formatter_class=formatter)
     parser.add_argument("--version", action="version", version="%(prog)s {}".format(__version__))
     sub = parser.add_subparsers(help="-- Command descriptions --", dest="command", title="commands",
-                                metavar="{motif_discovery, motif_sites, motif_coverage, motif_compare, motif_strands, motif_profile, motif_tracks, motif_fractions, motif_context, motif_gc, motif_overlap, motif_kmers, detect_contamination, include_contigs, check_installation}")
+                                metavar="{motif_discovery, motif_sites, motif_coverage, motif_compare, motif_strands, motif_profile, motif_tracks, motif_fractions, motif_pileup, motif_context, motif_gc, motif_overlap, motif_kmers, detect_contamination, include_contigs, check_installation}")
     p = sub.add_parser("motif_discovery", help="Finds motifs directly on bin level in provided assembly", add_help=False)
     p.add_argument("assembly", type=str, help="path to the assembly file.")
     p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
@@ -57,6 +57,7 @@ def create_parser():
     add_motif_profile_parser(sub)
     add_motif_tracks_parser(sub)
     add_motif_fractions_parser(sub)
+    add_motif_pileup_parser(sub)
     add_motif_context_parser(sub)
     add_motif_gc_parser(sub)
     add_motif_overlap_parser(sub)
@@ -575,6 +576,36 @@ def add_motif_fractions_parser(sub):
     o.add_argument("--min_sites", type=int, default=20, help="Sites below which a row is flagged few_sites. Default: %(default)s")
     o.add_argument("--minor_share", type=float, default=0.1,
                    help="Share of the sites the smaller mode of a bimodal motif needs, and a methylated / unmethylated motif may miss. Default: %(default)s")
+    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
+    gen = p.add_argument_group("general arguments")
+    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
+    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
+    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
+    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
+
+
+def add_motif_pileup_parser(sub):
+    """motif_pileup: the n_valid_cov and n_modified of the pileup record under every site of the motifs of bin-motifs.tsv files (no
+    counterpart on the reference's command line; modkit motif bed + bedtools intersect yield the table).  Arguments are those of
+    motif_fractions without the histogram options: same ingest, the pileup read as READ STATISTICS."""
+    p = sub.add_parser("motif_pileup", help="Reports the read counts under every motif site of bin-motifs.tsv files", add_help=False)
+    p.add_argument("assembly", type=str, help="path to the assembly file.")
+    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
+    gm = p.add_argument_group("contig bin arguments, use one of:")
+    g = gm.add_mutually_exclusive_group(required=True)
+    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
+    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
+    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
+    gm.add_argument("--extension", type=str, default=".fasta",
+                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
+    o = p.add_argument_group("Options")
+    o.add_argument("--bin_motifs", type=str, nargs="+", required=True, help="Path(s) to the bin-motifs.tsv whose motif sites are read (motif_discovery's output)")
+    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
+    o.add_argument("--all_occurrences", action="store_true", help="Also write the occurrences whose modified base carries no kept pileup record (0, 0 and an empty percentage)")
+    o.add_argument("--min_valid_read_coverage", type=int, default=5,
+                   help="Minimum valid base coverage (Nvalid_cov) for a pileup record to be read. Default: %(default)s")
+    o.add_argument("--min_valid_cov_to_diff_fraction", type=float, default=0.8,
+                   help="Minimum Nvalid_cov / (Nvalid_cov + Ndiff) for a pileup record to be read. Default: %(default)s")
     o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
     gen = p.add_argument_group("general arguments")
     gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")

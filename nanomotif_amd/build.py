@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SRC_HIP = [os.path.join(_CSRC, f) for f in ("nmscan.hip", "nmscore_classes.hip", "nmingest.hip", "nmwindows.hip", "nmmeth.hip", "nmbedgpu.hip", "nmfasta.hip", "nmsites.hip",
-                                                  "nmcoverage.hip", "nmcompare.hip", "nmstrands.hip", "nmprofile.hip", "nmtracks.hip", "nmfractions.hip",
+                                                  "nmcoverage.hip", "nmcompare.hip", "nmstrands.hip", "nmprofile.hip", "nmtracks.hip", "nmfractions.hip", "nmpileup.hip",
                                                   "nmcontext.hip", "nmkmers.hip", "nmgc.hip", "nmoverlap.hip")]
 SRC_HOST = [os.path.join(_CSRC, f) for f in ("nmbed.cpp", "nmhost.cpp", "nmcomm.cpp", "nmsearch.cpp", "nmpost.cpp", "nmpool.cpp", "nmsitestext.cpp")]
 OUT = os.path.join(_HERE, "libnmscan.so")

@@ -21,12 +21,6 @@ using namespace nmdetail;
 
 namespace {
 
-struct RsSlot {                              // the lookup tables of one read-statistics slot, per strand
-    const uint32_t *rank[2];
-    const uint64_t *base[2];
-    const uint2 *val[2];
-};
-
 struct FractionsArgs : ExportArgs {
     const uint32_t *cand_row0;               // first row of the candidate in the table
     const unsigned long long *cand_planes;   // [n_cand][2] presence planes P+ P- of the candidate's read-statistics slot
@@ -138,19 +132,11 @@ int nm_motif_fractions_count(nm_ctx *c, uint32_t n_cand, const uint32_t *cand_bi
     std::vector<uint32_t> slots(n_cand, 0);
     std::vector<unsigned long long> planes((size_t)n_cand * 2, 0);
     std::vector<RsSlot> rs(NM_MAX_MOD_SLOTS, RsSlot{});
-    const size_t words = plane_words(c);
     Staged st;
     int rc = stage_candidates(c, {n_cand, cand_bin, {cand_len, cand_modpos, cand_mask_offset, cand_masks}}, nullptr, nullptr, true, st,
                               [&](uint32_t k, uint32_t, uint64_t &) {                          // the candidate's read-statistics slot
-                                  const uint32_t slot = cand_rs_slot[k];
-                                  if (slot >= NM_MAX_MOD_SLOTS || !c->readstats[slot].present)
-                                      return fail(NM_ESTATE, "candidate %u: read-statistics slot %u holds no pileup (nm_readstats_upload)", k, slot);
-                                  const ReadStats &r = c->readstats[slot];
-                                  planes[(size_t)k * 2] = (unsigned long long)(uintptr_t)r.planes;
-                                  planes[(size_t)k * 2 + 1] = (unsigned long long)(uintptr_t)(r.planes + words);
-                                  rs[slot] = RsSlot{{r.rank[0], r.rank[1]}, {r.base[0], r.base[1]}, {r.val[0], r.val[1]}};
-                                  slots[k] = slot;
-                                  return (int)NM_OK;
+                                  slots[k] = cand_rs_slot[k];
+                                  return stage_readstats_slot(c, k, slots[k], rs.data(), planes.data() + (size_t)k * 2);
                               });
     if (rc) return rc;
     const uint64_t rows = st.rows;

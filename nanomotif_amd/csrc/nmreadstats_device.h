@@ -1,4 +1,4 @@
-// Device side of the read-statistics lookup (included by nmmeth.hip and nmfractions.hip, the two units that read a site's
+// Device side of the read-statistics lookup (included by nmmeth.hip, nmfractions.hip and nmpileup.hip, the units that read a site's
 // (n_valid_cov, n_modified) by rank): a mod code's presence plane says where kept records sit, the rank table counts the records of
 // the contig before every 512-bp block, and the records' values lie in plane (= position) order per strand — nothing is stored per
 // base pair.  One wave holds one chunk, a lane T_WORDS = 4 words of it, so a 16-word rank block is four consecutive lanes.
@@ -6,6 +6,24 @@
 #include "nmscan_device.h"
 
 namespace nmdetail {
+
+struct RsSlot {                              // the lookup tables of one read-statistics slot, per strand, as a kernel takes them
+    const uint32_t *rank[2];
+    const uint64_t *base[2];
+    const uint2 *val[2];
+};
+
+// Host, the check a unit hands to stage_candidates: candidate k's read-statistics slot — refused when it holds no pileup, else its tables
+// into rs[slot] and the addresses of its presence planes P+ P- into planes[0..1].
+inline int stage_readstats_slot(const nm_ctx *c, uint32_t k, uint32_t slot, RsSlot *rs, unsigned long long *planes) {
+    if (slot >= NM_MAX_MOD_SLOTS || !c->readstats[slot].present)
+        return fail(NM_ESTATE, "candidate %u: read-statistics slot %u holds no pileup (nm_readstats_upload)", k, slot);
+    const ReadStats &r = c->readstats[slot];
+    planes[0] = (unsigned long long)(uintptr_t)r.planes;
+    planes[1] = (unsigned long long)(uintptr_t)(r.planes + plane_words(c));
+    rs[slot] = RsSlot{{r.rank[0], r.rank[1]}, {r.base[0], r.base[1]}, {r.val[0], r.val[1]}};
+    return NM_OK;
+}
 
 // Value index of the first record of this lane's words on one strand: contig base + block rank + the records of the up to three
 // lanes before it in its rank block.  pw: the lane's presence words.  Every lane of the wave must call it (lane shuffles).

@@ -1,7 +1,8 @@
 // nm_motif_sites_text — the records of nm_motif_sites as the lines of motif-sites.bed, on a few host threads — and
 // nm_motif_compare_text, the records of nm_motif_compare_sites as the lines of switched-sites.bed: the same line with the
 // transition "a>b" in the state column — and nm_motif_strands_text, the records of nm_motif_strands_sites as the lines of hemi-sites.bed:
-// the pair "own-partner" in the state column and the partner's position in a ninth.
+// the pair "own-partner" in the state column and the partner's position in a ninth — and nm_motif_pileup_text, the records of
+// nm_motif_pileup_sites as the lines of motif-pileup.bed: n_valid_cov in the score column, n_modified and the percentage in the state's place.
 // The reference keeps the four position arrays of motif_model_contig(save_motif_positions=True) in memory
 // (find_motifs_bin.py:1322-1329) and writes no per-site file; the line format is this project's (README.md).
 // Two passes over the span: every thread sizes its share of the records exactly, the shares' offsets are a prefix sum, then every
@@ -48,6 +49,10 @@ const Labels TRANSITION_LABELS{TRANSITION_TEXT, TRANSITION_LEN, 9, 15u, NM_COMPA
 const char *const PAIR_TEXT[9] = {"mod-mod", "mod-nomod", "mod-nocall", "nomod-mod", "nomod-nomod", "nomod-nocall", "nocall-mod", "nocall-nomod",
                                   "nocall-nocall"};
 const Labels PAIR_LABELS{PAIR_TEXT, TRANSITION_LEN, 9, 15u, NM_STRANDS_MINUS};
+const Labels PILEUP_LABELS{nullptr, nullptr, 2, NM_PILEUP_CODE_BARE, NM_PILEUP_MINUS};      // (no label: the values stand in the state's place)
+
+// 100 mod / valid in hundredths, rounded half up in integers (valid > 0)
+inline uint64_t percent_hundredths(uint64_t mod, uint64_t valid) { return (20000 * mod + valid) / (2 * valid); }
 
 struct Span {
     const uint32_t *contig, *pos;
@@ -57,6 +62,8 @@ struct Span {
     const char *seg_text, *contig_text;
     Labels lab;
     const int32_t *seg_partner;                                          // per run the partner offset d (a ninth column), or NULL
+    const uint32_t *valid, *mod;                                         // motif-pileup.bed: a record's n_valid_cov and n_modified, or NULL
+    bool bare(uint64_t i) const { return code[i] & lab.mask; }
     // position of the partner of record i of run seg: pos + d on '+', pos - d on '-'
     int64_t partner(uint64_t i, uint32_t seg) const { return (int64_t)pos[i] + ((code[i] & lab.minus) ? -(int64_t)seg_partner[seg] : (int64_t)seg_partner[seg]); }
     // segment that holds record i (the last one whose begin is <= i; empty segments are passed over)
@@ -72,7 +79,11 @@ uint64_t size_range(const Span &s, uint64_t lo, uint64_t hi) {
         const uint64_t fixed = (s.seg_text_off[2 * seg + 2] - s.seg_text_off[2 * seg]) + 9;      // name + bin + 7 tabs + "0" + newline
         const uint32_t c = s.contig[i];
         const uint64_t p = s.pos[i];
-        bytes += (s.contig_text_off[c + 1] - s.contig_text_off[c]) + digits(p) + digits(p + 1) + 1 + s.lab.len[s.code[i] & s.lab.mask] + fixed;
+        bytes += (s.contig_text_off[c + 1] - s.contig_text_off[c]) + digits(p) + digits(p + 1) + 1 + fixed;
+        if (s.valid)                                                     // n_valid_cov for the "0", and n_modified \t [percent.dd] for the label
+            bytes += digits(s.valid[i]) - 1 + digits(s.mod[i]) + 1 + (s.bare(i) ? 0 : digits(percent_hundredths(s.mod[i], s.valid[i]) / 100) + 3);
+        else
+            bytes += s.lab.len[s.code[i] & s.lab.mask];
         if (s.seg_partner) bytes += 1 + digits((uint64_t)s.partner(i, seg));
     }
     return bytes;
@@ -95,13 +106,26 @@ char *write_range(const Span &s, uint64_t lo, uint64_t hi, char *out) {
         const uint64_t nl = s.seg_text_off[2 * seg + 1] - s.seg_text_off[2 * seg];
         memcpy(out, s.seg_text + s.seg_text_off[2 * seg], nl);
         out += nl;
-        memcpy(out, "\t0\t", 3);
-        out += 3;
+        *out++ = '\t';
+        out = put_u64(out, s.valid ? s.valid[i] : 0);
+        *out++ = '\t';
         *out++ = (s.code[i] & s.lab.minus) ? '-' : '+';
         *out++ = '\t';
-        const unsigned st = s.code[i] & s.lab.mask;
-        memcpy(out, s.lab.text[st], s.lab.len[st]);
-        out += s.lab.len[st];
+        if (s.valid) {
+            out = put_u64(out, s.mod[i]);
+            *out++ = '\t';
+            if (!s.bare(i)) {
+                const uint64_t h = percent_hundredths(s.mod[i], s.valid[i]);
+                out = put_u64(out, h / 100);
+                *out++ = '.';
+                *out++ = (char)('0' + h % 100 / 10);
+                *out++ = (char)('0' + h % 10);
+            }
+        } else {
+            const unsigned st = s.code[i] & s.lab.mask;
+            memcpy(out, s.lab.text[st], s.lab.len[st]);
+            out += s.lab.len[st];
+        }
         *out++ = '\t';
         const uint64_t bl = s.seg_text_off[2 * seg + 2] - s.seg_text_off[2 * seg + 1];
         memcpy(out, s.seg_text + s.seg_text_off[2 * seg + 1], bl);
@@ -118,11 +142,12 @@ char *write_range(const Span &s, uint64_t lo, uint64_t hi, char *out) {
 int records_text(const Labels &lab, uint64_t n, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code, uint32_t n_seg,
                  const uint64_t *seg_begin, const char *seg_text, const uint64_t *seg_text_off, uint32_t n_contigs, const char *contig_text,
                  const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes, const int32_t *seg_partner = nullptr,
-                 bool with_partner = false) {
+                 bool with_partner = false, const uint32_t *site_valid = nullptr, const uint32_t *site_mod = nullptr, bool with_values = false) {
     if (!n_bytes) return nm_set_error(NM_EINVAL, "NULL argument");
     *n_bytes = 0;
     if (n == 0) return NM_OK;
-    if (!site_contig || !site_pos || !site_code || !seg_begin || !seg_text || !seg_text_off || !contig_text || !contig_text_off || (with_partner && !seg_partner))
+    if (!site_contig || !site_pos || !site_code || !seg_begin || !seg_text || !seg_text_off || !contig_text || !contig_text_off || (with_partner && !seg_partner) ||
+        (with_values && (!site_valid || !site_mod)))
         return nm_set_error(NM_EINVAL, "NULL argument");
     if (n_seg == 0 || seg_begin[0] != 0 || seg_begin[n_seg] != n) return nm_set_error(NM_EINVAL, "the runs must cover the %llu records exactly", (unsigned long long)n);
     for (uint32_t s = 0; s < n_seg; ++s)
@@ -130,7 +155,7 @@ int records_text(const Labels &lab, uint64_t n, const uint32_t *site_contig, con
     unsigned n_thr = std::max(1u, std::min(16u, std::thread::hardware_concurrency() / 2));
     if (const char *e = getenv("NM_POST_THREADS")) n_thr = (unsigned)std::max(1, std::min(16, atoi(e)));
     n_thr = (unsigned)std::min<uint64_t>(n_thr, (n + 255) / 256);        // (a thread is not worth starting for less)
-    const Span sp{site_contig, site_pos, site_code, n_seg, seg_begin, seg_text_off, contig_text_off, seg_text, contig_text, lab, seg_partner};
+    const Span sp{site_contig, site_pos, site_code, n_seg, seg_begin, seg_text_off, contig_text_off, seg_text, contig_text, lab, seg_partner, site_valid, site_mod};
     auto lo_of = [&](unsigned t) { return n * t / n_thr; };
     std::vector<uint64_t> bytes(n_thr + 1, 0);
     std::vector<int> bad(n_thr, 0);
@@ -151,10 +176,15 @@ int records_text(const Labels &lab, uint64_t n, const uint32_t *site_contig, con
                 if (sp.partner(i, seg) < 0) { bad[t] = 2; return; }
             }
         }
+        if (site_valid)
+            for (uint64_t i = lo; i < hi; ++i)
+                if (!sp.bare(i) && (site_valid[i] == 0 || site_mod[i] > site_valid[i])) { bad[t] = 3; return; }
         bytes[t + 1] = size_range(sp, lo, hi);
     });
     for (unsigned t = 0; t < n_thr; ++t)
         if (bad[t] == 2) return nm_set_error(NM_EINVAL, "a record's partner lies before the start of its contig");
+    for (unsigned t = 0; t < n_thr; ++t)
+        if (bad[t] == 3) return nm_set_error(NM_EINVAL, "a site's n_valid_cov is 0 or below its n_modified");
     for (unsigned t = 0; t < n_thr; ++t)
         if (bad[t]) return nm_set_error(NM_EINVAL, "a record names a contig >= %u or carries a code that is none of the %u", n_contigs, 2 * lab.n);
     for (unsigned t = 0; t < n_thr; ++t) bytes[t + 1] += bytes[t];
@@ -187,4 +217,12 @@ extern "C" int nm_motif_strands_text(uint64_t n, const uint32_t *site_contig, co
                                      uint64_t *n_bytes) {
     return records_text(PAIR_LABELS, n, site_contig, site_pos, site_code, n_seg, seg_begin, seg_text, seg_text_off, n_contigs, contig_text,
                         contig_text_off, out, capacity, n_bytes, seg_partner_offset, true);
+}
+
+extern "C" int nm_motif_pileup_text(uint64_t n, const uint32_t *site_contig, const uint32_t *site_pos, const uint8_t *site_code, const uint32_t *site_valid,
+                                    const uint32_t *site_mod, uint32_t n_seg, const uint64_t *seg_begin, const char *seg_text, const uint64_t *seg_text_off,
+                                    uint32_t n_contigs, const char *contig_text, const uint64_t *contig_text_off, char *out, uint64_t capacity,
+                                    uint64_t *n_bytes) {
+    return records_text(PILEUP_LABELS, n, site_contig, site_pos, site_code, n_seg, seg_begin, seg_text, seg_text_off, n_contigs, contig_text,
+                        contig_text_off, out, capacity, n_bytes, nullptr, false, site_valid, site_mod, true);
 }

@@ -46,6 +46,12 @@ FRACTIONS_BUDGET_BYTES = 256 << 20             # default size of the table of on
 UNEXPLAINED_DTYPE =np.dtype([("set", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8)])   # ScanEngine.unexplained_sites
 
 
+PILEUP_SELECT = ("site", "bare")                 # NM_PILEUP_SITE / NM_PILEUP_BARE: occurrences with / without a kept record
+PILEUP_MINUS = 4                                 # NM_PILEUP_MINUS: the strand bit of a record of nm_motif_pileup_sites ...
+PILEUP_BARE = 1                                  # ... and NM_PILEUP_CODE_BARE: a bare occurrence (n_valid = n_mod = 0)
+PILEUP_RECORD_BYTES = 17                         # a record on the device: contig (4), position (4), code (1), n_valid_cov (4), n_modified (4)
+PILEUP_DTYPE = np.dtype([("candidate", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8), ("n_valid", np.uint32),
+                         ("n_mod", np.uint32)])
 GC_MAX_HALF = 31                               # NM_GC_MAX_HALF: positions a GC window reaches either side of the modified base
 GC_BUDGET_BYTES = 256 << 20                    # default size of the table of one library call of ScanEngine.motif_gc
 OVERLAP_MAX_PARTNERS = 4095                    # NM_OVERLAP_MAX_PARTNERS: partner motifs of one candidate of ScanEngine.motif_overlap
@@ -119,6 +125,18 @@ def site_state_set(states) -> int:
     if bad or not states:
         raise ValueError(f"states must be a non-empty selection of {SITE_STATES}, got {states!r}")
     return sum(1 << SITE_STATES.index(s) for s in set(states))
+
+
+def pileup_select(select) -> int:
+    """("site", "bare") -> NM_PILEUP_SITE | NM_PILEUP_BARE; ValueError for an unknown name or an empty selection."""
+    bits = 0
+    for s in select:
+        if s not in PILEUP_SELECT:
+            raise ValueError(f"unknown selection {s!r} (expected a selection of {PILEUP_SELECT})")
+        bits |= 1 << PILEUP_SELECT.index(s)
+    if bits == 0:
+        raise ValueError("no selection given")
+    return bits
 
 
 def transition_set(transitions) -> int:
@@ -985,17 +1003,18 @@ class ScanEngine:
         return names, rows, totals[:len(b)], table[:int(rows[-1])]
 
     @staticmethod
-    def _record_limit(max_records) -> int:
-        limit = SITE_BUDGET_BYTES // SITE_RECORD_BYTES if max_records is None else int(max_records)
+    def _record_limit(max_records, record_bytes=SITE_RECORD_BYTES) -> int:
+        limit = SITE_BUDGET_BYTES // record_bytes if max_records is None else int(max_records)
         if limit < 1:
             raise ValueError("max_records must be at least 1")
         return limit
 
-    def _record_windows(self, call, group_args, totals, limit: int, dtype, owner: str, unit: str):
-        """The window loop of the four record exports: consecutive owners (candidates, sets) are grouped while their ``totals`` fit
+    def _record_windows(self, call, group_args, totals, limit: int, dtype, owner: str, unit: str, values=()):
+        """The window loop of the record exports: consecutive owners (candidates, sets) are grouped while their ``totals`` fit
         ``limit``, and every group is fetched in windows of at most ``limit`` records — one, unless a single owner exceeds the limit.
         ``call``: the library's *_sites function; ``group_args(k, e)``: its arguments before first_record for the owners [k, e);
-        ``dtype``: the records' type, whose ``owner`` field is filled in here; ``unit``: what the library's message calls a group.
+        ``dtype``: the records' type, whose ``owner`` field is filled in here; ``unit``: what the library's message calls a group;
+        ``values``: the uint32 fields of ``dtype`` the call writes after the code (nm_motif_pileup_sites: n_valid, n_mod).
         The ctypes pointers of those arguments keep their arrays alive.  Yields (k, e, first_record, records of the group, the window's
         records)."""
         for k, e, held in _budget_groups(totals, limit):
@@ -1005,13 +1024,16 @@ class ScanEngine:
                 cap = min(limit, held - first) if held else 0
                 rec = np.zeros(cap, dtype=dtype)
                 contig, pos, code = (np.zeros(max(cap, 1), dtype=t) for t in (np.uint32, np.uint32, np.uint8))
+                more = [np.zeros(max(cap, 1), dtype=np.uint32) for _ in values]
                 off = np.zeros(e - k + 1, dtype=np.uint64)
                 written = C.c_uint64(0)
-                _lib.check(call(*args, first, cap, _ptr(contig, C.c_uint32), _ptr(pos, C.c_uint32), _ptr(code, C.c_uint8), _ptr(off, C.c_uint64),
-                                C.byref(written)))
+                _lib.check(call(*args, first, cap, _ptr(contig, C.c_uint32), _ptr(pos, C.c_uint32), _ptr(code, C.c_uint8),
+                                *(_ptr(m, C.c_uint32) for m in more), _ptr(off, C.c_uint64), C.byref(written)))
                 if int(off[-1]) != held or written.value != cap:
                     raise _lib.NmScanError(f"{call.__name__} delivered {written.value} of {cap} records ({int(off[-1])} in the {unit}, {held} counted)")
                 rec["contig"], rec["pos"], rec["code"] = contig[:cap], pos[:cap], code[:cap]
+                for name, m in zip(values, more):
+                    rec[name] = m[:cap]
                 # the owner of every record of the window: the prefix of the group, cut to [first, first + cap)
                 cut = np.clip(off.astype(np.int64) - first, 0, cap)
                 rec[owner] = np.repeat(np.arange(k, e, dtype=np.uint32), np.diff(cut))
@@ -1314,7 +1336,6 @@ class ScanEngine:
         the sum of n_modified over the sites.  ``bins``: 2..64.  A candidate of a mod code without resident read statistics is a
         ValueError.  Consecutive candidates share one library call while their table fits ``max_bytes`` (default
         ``FRACTIONS_BUDGET_BYTES``); a group always holds at least one candidate.  What is yielded does not depend on ``max_bytes``."""
-        from .contig_methylation import MOD_CODES
         bins = int(bins)
         if not FRACTIONS_MIN_BINS <= bins <= FRACTIONS_MAX_BINS:
             raise ValueError(f"bins {bins} outside {FRACTIONS_MIN_BINS}..{FRACTIONS_MAX_BINS}")
@@ -1322,11 +1343,15 @@ class ScanEngine:
         if limit < 1:
             raise ValueError("max_bytes must be at least 1")
         candidates = list(candidates)
+        return self._fraction_groups(candidates, self._readstats_batch(candidates), bins, limit)
+
+    def _readstats_batch(self, candidates: list) -> CandidateBatch:
+        """``candidates`` with their slots naming READ-STATISTICS slots; a mod code without resident read statistics is a ValueError."""
+        from .contig_methylation import MOD_CODES
         missing = sorted({str(c[1]) for c in candidates if c[1] not in self.readstats_mods})
         if missing:
             raise ValueError(f"no read statistics are resident for mod type(s) {', '.join(missing)} (resident: {', '.join(sorted(self.readstats_mods)) or 'none'})")
-        b = self.make_batch(candidates, slot_of=lambda mt: MOD_CODES.index(mt))
-        return self._fraction_groups(candidates, b, bins, limit)
+        return self.make_batch(candidates, slot_of=lambda mt: MOD_CODES.index(mt))
 
     def _fraction_groups(self, candidates, b: CandidateBatch, nb: int, limit: int):
         bins = [int(x) for x in b.bins]
@@ -1341,6 +1366,41 @@ class ScanEngine:
             _lib.check(self.lib.nm_motif_fractions_count(self.ctx, *self._batch_args(sub), nb, _ptr(table, C.c_uint64)))
             for j in range(k, e):
                 yield candidates[j], names[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
+
+    # ------------------------------------------------------------------ per-site read counts at motif sites (nm_motif_pileup_*)
+    def _pileup_counts(self, b: CandidateBatch, select: int):
+        return self._count_table(self.lib.nm_motif_pileup_count, self._batch_args(b), b, select, 4)
+
+    def motif_pileup_counts(self, candidates):
+        """Per (candidate, contig) the four occurrence counts (fwd site, fwd bare, rev site, rev bare) of every resident contig of the
+        candidate's bin (nm_motif_pileup_count), read against the READ STATISTICS of the candidate's mod code as ``motif_fractions`` reads
+        them: a site is an occurrence whose modified base carries a kept record, a bare occurrence one without.  Returns a list, per
+        candidate, of (contig names, int64[n_contigs, 4]).  A mod code without resident read statistics is a ValueError."""
+        b = self._readstats_batch(list(candidates))
+        names, rows, _, table = self._pileup_counts(b, 3)
+        return [(names[int(b.bins[k])], table[int(rows[k]):int(rows[k + 1])]) for k in range(len(b))]
+
+    def motif_pileup(self, candidates, select=("site",), max_records=None):
+        """Generator over the per-site read counts of ``candidates`` (sequence of (Motif, mod_type, bin)): for every occurrence under
+        ``select`` (a selection of "site", "bare") the n_valid_cov and n_modified of the kept pileup record under its modified base
+        (nm_motif_pileup_sites).  Yields ``SiteBatch`` objects in candidate order; their ``records`` (fields candidate, contig, pos, code,
+        n_valid, n_mod; code = 4 for the '-' strand | 1 for a bare occurrence, which carries 0 / 0) concatenated are the occurrences in the
+        order candidate, contig (``bin_contigs`` order), position, '+' before '-'; ``counts`` as ``motif_pileup_counts`` returns them.  No
+        batch holds more than ``max_records`` records (default: ``SITE_BUDGET_BYTES`` of device records, 17 bytes each).  The
+        concatenation does not depend on ``max_records``.  A mod code without resident read statistics is a ValueError."""
+        b = self._readstats_batch(list(candidates))
+        sel = pileup_select(select)
+        limit = self._record_limit(max_records, PILEUP_RECORD_BYTES)
+        return self._pileup_windows(b, sel, limit)
+
+    def _pileup_windows(self, b: CandidateBatch, sel: int, limit: int):
+        names, rows, totals, table = self._pileup_counts(b, sel)
+
+        def group_args(k, e):
+            sub = b.slice(k, e)
+            return (self.ctx, *self._batch_args(sub), sel)
+        windows = self._record_windows(self.lib.nm_motif_pileup_sites, group_args, totals, limit, PILEUP_DTYPE, "candidate", "batch", values=("n_valid", "n_mod"))
+        yield from self._site_batches(windows, b, names, rows, table)
 
     # ------------------------------------------------------------------ motif methylation by local GC content (nm_motif_gc_count)
     def motif_gc(self, candidates, half=31, max_bytes=None):
