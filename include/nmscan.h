@@ -322,6 +322,9 @@ int nm_hit_positions(nm_ctx *ctx, uint32_t contig_id, uint32_t mod_slot, uint8_t
  * [5] = workgroups of the last scoring launch, [6] = candidates of the last launch scored on the
  * strand-implied ("compact") state, [7] = on the general 4-plane state. */
 int nm_stats(nm_ctx *ctx, uint64_t what[8]);
+/* *parked = 1 when the last scoring launch was the class kernel that parks a chunk's state words in LDS (heavy narrow compact
+ * batches with IUPAC sets, not per-contig, no group of 29 - 32 or 57 - 64 candidates, NM_SCORE_PARK not 0), else 0. */
+int nm_last_score_parked(nm_ctx *ctx, int *parked);
 
 /* Per-CONTIG counters: what nm_score_batch sums over a bin, kept apart per contig — motif_model_contig
  * (find_motifs_bin.py:1285-1331) for every contig of the candidate's bin in one launch; the per-contig motif

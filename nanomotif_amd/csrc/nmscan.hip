@@ -466,6 +466,7 @@ struct LaunchShape {
     bool fuse;                // two slots in one workgroup column
     bool per_contig;
     bool classes;             // narrow compact non-literal heavy batch: the class-plane variants and their program layout
+    bool park;                // ... the one that parks the state words in LDS (never per-contig)
 };
 
 template <class K>
@@ -484,7 +485,7 @@ void launch_score(const ScoreArgs &a, uint32_t gx, uint32_t gy, const LaunchShap
     if (sh.per_contig) {      // (candidate, contig) counters: the plain one-slot-per-column kernels with the other reduction key
         if (sh.wide == 2 && sh.compact) launch_variant<Variant<3, 3, true, 1, false, false, true>>(a, gx, gy, s);
         else if (sh.wide == 2) launch_variant<Variant<3, 3, false, 1, false, false, true>>(a, gx, gy, s);
-        else if (!sh.wide && sh.compact && sh.classes) launch_score_classes(a, gx, gy, true, s);
+        else if (!sh.wide && sh.compact && sh.classes) launch_score_classes(a, gx, gy, true, false, s);
         else if (!sh.wide && sh.compact) launch_variant<Variant<1, 1, true, 1, false, false, true>>(a, gx, gy, s);
         else if (!sh.wide) launch_variant<Variant<1, 1, false, 1, false, false, true>>(a, gx, gy, s);
         else if (sh.compact) launch_variant<Variant<2, 2, true, 1, false, false, true>>(a, gx, gy, s);
@@ -495,7 +496,7 @@ void launch_score(const ScoreArgs &a, uint32_t gx, uint32_t gy, const LaunchShap
         if (sh.compact) launch_by_load<3, true, false>(a, gx, gy, sh, s);
         else launch_by_load<3, false, false>(a, gx, gy, sh, s);
     } else if (!sh.wide && sh.compact) {
-        if (sh.classes) launch_score_classes(a, gx, gy, false, s);
+        if (sh.classes) launch_score_classes(a, gx, gy, false, sh.park, s);
         else if (sh.lit) launch_by_load<1, true, true>(a, gx, gy, sh, s);
         else launch_by_load<1, true, false>(a, gx, gy, sh, s);
     } else if (!sh.wide) launch_by_load<1, false, false>(a, gx, gy, sh, s);
@@ -611,6 +612,7 @@ int score_collect(nm_ctx *c, const ScoreRun &r, nm_ctx::Waiting &wait_slot) {
     c->last_wgs = p.last_wgs;
     c->last_compact = p.all_compact ? p.n_prog : 0;
     c->last_general = p.all_compact ? 0 : p.n_prog;
+    c->last_parked = p.n_prog && p.park;
     if (r.rq.defer) {
         nmdetail::wait_set(c, wait_slot, nm_ctx::Waiting{r.hs + p.off_counts, p.out_bytes, c->cur_stage, true});
     } else if (p.via_stage) {
@@ -756,7 +758,7 @@ int score_impl(nm_ctx *c, const ScoreRequest &rq) {
     a.pieces_per_run = p.pieces_per_run;
     a.fine_log2 = p.fine_log2;
     a.j_big = p.j_big;
-    const LaunchShape shape{p.any_wide, p.all_compact, p.lit, p.cf, p.fuse, p.per_contig, p.classes};
+    const LaunchShape shape{p.any_wide, p.all_compact, p.lit, p.cf, p.fuse, p.per_contig, p.classes, p.park};
     if (r.timed_launch && p.compile != PLAN_COMPILE_SPEC) HIP_TRY(hipEventRecord(r.e0, r.sst));
     if (p.n_prog) launch_score(a, p.gx, p.gy, shape, r.sst);   // else nothing resident for this batch: the zeroed table is the answer
     HIP_TRY(hipGetLastError());
@@ -1546,6 +1548,12 @@ int nm_stats(nm_ctx *c, uint64_t what[8]) {
     what[5] = c->last_wgs;
     what[6] = c->last_compact;
     what[7] = c->last_general;
+    return NM_OK;
+}
+
+int nm_last_score_parked(nm_ctx *c, int *parked) {
+    if (!c || !parked) return fail(NM_EINVAL, "NULL argument");
+    *parked = c->last_parked ? 1 : 0;
     return NM_OK;
 }
 

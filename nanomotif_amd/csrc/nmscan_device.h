@@ -36,12 +36,19 @@ typedef const uint8_t __attribute__((address_space(4))) *cu8p;
 
 // CLS (narrow, compact, non-literal heavy batches only): every IUPAC set is ONE constraint on the class planes
 // (ClassTile / ClassWalk below); the program is the 32-dword class layout, of which PDW and NP say nothing.
-template <int GN_, int GP_, bool COMPACT_, int NS_, bool LIT_, bool CF_, bool PC_ = false, bool CLS_ = false>
+// PARK (the CLS variant that is not per-contig): the chunk's state words M and U, read by nothing but the finalize of a walk, wait
+// in LDS through the walks — a slot per thread, written once per entry and read back behind every walk's last constraint.
+// Their eight registers are free where the body peaks: 72 VGPRs, 7 waves per SIMD.  A pass counts PLAN_PARK_ROWS candidates, so
+// that seven workgroups' counters and park areas fit a CU's LDS (profiles/r27/park_state.md).
+template <int GN_, int GP_, bool COMPACT_, int NS_, bool LIT_, bool CF_, bool PC_ = false, bool CLS_ = false, bool PARK_ = false>
 struct Variant {
     static constexpr int GN = GN_, GP = GP_, NS = NS_;
     static constexpr bool COMPACT = COMPACT_, LIT = LIT_, CF = CF_, PC = PC_;   // PC: counters keyed by (candidate, contig)
-    static constexpr bool CLS = CLS_;
+    static constexpr bool CLS = CLS_, PARK = PARK_;
     static_assert(!CLS || (GN == 1 && GP == 1 && COMPACT && NS == 1 && !LIT && !CF), "class planes: narrow compact heavy variants only");
+    static_assert(!PARK || (CLS && !PC), "parked state words: the class variant with LDS counters only");
+    static constexpr int ROWS = PARK ? (int)PLAN_PARK_ROWS : BMAX;   // LDS counter rows of a workgroup = candidates of a pass (NS = 1)
+    static_assert(BMAX == (int)PLAN_PASS_ROWS, "the plan counts passes of BMAX candidates");
     static constexpr int NW = T_WORDS + GN + GP;
     static constexpr int NP = LIT ? 4 : 8;                 // planes per tile
     static constexpr int NST = COMPACT ? 2 : 4;            // state planes per slot
@@ -728,8 +735,8 @@ struct ScoreArgs {
     const uint32_t *strip_rows; // and the 64 strips of every packed row
 };
 
-// the CLS variants (Variant<1, 1, true, 1, false, false, PC, true>): instantiated by nmscore_classes.hip
-void launch_score_classes(const ScoreArgs &a, uint32_t gx, uint32_t gy, bool per_contig, hipStream_t s);
+// the CLS variants (Variant<1, 1, true, 1, false, false, PC, true, PARK>): instantiated by nmscore_classes.hip
+void launch_score_classes(const ScoreArgs &a, uint32_t gx, uint32_t gy, bool per_contig, bool park, hipStream_t s);
 
 }  // namespace nmdetail
 
@@ -811,10 +818,37 @@ __device__ __forceinline__ void score_heavy(const ScoreArgs &a, const TileT &til
     constexpr int MDW = K::CLS ? CLS_PROG_DW : K::PDW;
     static_assert(!K::CLS || CLS_PROG_DW == 2 * K::PDW, "a class program takes the room of both halves of a plain one");
     std::conditional_t<K::CLS, ClassWalk<K, TileT>, JointWalk<K>> jw;
+    // PARK: the state words leave their registers here, once per entry, for the thread's own slot behind the counter rows
+    // ([plane][threadIdx.x]: a lane reads only what it wrote, and a wave's LDS operations complete in order — no barrier);
+    // the compiler barrier keeps the stored registers from being handed to the reads below
+    auto park_slot = [&]() { return reinterpret_cast<uint4 *>(lds_acc + K::ROWS * 2 * 64) + threadIdx.x; };
+    if constexpr (K::PARK) {
+        uint4 *const park = park_slot();
+        park[0] = make_uint4(sw[0][0], sw[0][1], sw[0][2], sw[0][3]);
+        park[256] = make_uint4(sw[1][0], sw[1][1], sw[1][2], sw[1][3]);
+        asm volatile("" ::: "memory");
+    }
+    // PARK: the next candidate's program is asked for behind the walk instead of at the top of the next one, into the scalar
+    // registers the walk has finished with.  Where the two s_load_dwordx16 land is the scheduler's choice: as built (ROCm 7.2) they
+    // sink below the reads of the parked words and the finalize, in front of the two ds_add_u32, and the next walk still starts
+    // with its s_waitcnt lgkmcnt(0); the finalize waits for the LDS reads alone (profiles/r27/park_state.md: measured, not explained)
+    auto fetch_ahead = [&](uint32_t k, uint32_t (&m)[MDW]) {
+        typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+        typedef const u32x16 __attribute__((address_space(4))) *cu32x16p;
+        const cu32x16p prog = (cu32x16p)(a.programs + (size_t)(k0 + k) * (2 * K::PDW));
+        const u32x16 lo = prog[0], hi = prog[1];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { m[i] = lo[i]; m[16 + i] = hi[i]; }
+    };
+    [[maybe_unused]] uint32_t ahead[MDW];
+    if constexpr (K::PARK) fetch_ahead(0, ahead);
     for (uint32_t k = 0; k < nb; ++k) {
         cu32p prog = (cu32p)(a.programs + (size_t)(k0 + k) * (2 * K::PDW));
         uint32_t m[MDW];
-        if constexpr (K::CLS) {            // two loads of 16 dwords each, whatever the walk looks at first
+        if constexpr (K::PARK) {
+#pragma unroll
+            for (int i = 0; i < MDW; ++i) m[i] = ahead[i];
+        } else if constexpr (K::CLS) {     // two loads of 16 dwords each, whatever the walk looks at first
             typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
             typedef const u32x16 __attribute__((address_space(4))) *cu32x16p;
             const u32x16 lo = ((cu32x16p)prog)[0], hi = ((cu32x16p)prog)[1];
@@ -825,13 +859,27 @@ __device__ __forceinline__ void score_heavy(const ScoreArgs &a, const TileT &til
             for (int i = 0; i < MDW; ++i) m[i] = prog[i];
         }
         jw.walk(m, tile, basef, baser);
+        // PARK: the words come back behind the walk's last constraint (two ds_read_b128; the barrier keeps them from rising into the walk)
+        [[maybe_unused]] uint32_t pw[2][T_WORDS];
+        if constexpr (K::PARK) {
+            asm volatile("" ::: "memory");
+            fetch_ahead(min(k + 1, nb - 1), ahead);
+            const uint4 *const park = park_slot();
+            const uint4 pm = park[0], pu = park[256];
+            pw[0][0] = pm.x; pw[0][1] = pm.y; pw[0][2] = pm.z; pw[0][3] = pm.w;
+            pw[1][0] = pu.x; pw[1][1] = pu.y; pw[1][2] = pu.z; pw[1][3] = pu.w;
+        }
+        auto state = [&](int i, int t) -> uint32_t {           // M (0) or U (1) of word t
+            if constexpr (K::PARK) return pw[i][t];
+            else return sw[i][t];
+        };
         uint32_t n_mod = 0, n_non = 0;
 #pragma unroll
         for (int t = 0; t < T_WORDS; ++t) {
             if (K::COMPACT) {
                 const uint32_t sites = jw.accf[t] | jw.accr[t];  // forward sites sit on the canonical base, reverse on its complement
-                n_mod += __popc(sites & sw[0][t]);
-                n_non += __popc(sites & sw[1][t]);
+                n_mod += __popc(sites & state(0, t));
+                n_non += __popc(sites & state(1, t));
                 // CLS: v_bcnt_u32_b32 adds to its second operand; pinned between the words the two counters stay two chains
                 // of four v_bcnt (left alone the compiler sums each counter as a tree and joins it with a v_add3_u32)
                 if constexpr (K::CLS) { asm("" : "+v"(n_mod)); asm("" : "+v"(n_non)); }
@@ -921,7 +969,7 @@ template <class T>
 struct TileTag { using type = T; };
 
 // With NS > 1 a tile's sequence planes are loaded and expanded once and serve the candidates of all NS slots (each slot
-// brings its own state planes); with NS = 1 the slot comes from blockIdx.y.  A pass handles up to BMAX / NS candidates
+// brings its own state planes); with NS = 1 the slot comes from blockIdx.y.  A pass handles up to ROWS / NS candidates (ROWS = BMAX but for PARK)
 // per slot; LDS rows are [candidate k][slot j].
 // One PIECE of work: the chunks [sg.x, sg.x + sg.y) of bin sg.z, all candidates of the workgroup's slot column(s), counters
 // accumulated in LDS and flushed to the count table at the end.  Called once per workgroup by score_kernel (piece = a
@@ -930,7 +978,7 @@ template <class K>
 __device__ __forceinline__ void score_piece(const ScoreArgs &a, const uint4 sg, const StatePlanes (&stp)[K::NS], const bool (&is_c)[K::NS],
                                             uint32_t *lds_acc, const int lane, const uint32_t wave) {
     constexpr int NS = K::NS;
-    constexpr uint32_t H = BMAX / NS;
+    constexpr uint32_t H = K::ROWS / NS;
     // the wave's first chunk is requested before anything else of the segment is looked at (candidate ranges, LDS
     // clearing, the barrier): a workgroup lives for four chunks per wave, its start-up chain would otherwise sit
     // in front of every fourth memory round trip
@@ -1006,8 +1054,16 @@ __device__ __forceinline__ void score_piece(const ScoreArgs &a, const uint4 sg, 
             uint32_t s = 0;
 #pragma unroll 4
             for (int jj = 0; jj < 16; ++jj) s += lds_acc[i * 64 + q * 16 + jj];
-            s += __shfl_xor(s, 1);
-            s += __shfl_xor(s, 2);
+            // PARK: the lane pattern of a swizzle is an immediate, where __shfl_xor holds the lane index through every walk (in
+            // scratch at 72 registers).  The only reason for the second path is that register: if the PARK kernel no longer
+            // compiles to 72 VGPRs without scratch (73 is 6 waves: the unparked kernel plus an LDS round trip a walk), look here first
+            if constexpr (K::PARK) {
+                s += (uint32_t)__builtin_amdgcn_ds_swizzle((int)s, (1 << 10) | 0x1f);
+                s += (uint32_t)__builtin_amdgcn_ds_swizzle((int)s, (2 << 10) | 0x1f);
+            } else {
+                s += __shfl_xor(s, 1);
+                s += __shfl_xor(s, 2);
+            }
             if (q == 0 && s) {
                 uint4 rj = range[0];
 #pragma unroll
@@ -1041,8 +1097,13 @@ __device__ __forceinline__ void score_piece(const ScoreArgs &a, const uint4 sg, 
         clear_rows(rows_hi);
         for (uint32_t ck = wave; ck < sg.y; ck += 4) {
             RawChunk<K> cur;
-            if constexpr (LIST) cur.load_entry(a.seq, stp, ((cu32p)a.work_list)[sg.x + ck], a.strip_rows, lane);
-            else cur.load(a.seq, stp, sg.x + ck, lane);
+            // PARK: what the loads derive from the lane (its word offset, its place in a packed row) is worked out per entry;
+            // hoisted, it stays live through every walk of the segment and goes to scratch.  Compiler-dependent like the swizzles
+            // of flush_rows: after a compiler change check 72 VGPRs, ScratchSize 0, Occupancy 7 in the resource-usage remark
+            int load_lane = lane;
+            if constexpr (K::PARK) asm volatile("" : "+v"(load_lane));
+            if constexpr (LIST) cur.load_entry(a.seq, stp, ((cu32p)a.work_list)[sg.x + ck], a.strip_rows, load_lane);
+            else cur.load(a.seq, stp, sg.x + ck, load_lane);
             score_chunk(cur, pass0, LIST ? 0u : sg.x + ck);
         }
         flush_rows(rows_hi, pass0);
@@ -1051,7 +1112,8 @@ __device__ __forceinline__ void score_piece(const ScoreArgs &a, const uint4 sg, 
 
 // (CLS: a negative constraint of the boundary-chunk body shifts two planes; asked for 6 waves the scheduler keeps its
 // temporaries inside the 80 VGPRs of the 8-plane variant, without scratch)
-#define NM_SCORE_BOUNDS __launch_bounds__(256, (K::GN + K::GP > 2 ? 2 : (K::LIT ? NM_LIT_WAVES : (K::CLS ? 6 : 4))))
+// (PARK: seven; the per-contig twin asked for seven without parking spills)
+#define NM_SCORE_BOUNDS __launch_bounds__(256, (K::GN + K::GP > 2 ? 2 : (K::LIT ? NM_LIT_WAVES : (K::CLS ? (K::PARK ? 7 : 6) : 4))))
 
 // per-slot facts are read from the kernel arguments once per workgroup
 #define NM_SLOT_SETUP                                                                                               \
@@ -1067,7 +1129,8 @@ __device__ __forceinline__ void score_piece(const ScoreArgs &a, const uint4 sg, 
 
 template <class K>
 __global__ NM_SCORE_BOUNDS void score_kernel(ScoreArgs a) {
-    __shared__ uint32_t lds_acc[BMAX * 2 * 64];
+    // the counter rows, and behind them the park area of a PARK variant: [2][256] uint4, outside every row a pass clears or flushes
+    __shared__ alignas(16) uint32_t lds_acc[K::ROWS * 2 * 64 + (K::PARK ? 2 * 256 * 4 : 0)];
     // the workgroup's piece of the segment table (nmscore_plan.h: plan_block_piece and plan_cut_piece, shared with the host check —
     // the XCD-aware runs, the split and the finer cut of the pieces dispatched last)
     const PlanGrid grid{a.n_segments, a.split_log2, a.pieces_per_run, a.j_big, a.fine_log2};
@@ -1096,8 +1159,9 @@ __global__ NM_SCORE_BOUNDS void score_kernel(ScoreArgs a) {
 #ifdef NM_SCORE_CLASSES_UNIT
 namespace nmdetail {
 
-void launch_score_classes(const ScoreArgs &a, uint32_t gx, uint32_t gy, bool per_contig, hipStream_t s) {
+void launch_score_classes(const ScoreArgs &a, uint32_t gx, uint32_t gy, bool per_contig, bool park, hipStream_t s) {
     if (per_contig) hipLaunchKernelGGL((score_kernel<Variant<1, 1, true, 1, false, false, true, true>>), dim3(gx, gy), dim3(256), 0, s, a);
+    else if (park) hipLaunchKernelGGL((score_kernel<Variant<1, 1, true, 1, false, false, false, true, true>>), dim3(gx, gy), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((score_kernel<Variant<1, 1, true, 1, false, false, false, true>>), dim3(gx, gy), dim3(256), 0, s, a);
 }
 

@@ -204,6 +204,7 @@ struct nm_ctx {
     unsigned long long *d_other = nullptr;
     uint64_t other_letters = 0;
     uint64_t launches = 0, last_wgs = 0, last_compact = 0, last_general = 0;
+    bool last_parked = false;                         // the last scoring launch was the parked class kernel (nm_last_score_parked)
     // multi-GPU exchange (nmcomm.cpp): RCCL communicator, its stream, one completion event per table buffer
     void *comm = nullptr;
     int comm_rank = 0, comm_world = 0;

@@ -27,6 +27,11 @@ struct CandRec {
 struct PlanU4 { uint32_t x, y, z, w; };                 // a range or segment entry as the kernels read it (uint4)
 
 constexpr size_t PLAN_STAGE_DIRECT_MAX = (size_t)4 << 20;      // count tables and staged tables up to here take the short ways
+// candidates of a (slot, bin) group one pass of score_kernel counts in LDS (BMAX, nmscan_internal.h), and what the parked class
+// kernel has room for beside its park area (nmscan_device.h: Variant::PARK)
+constexpr uint32_t PLAN_PASS_ROWS = 32, PLAN_PARK_ROWS = 28;
+// workgroups a CU holds at once: the parked class kernel runs 7 waves per SIMD, every other heavy kernel 6 or fewer
+constexpr uint32_t PLAN_RESIDENT_PER_CU = 6, PLAN_RESIDENT_PER_CU_PARKED = 7;
 
 // What a scoring call is asked for; an entry point fills the fields it uses.
 struct ScoreRequest {
@@ -75,9 +80,11 @@ struct ScorePlan {
     uint32_t n_active_bins = 0, n_groups = 0;
     size_t n_active_segs = 0;
     bool use_list = false, pack = false;                // the batch walks a work list (heavy, not per-contig), the one with packed tails
+    bool park_fits = true;                              // no (slot, bin) group takes more passes at PLAN_PARK_ROWS candidates than at PLAN_PASS_ROWS
     uint64_t out_rows = 0;
     // ---- shape
     bool lit = false, light = false, cf = false, classes = false, cls_head = true, fuse = false;
+    bool park = false;                                  // the class kernel that parks a chunk's state words in LDS (7 waves per SIMD)
     int cls_tail = 3;                                   // tail descriptors the class compiler writes: 1 literals, 2 the lone class
     bool own_segments = false, via_stage = false, inline_prep = false, by_kernels = false;
     PlanCompile compile = PLAN_COMPILE_NONE;
@@ -249,7 +256,11 @@ inline int plan_classify(ScorePlan &p, const ScoreRequest &rq, const PlanFacts &
     size_t list_segs = 0;
     for (uint32_t b = 0; b < n_bins; ++b) {
         uint32_t groups = 0;
-        for (uint32_t i = 0; i < p.n_active; ++i) groups += bucket[(size_t)p.active[i] * n_bins + b + 1] > 0;
+        for (uint32_t i = 0; i < p.n_active; ++i) {
+            const uint32_t n = bucket[(size_t)p.active[i] * n_bins + b + 1];
+            groups += n > 0;
+            if ((n + PLAN_PARK_ROWS - 1) / PLAN_PARK_ROWS != (n + PLAN_PASS_ROWS - 1) / PLAN_PASS_ROWS) p.park_fits = false;
+        }
         if (!groups) continue;
         p.n_groups += groups;
         bin_active[b] = 1;
@@ -284,6 +295,12 @@ inline void plan_shape(ScorePlan &p, const ScoreRequest &rq, const PlanFacts &f)
     p.cls_head = !(head_env && atoi(head_env) == 0);
     p.cls_tail = tail_env ? atoi(tail_env) & 3 : 3;
     p.classes = !rq.spec && !p.lit && !p.any_wide && p.all_compact && !p.cf && !(cls_env && atoi(cls_env) == 0);
+    // A class batch that is not per-contig runs the parked instantiation (nmscan_device.h: Variant::PARK; 28 candidates a pass,
+    // 7 waves per SIMD) unless a group would pay for the smaller pass with one more walk over its segments (29 - 32 and 57 - 64
+    // candidates).  NM_SCORE_PARK=0, read at every call as well, keeps the batch on the unparked instantiation (same-process
+    // A/B, tests/test_gpu_score_park.py).
+    const char *park_env = getenv("NM_SCORE_PARK");
+    p.park = p.classes && !p.per_contig && p.park_fits && !(park_env && atoi(park_env) == 0);
     // The static segment table covers every bin; a batch whose candidates sit in a few bins only — the long tail of the
     // search: a handful of tasks still open among hundreds of bins — would launch thousands of workgroups that find no
     // candidate range and leave.  Such a batch brings its own table: the segments of the bins it has candidates for.
@@ -370,14 +387,14 @@ inline void plan_fill(const ScorePlan &p, const ScoreRequest &rq, const PlanFact
     }
 }
 
-// ---- 5. the grid.  Workgroups that will find candidates, against what the device runs at once (~6 per CU): below ~2 rounds of
+// ---- 5. the grid.  Workgroups that will find candidates, against what the device runs at once (6 per CU, 7 of the parked class kernel): below ~2 rounds of
 // workgroups the last, partly filled round is a large share of the launch -> smaller pieces.  The grid is runs of pieces (8 for
 // the XCD-remapped heavy variants, 1 for the streaming ones); in every run the pieces a full round of resident workgroups would
 // take LAST are cut finer (down to 4 chunks = one per wave).  score_kernel (nmscan_device.h) decodes blockIdx.x accordingly.
 inline void plan_geometry(ScorePlan &p, const PlanFacts &f) {
     uint64_t est_wgs = (uint64_t)p.n_segments * p.n_groups / std::max<uint32_t>(p.own_segments ? p.n_active_bins : f.n_bins, 1);
     if (p.light && p.n_active == 2 && p.lit) est_wgs = (est_wgs + 1) / 2;   // fused slots: one workgroup serves both
-    const uint64_t resident = (uint64_t)f.n_cus * 6;
+    const uint64_t resident = (uint64_t)f.n_cus * (p.park ? PLAN_RESIDENT_PER_CU_PARKED : PLAN_RESIDENT_PER_CU);
     uint32_t split_log2 = 0;
     while (split_log2 < 2 && (est_wgs << split_log2) < 2 * resident) ++split_log2;      // measured: halves win below ~2 rounds, quarters never
     if (f.opt_split >= 0) split_log2 = (uint32_t)f.opt_split;

@@ -1625,7 +1625,9 @@ class ScanEngine:
         _lib.check(self.lib.nm_stats(self.ctx, w))
         keys = ["total_bp", "padded_bp", "seq_plane_bytes", "state_plane_bytes", "launches", "last_workgroups",
                 "last_compact", "last_general"]
-        return dict(zip(keys, [int(x) for x in w]))
+        parked = C.c_int(0)
+        _lib.check(self.lib.nm_last_score_parked(self.ctx, C.byref(parked)))
+        return {**dict(zip(keys, [int(x) for x in w])), "last_parked": int(parked.value)}
 
     def timing_reset(self, enable=True):
         """True / 1: collect the scoring launches; 2: every device phase of the library (pre-filters, window gathers, window

@@ -1,6 +1,7 @@
 // Stand-alone check of the scoring plan (nanomotif_amd/csrc/nmscore_plan.h) on the CPU: random and directed batches, every
 // plan compared with a plain restatement written here, the work lists of the heavy kernels (nmscore_worklist.h) included: the grid
 // of every planned batch reaches every strip of sequence of every active bin exactly once.  Build: g++ -O2 -std=c++17 driver.cpp -o plan_check; run: ./plan_check [seed]
+// (./plan_check park: the cases of the parked class kernel alone, one line per planned batch — tests/test_score_park_host.py)
 // (tests/test_score_plan_host.py does both, a second time with -fsanitize=address,undefined where that links).
 #include <cinttypes>
 #include <cstdarg>
@@ -310,8 +311,16 @@ ScorePlan run_case(const char *name, World &w, const Batch &b) {
         if (bin_used[bb]) { ++n_act_bins; n_act_segs += (w.nchunks[bb] + f.seg_chunks - 1) / f.seg_chunks; }
         if (bin_used[bb] && w.lists) n_act_list_segs += (wl.bin_len[bb] + f.seg_chunks - 1) / f.seg_chunks;
     }
-    for (size_t i = 0; i < order.size(); ++i)
-        if (i == 0 || b.slot[order[i]] != b.slot[order[i - 1]] || b.bin[order[i]] != b.bin[order[i - 1]]) ++n_groups;
+    // the park rule: no (slot, bin) group takes more passes of 28 candidates than of 32 (sizes 29 - 32 and 57 - 64 do)
+    bool park_fits = true;
+    for (size_t i = 0, from = 0; i < order.size(); ++i) {
+        if (i == 0 || b.slot[order[i]] != b.slot[order[i - 1]] || b.bin[order[i]] != b.bin[order[i - 1]]) { ++n_groups; from = i; }
+        if (i + 1 == order.size() || b.slot[order[i + 1]] != b.slot[order[i]] || b.bin[order[i + 1]] != b.bin[order[i]]) {
+            const size_t size = i + 1 - from;
+            if ((size + 27) / 28 != (size + 31) / 32) park_fits = false;
+        }
+    }
+    CHECK(p.park_fits == park_fits, "park_fits %d, the group sizes say %d", p.park_fits, park_fits);
     // a heavy batch that is not per-contig walks the work list: its segments are counted over list positions
     const bool use_list = w.lists && !b.per_contig && !(order.size() <= 6 * (size_t)n_groups && !f.opt_no_cf);
     CHECK(p.use_list == use_list && p.pack == (use_list && pack == 1), "use_list %d pack %d, expected %d %d", p.use_list, p.pack, use_list, use_list && pack == 1);
@@ -331,6 +340,8 @@ ScorePlan run_case(const char *name, World &w, const Batch &b) {
     CHECK(p.lit == lit && p.light == light && p.cf == cf && p.classes == classes && p.fuse == (n_active == 2 && cf && lit) && p.own_segments == own,
           "shape lit %d light %d cf %d classes %d fuse %d own %d, expected %d %d %d %d %d %d", p.lit, p.light, p.cf, p.classes, p.fuse, p.own_segments, lit,
           light, cf, classes, n_active == 2 && cf && lit, own);
+    const bool park = classes && !b.per_contig && park_fits && !env_zero("NM_SCORE_PARK");
+    CHECK(p.park == park, "park %d, expected %d (classes %d per-contig %d fits %d)", p.park, park, classes, b.per_contig, park_fits);
     CHECK(p.cls_head == !env_zero("NM_SCORE_HEAD"), "cls_head %d", p.cls_head);
     const char *tail = getenv("NM_SCORE_TAIL");                                      // unset: both kinds of tail descriptor; 0, 1, 2
     CHECK(p.cls_tail == (tail ? tail[0] - '0' : 3), "cls_tail %d", p.cls_tail);
@@ -421,6 +432,17 @@ ScorePlan run_case(const char *name, World &w, const Batch &b) {
     CHECK(p.split_log2 == split && p.split_log2 <= 2 && p.fine_log2 == (f.opt_fine >= 0 ? (uint32_t)f.opt_fine : 2 - split), "split %u fine %u", p.split_log2, p.fine_log2);
     CHECK(p.gy == ((n_active == 2 && cf && lit) ? 1u : std::max(n_active, 1u)) && p.last_wgs == (uint64_t)p.gx * p.gy, "gy %u, workgroups %" PRIu64, p.gy, p.last_wgs);
     CHECK(p.gx % (cf ? 1 : 8) == 0 && p.j_big <= p.pieces_per_run, "gx %u j_big %u pieces_per_run %u", p.gx, p.j_big, p.pieces_per_run);
+    {   // the grid's numbers from what a CU holds at once: 7 workgroups of the parked class kernel, 6 of every other
+        const uint64_t resident = (uint64_t)f.n_cus * (park ? 7 : 6);
+        uint64_t est = (uint64_t)p.n_segments * n_groups / std::max<uint32_t>(own ? n_act_bins : n_bins, 1);
+        if (light && n_active == 2 && lit) est = (est + 1) / 2;
+        const uint32_t want_split = f.opt_split >= 0 ? (uint32_t)f.opt_split : est >= 2 * resident ? 0 : 2 * est >= 2 * resident ? 1 : 2;
+        const uint32_t runs = cf ? 1 : 8, per_run = ((p.n_segments << want_split) + runs - 1) / runs;
+        const uint32_t tail = p.fine_log2 == 0 ? 0 : (uint32_t)std::min<uint64_t>(per_run, (resident / p.gy + runs - 1) / runs);
+        CHECK(p.split_log2 == want_split && p.pieces_per_run == per_run && p.j_big == per_run - tail && p.gx == (per_run - tail + (tail << p.fine_log2)) * runs,
+              "grid split %u per run %u j_big %u gx %u; %" PRIu64 " resident workgroups give %u %u %u %u", p.split_log2, p.pieces_per_run, p.j_big, p.gx, resident,
+              want_split, per_run, per_run - tail, (per_run - tail + (tail << p.fine_log2)) * runs);
+    }
     for (uint32_t block = 0; block < p.gx; ++block) {
         uint32_t first = 0, count = 0;
         if (!decode_block(p, cf, block, segments, &first, &count)) continue;
@@ -470,6 +492,7 @@ void random_case(int i) {
     set_env("NM_SCORE_HEAD", chance(0.15) ? "0" : nullptr);
     { static const char *const tails[3] = {"0", "1", "2"}; set_env("NM_SCORE_TAIL", chance(0.3) ? tails[rnd(0, 2)] : nullptr); }
     set_env("NM_SCORE_PACK_TAILS", chance(0.3) ? "0" : nullptr);
+    set_env("NM_SCORE_PARK", chance(0.25) ? "0" : nullptr);
     w.lists = chance(0.85);
     Batch b;
     const uint32_t n = chance(0.05) ? 0 : chance(0.15) ? rnd(1, 5000) : rnd(1, 300);
@@ -513,7 +536,7 @@ void random_case(int i) {
     run_case(("random " + std::to_string(i)).c_str(), w, b);
 }
 
-void clear_env() { for (const char *e : {"NM_ALL_SEGMENTS", "NM_STAGE_COPIES", "NM_SCORE_CLASSES", "NM_SCORE_HEAD", "NM_SCORE_TAIL", "NM_SCORE_PACK_TAILS"}) unsetenv(e); }
+void clear_env() { for (const char *e : {"NM_ALL_SEGMENTS", "NM_STAGE_COPIES", "NM_SCORE_CLASSES", "NM_SCORE_HEAD", "NM_SCORE_TAIL", "NM_SCORE_PACK_TAILS", "NM_SCORE_PARK"}) unsetenv(e); }
 
 // n candidates dealt round the groups (slot s, bin b), s < n_slots, b < use_bins
 Batch dealt(const World &w, uint32_t n, uint32_t use_bins, uint32_t n_slots, int kind) {
@@ -629,13 +652,114 @@ void directed_cases() {
         }
 }
 
+// ---- the parked class kernel: which batches take it, and what its 7 resident workgroups a CU do to the grid.  `report`: one line
+// per planned batch on stdout, for tests/test_score_park_host.py
+void park_line(bool report, const char *what, uint32_t size, const World &w, const ScorePlan &p) {
+    if (report)
+        printf("park %s size %u parked %d classes %d fits %d n_cus %u n_segments %u n_groups %u split_log2 %u fine_log2 %u pieces_per_run %u j_big %u gx %u gy %u\n", what, size,
+               p.park, p.classes, p.park_fits, w.f.n_cus, p.n_segments, p.n_groups, p.split_log2, p.fine_log2, p.pieces_per_run, p.j_big, p.gx, p.gy);
+}
+
+// `size` candidates with a set in each of `groups` (slot 0, bin) groups, bin < groups
+Batch park_batch(const World &w, uint32_t size, uint32_t groups) {
+    Batch b;
+    for (uint32_t g = 0; g < groups; ++g)
+        for (uint32_t k = 0; k < size; ++k) add_motif(b, w, g, 0, k == 0 ? 1 : (int)rnd(0, 2));
+    // (a set that fell on the modified base stays a literal: one candidate that surely has a set)
+    const uint8_t can = (w.f.slot_is_c & 1u) ? NM_BASE_C : NM_BASE_A;
+    const uint8_t motif[3] = {5, can, 8};
+    b.len[0] = 3; b.mp[0] = 1; b.off[0] = (uint32_t)b.masks.size();
+    b.masks.insert(b.masks.end(), motif, motif + 3);
+    return b;
+}
+
+void park_cases(bool report) {
+    clear_env();
+    // a small assembly: two bins of a few contigs
+    World small = make_world_of({{3 * 8192 + 500, 9000, 700}, {5 * 8192 + 100, 300}}, 16, 2);
+    for (uint32_t size : {1u, 10u, 27u, 28u, 29u, 30u, 32u, 33u, 56u, 57u, 60u, 64u, 65u, 84u, 85u, 96u, 97u}) {
+        const bool fits = (size + 27) / 28 == (size + 31) / 32;
+        // size 1 .. 6 in both groups is a light batch: the group under test sits beside one of 28
+        Batch b = park_batch(small, size, 1);
+        for (uint32_t k = 0; k < 28; ++k) add_motif(b, small, 1, 0, 1);
+        ScorePlan p = run_case("park rule", small, b);
+        CHECK(p.classes && p.park == fits && p.park_fits == fits, "a group of %u: classes %d parked %d", size, p.classes, p.park);
+        park_line(report, "rule", size, small, p);
+        setenv("NM_SCORE_PARK", "0", 1);
+        p = run_case("park rule, NM_SCORE_PARK=0", small, b);
+        CHECK(p.classes && !p.park && p.park_fits == fits, "NM_SCORE_PARK=0 and a group of %u: parked %d", size, p.park);
+        park_line(report, "switch0", size, small, p);
+        setenv("NM_SCORE_PARK", "1", 1);
+        p = run_case("park rule, NM_SCORE_PARK=1", small, b);
+        CHECK(p.park == fits, "NM_SCORE_PARK=1 and a group of %u: parked %d", size, p.park);
+        clear_env();
+        // one group that does not fit unparks the whole batch, wherever it is
+        Batch two = park_batch(small, 28, 1);
+        for (uint32_t k = 0; k < size; ++k) add_motif(two, small, 1, 1, 1);
+        p = run_case("park rule, second slot", small, two);
+        CHECK(p.classes && p.park == fits, "a group of %u in the second slot: parked %d", size, p.park);
+        // per-contig rows: the twin kernel, never parked
+        Batch rows = b;
+        add_rows(rows, small);
+        p = run_case("park rule, per-contig", small, rows);
+        CHECK(p.classes && !p.park, "a per-contig batch is parked");
+        park_line(report, "per_contig", size, small, p);
+        setenv("NM_SCORE_CLASSES", "0", 1);
+        p = run_case("park rule, NM_SCORE_CLASSES=0", small, b);
+        CHECK(!p.classes && !p.park, "NM_SCORE_CLASSES=0 and a parked batch");
+        park_line(report, "classes0", size, small, p);
+        clear_env();
+    }
+    {   // light (six a group), literal-only and wide batches: other kernels
+        ScorePlan p = run_case("park, light", small, dealt(small, 12, 2, 1, 1));
+        CHECK(p.cf && !p.classes && !p.park, "a light batch: cf %d parked %d", p.cf, p.park);
+        park_line(report, "light", 6, small, p);
+        p = run_case("park, literal", small, dealt(small, 40, 2, 1, 0));
+        CHECK(p.lit && !p.park, "a literal batch: lit %d parked %d", p.lit, p.park);
+        park_line(report, "literal", 20, small, p);
+        Batch wide = park_batch(small, 10, 2);
+        add_motif(wide, small, 0, 0, 1, 40);
+        p = run_case("park, wide", small, wide);
+        CHECK(p.any_wide == 1 && !p.classes && !p.park, "a wide batch: parked %d", p.park);
+        park_line(report, "wide", 11, small, p);
+    }
+    // the grid: `bins` bins of one contig of 255 full chunks and a tail (16 or 17 segments each), 256 CUs.  208 bins are more than two
+    // rounds of 6 x 256 workgroups and fewer than two of 7 x 256: the parked batch halves its pieces, the unparked one does not; 120 bins
+    // are fewer than two rounds and 400 more on both sides: the same split, other j_big and gx
+    for (uint32_t bins : {120u, 208u, 400u}) {
+        World big = make_world_of(std::vector<std::vector<uint64_t>>(bins, {(uint64_t)255 * 8192 + 4000}), 16, 1);
+        const Batch b = park_batch(big, 7, bins);
+        const ScorePlan parked = run_case("park grid", big, b);
+        park_line(report, "grid", bins, big, parked);
+        setenv("NM_SCORE_PARK", "0", 1);
+        const ScorePlan plain = run_case("park grid, NM_SCORE_PARK=0", big, b);
+        park_line(report, "grid0", bins, big, plain);
+        clear_env();
+        CHECK(parked.park && !plain.park && parked.n_segments == plain.n_segments, "grid of %u bins: parked %d | %d", bins, parked.park, plain.park);
+        const uint64_t est = parked.n_segments;            // one group a bin, every bin active
+        CHECK((est < 2 * 6 * 256) == (bins == 120) && (est >= 2 * 7 * 256) == (bins == 400), "%u bins are %" PRIu64 " workgroups", bins, est);
+        CHECK(parked.split_log2 == (bins == 400 ? 0u : 1u) && plain.split_log2 == (bins == 120 ? 1u : 0u), "%u bins: split %u | %u", bins, parked.split_log2, plain.split_log2);
+        const uint32_t per_run_parked = ((parked.n_segments << parked.split_log2) + 7) / 8, per_run_plain = ((plain.n_segments << plain.split_log2) + 7) / 8;
+        CHECK(parked.j_big == per_run_parked - 7 * 256 / 8 && plain.j_big == per_run_plain - 6 * 256 / 8, "%u bins: j_big %u | %u", bins, parked.j_big, plain.j_big);
+        CHECK(parked.gx == (parked.j_big + (7u * 256 / 8 << parked.fine_log2)) * 8 && plain.gx == (plain.j_big + (6u * 256 / 8 << plain.fine_log2)) * 8, "%u bins: gx %u | %u", bins,
+              parked.gx, plain.gx);
+    }
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
+    if (argc > 1 && std::string(argv[1]) == "park") {   // the park cases alone, reported line by line
+        rng.seed(20240521ull);
+        park_cases(true);
+        printf("plan_check ok: park cases, %ld batches, %ld checks\n", g_cases, g_checks);
+        return 0;
+    }
     const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 0) : 20240521ull;
     const int n_random = argc > 2 ? atoi(argv[2]) : 3000;
     rng.seed(seed);
     directed_cases();
+    park_cases(false);
     const long directed = g_cases;
     for (int i = 0; i < n_random; ++i) random_case(i);
     clear_env();
