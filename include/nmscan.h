@@ -325,6 +325,14 @@ int nm_stats(nm_ctx *ctx, uint64_t what[8]);
 /* *parked = 1 when the last scoring launch was the class kernel that parks a chunk's state words in LDS (heavy narrow compact
  * batches with IUPAC sets, not per-contig, no group of 29 - 32 or 57 - 64 candidates, NM_SCORE_PARK not 0), else 0. */
 int nm_last_score_parked(nm_ctx *ctx, int *parked);
+/* How the last scoring call was enqueued.  A batch whose counts stay on the device (nm_score_batch_device) may take the short
+ * enqueue; every other call, and every call under NM_SCORE_ENQUEUE=0 (read at every call: same-process A/B), reports 0 — the
+ * hipMemsetAsync of the table and three recorded events as they always were. */
+#define NM_ENQ_BOUND_EVENTS 1u   /* the clear is a dispatch of the library's own, the timing pair is bound to the two dispatches, and when
+                                    launches are collected (nm_timing_reset(1)) the staging pair's release marker is the pair's second event */
+#define NM_ENQ_FUSED_INGEST 2u   /* reserved, never reported: the tables read from pinned memory by the compile dispatch (not built) */
+#define NM_ENQ_STREAM_WAIT 4u    /* reserved, never reported: an idle scoring stream waits for the programs itself (measured, taken out) */
+int nm_last_score_enqueue(nm_ctx *ctx, uint32_t *flags);
 
 /* Per-CONTIG counters: what nm_score_batch sums over a bin, kept apart per contig — motif_model_contig
  * (find_motifs_bin.py:1285-1331) for every contig of the candidate's bin in one launch; the per-contig motif

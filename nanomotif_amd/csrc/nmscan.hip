@@ -396,7 +396,7 @@ int ensure_stage(nm_ctx *c, size_t bytes, int mode) {
     nm_ctx::Stage &st = c->stage[idx];
     if (!st.busy) HIP_TRY(hipEventCreateWithFlags(&st.busy, hipEventDisableTiming));
     if (st.pending) {
-        HIP_TRY(hipEventSynchronize(st.busy));
+        HIP_TRY(hipEventSynchronize(st.marker));
         st.pending = false;
     }
     bytes += 32;                                           // stage_in / stage_out move whole 16-byte words
@@ -418,8 +418,17 @@ int ensure_stage(nm_ctx *c, size_t bytes, int mode) {
 
 int release_stage(nm_ctx *c, hipStream_t s) {   // call after the last device work that reads the acquired pair was enqueued
     HIP_TRY(hipEventRecord(c->cur_stage->busy, s ? s : c->stream));
+    c->cur_stage->marker = c->cur_stage->busy;
     c->cur_stage->pending = true;
     return NM_OK;
+}
+
+// The same for a pair whose last reader is a dispatch that carries `stop` as its stop event: the pair remembers that event and no
+// packet is queued.  Only for an event nothing records again while the pair may be pending: a pool event of nm_timing_reset(1),
+// which stays its launch's own until the next nm_timing_reset — and that drains every such pair (see there).
+void release_stage_bound(nm_ctx *c, hipEvent_t stop) {
+    c->cur_stage->marker = stop;
+    c->cur_stage->pending = true;
 }
 
 constexpr size_t EV_POOL_MAX = 65536;
@@ -470,38 +479,40 @@ struct LaunchShape {
 };
 
 template <class K>
-void launch_variant(const ScoreArgs &a, uint32_t gx, uint32_t gy, hipStream_t s) {
-    hipLaunchKernelGGL((score_kernel<K>), dim3(gx, gy), dim3(256), 0, s, a);
+void launch_variant(const ScoreArgs &a, uint32_t gx, uint32_t gy, hipStream_t s, hipEvent_t stop) {
+    // stop: an event bound to the dispatch (complete when the kernel is, its time the kernel's end) instead of one recorded behind it
+    if (stop) hipExtLaunchKernelGGL((score_kernel<K>), dim3(gx, gy), dim3(256), 0, s, nullptr, stop, 0, a);
+    else hipLaunchKernelGGL((score_kernel<K>), dim3(gx, gy), dim3(256), 0, s, a);
 }
 
 template <int G, bool COMPACT, bool LIT>
-void launch_by_load(const ScoreArgs &a, uint32_t gx, uint32_t gy, const LaunchShape &sh, hipStream_t s) {
-    if (!sh.light) launch_variant<Variant<G, G, COMPACT, 1, LIT, false>>(a, gx, gy, s);
-    else if (sh.fuse && LIT) launch_variant<Variant<G, G, COMPACT, 2, LIT, true>>(a, gx, gy, s);   // (fusing two slots on the 8-plane tile needs 128 VGPRs)
-    else launch_variant<Variant<G, G, COMPACT, 1, LIT, true>>(a, gx, gy, s);
+void launch_by_load(const ScoreArgs &a, uint32_t gx, uint32_t gy, const LaunchShape &sh, hipStream_t s, hipEvent_t stop = nullptr) {
+    if (!sh.light) launch_variant<Variant<G, G, COMPACT, 1, LIT, false>>(a, gx, gy, s, stop);
+    else if (sh.fuse && LIT) launch_variant<Variant<G, G, COMPACT, 2, LIT, true>>(a, gx, gy, s, stop);   // (fusing two slots on the 8-plane tile needs 128 VGPRs)
+    else launch_variant<Variant<G, G, COMPACT, 1, LIT, true>>(a, gx, gy, s, stop);
 }
 
-void launch_score(const ScoreArgs &a, uint32_t gx, uint32_t gy, const LaunchShape &sh, hipStream_t s) {
+void launch_score(const ScoreArgs &a, uint32_t gx, uint32_t gy, const LaunchShape &sh, hipStream_t s, hipEvent_t stop = nullptr) {
     if (sh.per_contig) {      // (candidate, contig) counters: the plain one-slot-per-column kernels with the other reduction key
-        if (sh.wide == 2 && sh.compact) launch_variant<Variant<3, 3, true, 1, false, false, true>>(a, gx, gy, s);
-        else if (sh.wide == 2) launch_variant<Variant<3, 3, false, 1, false, false, true>>(a, gx, gy, s);
-        else if (!sh.wide && sh.compact && sh.classes) launch_score_classes(a, gx, gy, true, false, s);
-        else if (!sh.wide && sh.compact) launch_variant<Variant<1, 1, true, 1, false, false, true>>(a, gx, gy, s);
-        else if (!sh.wide) launch_variant<Variant<1, 1, false, 1, false, false, true>>(a, gx, gy, s);
-        else if (sh.compact) launch_variant<Variant<2, 2, true, 1, false, false, true>>(a, gx, gy, s);
-        else launch_variant<Variant<2, 2, false, 1, false, false, true>>(a, gx, gy, s);
+        if (sh.wide == 2 && sh.compact) launch_variant<Variant<3, 3, true, 1, false, false, true>>(a, gx, gy, s, stop);
+        else if (sh.wide == 2) launch_variant<Variant<3, 3, false, 1, false, false, true>>(a, gx, gy, s, stop);
+        else if (!sh.wide && sh.compact && sh.classes) launch_score_classes(a, gx, gy, true, false, s, stop);
+        else if (!sh.wide && sh.compact) launch_variant<Variant<1, 1, true, 1, false, false, true>>(a, gx, gy, s, stop);
+        else if (!sh.wide) launch_variant<Variant<1, 1, false, 1, false, false, true>>(a, gx, gy, s, stop);
+        else if (sh.compact) launch_variant<Variant<2, 2, true, 1, false, false, true>>(a, gx, gy, s, stop);
+        else launch_variant<Variant<2, 2, false, 1, false, false, true>>(a, gx, gy, s, stop);
         return;
     }
     if (sh.wide == 2) {       // motifs that reach more than 63 positions from the modified base (search frames above 127)
-        if (sh.compact) launch_by_load<3, true, false>(a, gx, gy, sh, s);
-        else launch_by_load<3, false, false>(a, gx, gy, sh, s);
+        if (sh.compact) launch_by_load<3, true, false>(a, gx, gy, sh, s, stop);
+        else launch_by_load<3, false, false>(a, gx, gy, sh, s, stop);
     } else if (!sh.wide && sh.compact) {
-        if (sh.classes) launch_score_classes(a, gx, gy, false, sh.park, s);
-        else if (sh.lit) launch_by_load<1, true, true>(a, gx, gy, sh, s);
-        else launch_by_load<1, true, false>(a, gx, gy, sh, s);
-    } else if (!sh.wide) launch_by_load<1, false, false>(a, gx, gy, sh, s);
-    else if (sh.compact) launch_by_load<2, true, false>(a, gx, gy, sh, s);
-    else launch_by_load<2, false, false>(a, gx, gy, sh, s);
+        if (sh.classes) launch_score_classes(a, gx, gy, false, sh.park, s, stop);
+        else if (sh.lit) launch_by_load<1, true, true>(a, gx, gy, sh, s, stop);
+        else launch_by_load<1, true, false>(a, gx, gy, sh, s, stop);
+    } else if (!sh.wide) launch_by_load<1, false, false>(a, gx, gy, sh, s, stop);
+    else if (sh.compact) launch_by_load<2, true, false>(a, gx, gy, sh, s, stop);
+    else launch_by_load<2, false, false>(a, gx, gy, sh, s, stop);
 }
 
 // What the enqueueing steps of one scoring call share: its plan, where it runs and what it writes.
@@ -515,7 +526,25 @@ struct ScoreRun {
     unsigned long long *out;
     hipEvent_t e0, e1;
     bool timed_launch;
+    uint32_t enq;                       // NM_ENQ_*: the parts of the short enqueue this call takes (score_enqueue_form)
 };
+
+// The clear of a caller's count table as a dispatch of the library's own: the stream, the position and the bytes of the
+// hipMemsetAsync it stands for (the clear stays ordered on the scoring stream against whatever the caller queued on
+// the table), and a dispatch carries the timing pair's first event as its stop event.
+__global__ __launch_bounds__(256) void clear_counts_kernel(unsigned long long *__restrict__ out, uint64_t n_words) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_words; k += stride) out[k] = 0ull;
+}
+
+// Which enqueue a call takes (include/nmscan.h: NM_ENQ_*).  The short one is for a batch whose counts stay on the device and that
+// nobody waits for — d_out given, no host counts, not deferred, no spec source: it prepares on the copy stream and is always timed.
+// allowed: NM_SCORE_ENQUEUE, read at every call (same-process A/B, tests/test_gpu_score_enqueue.py), unset = all; 0 = the enqueue as
+// it was: hipMemsetAsync and three recorded events.
+uint32_t score_enqueue_form(const ScoreRequest &rq, const ScorePlan &p, uint32_t allowed) {
+    if (!rq.d_out || rq.h_out || rq.defer || rq.spec || p.via_stage || p.by_kernels || p.inline_prep) return 0;
+    return allowed & NM_ENQ_BOUND_EVENTS;
+}
 
 // Everything the scoring launch waits for, in the order the measured step time rests on: tables in, the timing pair, the
 // programs (compiled here, or written by the spec source between its own clear and the scoring), the hand-over from the
@@ -590,6 +619,16 @@ int score_prepare(nm_ctx *c, ScoreRun &r, uint32_t c_slots) {       // c_slots: 
 #else
     constexpr int score_probe = 0;                       // (the shipped library has no switch that changes what a call computes)
 #endif
+    if (r.enq & NM_ENQ_BOUND_EVENTS) {
+        // (never a spec or by_kernels batch: score_enqueue_form)  the timing pair's first event is complete when the clear is
+        if (!(score_probe & 1) && p.clear_bytes) {
+            const uint64_t n_words = p.clear_bytes / sizeof(unsigned long long);
+            const uint32_t blocks = (uint32_t)std::min<uint64_t>(1024, (n_words + 255) / 256);
+            hipExtLaunchKernelGGL(clear_counts_kernel, dim3(blocks), dim3(256), 0, r.sst, nullptr, r.e0, 0, r.out, n_words);
+            HIP_TRY(hipGetLastError());
+        } else HIP_TRY(hipEventRecord(r.e0, r.sst));
+        return NM_OK;
+    }
     if (p.compile != PLAN_COMPILE_SPEC && !p.by_kernels && !(score_probe & 1)) HIP_TRY(hipMemsetAsync(r.out, 0, p.clear_bytes, r.sst));
     return NM_OK;
 }
@@ -602,8 +641,15 @@ int score_collect(nm_ctx *c, const ScoreRun &r, nm_ctx::Waiting &wait_slot) {
         const int rc = stage_out(r.sst, r.out, r.hs + p.off_counts, p.clear_bytes);
         if (rc) return rc;
     } else if (p.via_stage) HIP_TRY(hipMemcpyAsync(r.hs + p.off_counts, r.out, p.clear_bytes, hipMemcpyDeviceToHost, r.sst));
-    const int rc = release_stage(c, r.sst);
-    if (rc) return rc;
+    // The pair's release marker.  Launches collected (nm_timing_reset(1)): e1 is this launch's own pool event, bound to the kernel that
+    // reads the pair last — the pair remembers it and nothing is recorded.  Otherwise e1 is the ctx's one ev1, bound again by the next
+    // call (a waiter would wait for the newest launch, not for this one): `busy` is recorded as before.
+    if ((r.enq & NM_ENQ_BOUND_EVENTS) && c->ev_collect) nmdetail::release_stage_bound(c, r.e1);
+    else {
+        const int rc = release_stage(c, r.sst);
+        if (rc) return rc;
+    }
+    c->last_enqueue = r.enq;
     c->cur_stage->last_out = r.rq.d_out;
     c->cur_stage->last_stream = r.sst;
     c->last_score_stream = r.sst;
@@ -692,11 +738,15 @@ int score_impl(nm_ctx *c, const ScoreRequest &rq) {
         // earlier launch in flight wrote d_out from the other lane, this lane waits for it (its staging pair's event)
         for (auto &st : c->stage)
             if (&st != c->cur_stage && st.pending && st.last_out == rq.d_out && st.last_stream && st.last_stream != r.sst)
-                HIP_TRY(hipStreamWaitEvent(r.sst, st.busy, 0));
+                HIP_TRY(hipStreamWaitEvent(r.sst, st.marker, 0));
     }
     // staged tables travel and are compiled on the copy stream; the scoring stream waits for the compiled programs.  A call
     // that returns host counts prepares on the scoring stream itself (plan_shape: inline_prep)
     r.pst = p.inline_prep ? r.sst : c->copy_stream;
+    {
+        const char *enq_env = getenv("NM_SCORE_ENQUEUE");
+        r.enq = score_enqueue_form(rq, p, enq_env ? (uint32_t)atoi(enq_env) : ~0u);
+    }
     // ---- fill
     r.hs = static_cast<uint8_t *>(c->h_stage);
     r.ds = static_cast<uint8_t *>(c->d_stage);
@@ -759,6 +809,14 @@ int score_impl(nm_ctx *c, const ScoreRequest &rq) {
     a.fine_log2 = p.fine_log2;
     a.j_big = p.j_big;
     const LaunchShape shape{p.any_wide, p.all_compact, p.lit, p.cf, p.fuse, p.per_contig, p.classes, p.park};
+    if (r.enq & NM_ENQ_BOUND_EVENTS) {
+        // two dispatches, no packet besides: e0 came with the clear (score_prepare), e1 comes with the scoring kernel — the measured
+        // time is still the end of the clear to the end of the kernel
+        if (p.n_prog) launch_score(a, p.gx, p.gy, shape, r.sst, r.e1);
+        else HIP_TRY(hipEventRecord(r.e1, r.sst));             // (nothing resident for this batch: the zeroed table is the answer)
+        HIP_TRY(hipGetLastError());
+        return score_collect(c, r, wait_slot);
+    }
     if (r.timed_launch && p.compile != PLAN_COMPILE_SPEC) HIP_TRY(hipEventRecord(r.e0, r.sst));
     if (p.n_prog) launch_score(a, p.gx, p.gy, shape, r.sst);   // else nothing resident for this batch: the zeroed table is the answer
     HIP_TRY(hipGetLastError());
@@ -1557,6 +1615,12 @@ int nm_last_score_parked(nm_ctx *c, int *parked) {
     return NM_OK;
 }
 
+int nm_last_score_enqueue(nm_ctx *c, uint32_t *flags) {
+    if (!c || !flags) return fail(NM_EINVAL, "NULL argument");
+    *flags = c->last_enqueue;
+    return NM_OK;
+}
+
 int nm_timing_reset(nm_ctx *c, int enable) {
     if (!c) return fail(NM_EINVAL, "ctx is NULL");
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1564,6 +1628,14 @@ int nm_timing_reset(nm_ctx *c, int enable) {
         const int rcj = join_lanes(c);          // the event pairs are reused: nothing may still be about to record them
         if (rcj) return rcj;
     }
+    // A staging pair may remember a pool event as its release marker (score_collect).  The events are handed out again from here on,
+    // so every such pair is drained here: both scoring streams have just been synchronised, the dispatch the event was bound to has
+    // finished, and the pair is free — a later waiter must not find the event bound to a newer launch.
+    for (auto &st : c->stage)
+        if (st.pending && st.marker != st.busy) {
+            st.pending = false;
+            st.marker = st.busy;
+        }
     c->ev_used = 0;
     c->ev_collect = enable != 0;
     c->ev_collect_all = enable == 2;

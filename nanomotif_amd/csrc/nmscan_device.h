@@ -736,7 +736,8 @@ struct ScoreArgs {
 };
 
 // the CLS variants (Variant<1, 1, true, 1, false, false, PC, true, PARK>): instantiated by nmscore_classes.hip
-void launch_score_classes(const ScoreArgs &a, uint32_t gx, uint32_t gy, bool per_contig, bool park, hipStream_t s);
+// stop: an event bound to the dispatch itself (hipExtLaunchKernelGGL: complete when the kernel is, its time the kernel's end), or NULL
+void launch_score_classes(const ScoreArgs &a, uint32_t gx, uint32_t gy, bool per_contig, bool park, hipStream_t s, hipEvent_t stop = nullptr);
 
 }  // namespace nmdetail
 
@@ -1159,10 +1160,16 @@ __global__ NM_SCORE_BOUNDS void score_kernel(ScoreArgs a) {
 #ifdef NM_SCORE_CLASSES_UNIT
 namespace nmdetail {
 
-void launch_score_classes(const ScoreArgs &a, uint32_t gx, uint32_t gy, bool per_contig, bool park, hipStream_t s) {
-    if (per_contig) hipLaunchKernelGGL((score_kernel<Variant<1, 1, true, 1, false, false, true, true>>), dim3(gx, gy), dim3(256), 0, s, a);
-    else if (park) hipLaunchKernelGGL((score_kernel<Variant<1, 1, true, 1, false, false, false, true, true>>), dim3(gx, gy), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((score_kernel<Variant<1, 1, true, 1, false, false, false, true>>), dim3(gx, gy), dim3(256), 0, s, a);
+template <class K>
+static void launch_classes_variant(const ScoreArgs &a, uint32_t gx, uint32_t gy, hipStream_t s, hipEvent_t stop) {
+    if (stop) hipExtLaunchKernelGGL((score_kernel<K>), dim3(gx, gy), dim3(256), 0, s, nullptr, stop, 0, a);
+    else hipLaunchKernelGGL((score_kernel<K>), dim3(gx, gy), dim3(256), 0, s, a);
+}
+
+void launch_score_classes(const ScoreArgs &a, uint32_t gx, uint32_t gy, bool per_contig, bool park, hipStream_t s, hipEvent_t stop) {
+    if (per_contig) launch_classes_variant<Variant<1, 1, true, 1, false, false, true, true>>(a, gx, gy, s, stop);
+    else if (park) launch_classes_variant<Variant<1, 1, true, 1, false, false, false, true, true>>(a, gx, gy, s, stop);
+    else launch_classes_variant<Variant<1, 1, true, 1, false, false, false, true>>(a, gx, gy, s, stop);
 }
 
 }  // namespace nmdetail

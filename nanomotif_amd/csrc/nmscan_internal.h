@@ -2,6 +2,7 @@
 // plane / context structures and the small host helpers they share.  Not part of the C ABI (include/nmscan.h).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 
 #include <algorithm>
 #include <cstdarg>
@@ -169,6 +170,9 @@ struct nm_ctx {
         void *d = nullptr, *h = nullptr;
         size_t bytes = 0;
         hipEvent_t busy = nullptr;
+        // what a waiter waits on while `pending`: `busy`, recorded behind the last reader (release_stage), or the stop event bound to
+        // the scoring dispatch of a timed device-output batch (a pool event of nm_timing_reset(1): no packet of its own)
+        hipEvent_t marker = nullptr;
         bool pending = false;
         const void *last_out = nullptr;        // count table the last scoring launch of this pair wrote, and its stream
         hipStream_t last_stream = nullptr;
@@ -205,6 +209,7 @@ struct nm_ctx {
     uint64_t other_letters = 0;
     uint64_t launches = 0, last_wgs = 0, last_compact = 0, last_general = 0;
     bool last_parked = false;                         // the last scoring launch was the parked class kernel (nm_last_score_parked)
+    uint32_t last_enqueue = 0;                        // how the last scoring call was enqueued (nm_last_score_enqueue: NM_ENQ_*)
     // multi-GPU exchange (nmcomm.cpp): RCCL communicator, its stream, one completion event per table buffer
     void *comm = nullptr;
     int comm_rank = 0, comm_world = 0;

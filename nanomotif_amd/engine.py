@@ -1629,6 +1629,14 @@ class ScanEngine:
         _lib.check(self.lib.nm_last_score_parked(self.ctx, C.byref(parked)))
         return {**dict(zip(keys, [int(x) for x in w])), "last_parked": int(parked.value)}
 
+    def last_score_enqueue(self) -> int:
+        """How the last scoring call was enqueued (include/nmscan.h: NM_ENQ_*): bit 0 the timing pair bound to the clear and the scoring
+        dispatch, bit 2 the scoring stream (found idle) waits for the programs instead of the host; 0: the enqueue of every call that is
+        not ``score_into_device``, and of every call under NM_SCORE_ENQUEUE=0."""
+        flags = C.c_uint32(0)
+        _lib.check(self.lib.nm_last_score_enqueue(self.ctx, C.byref(flags)))
+        return int(flags.value)
+
     def timing_reset(self, enable=True):
         """True / 1: collect the scoring launches; 2: every device phase of the library (pre-filters, window gathers, window
         batches, background counts); False / 0: stop."""
