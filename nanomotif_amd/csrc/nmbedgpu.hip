@@ -15,7 +15,9 @@
 //   leftovers     rows the kernel will not decide (a mod code other than m / a / 21839, a number outside the fast path)
 //                 are listed and parsed by the host parser's routines (nmbed_parse.h), then patched in.
 // The columns stay in HBM in exactly the types nm_ingest_pileup takes (rows_on_device = 1): no pileup row ever exists
-// as a host array.  nmbed.cpp's parser is the bit-exactness oracle for every row (tests/test_gpu_bed_device.py).
+// as a host array.  nmbed.cpp's parser is the bit-exactness oracle for every row (tests/test_gpu_bed_device.py); since it shares
+// nmbed_parse.h with this file, the text kernels are also pinned to a plain-Python reference at their borders — 64-byte groups, 16 KiB
+// blocks, the 128-byte mask, slabs cut with NM_BED_SLAB_BYTES (tests/bed_text_geometry.py, tests/test_gpu_bed_text_geometry.py).
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -166,16 +168,19 @@ __device__ __forceinline__ bool field_is_null(const uint8_t *p, uint32_t n) {
     return n == 0 || (n == 2 && p[0] == 'N' && p[1] == 'A') || (n == 4 && p[0] == 'n' && p[1] == 'u' && p[2] == 'l' && p[3] == 'l');
 }
 
+// nmbedparse::parse_int's rule: -?[0-9]+, a lone '-' is no integer, the value saturates at +-INT64_MAX and never wraps
 __device__ __forceinline__ bool dev_parse_int(const uint8_t *p, uint32_t n, long long *out) {
     if (n == 0) return false;
     bool neg = false;
     uint32_t i = 0;
     if (p[0] == '-') { neg = true; i = 1; }
+    if (i == n) return false;
+    constexpr long long MAX = 0x7FFFFFFFFFFFFFFFll, LIM = MAX / 10;     // (MAX ends in 7)
     long long v = 0;
     for (; i < n; ++i) {
         const uint32_t d = (uint32_t)p[i] - '0';
         if (d > 9) return false;
-        v = v * 10 + d;
+        v = (v > LIM || (v == LIM && d > 7)) ? MAX : v * 10 + d;
     }
     *out = neg ? -v : v;
     return true;
@@ -333,6 +338,12 @@ __global__ __launch_bounds__(256) void bed_parse_kernel(const uint8_t *__restric
         else if (pos < 0) err = E_START_NEG;
         else if (pos > 0xFFFFFFFEll) err = E_POS_RANGE;
     }
+    // (the host reader's order within a row: columns, start, strand, coverage, percentage, counts)
+    // '+' or '-' and nothing else: the scoring path compares the column with exactly these (find_motifs_bin.py:1308-1314)
+    if (!err) {
+        if (e5 - b5 == 1 && (p[b5] == '+' || p[b5] == '-')) st = p[b5];
+        else err = E_STRAND;
+    }
     if (!err && !field_is_null(p + b9, e9 - b9) && !dev_parse_int(p + b9, e9 - b9, &cov)) err = E_COV;
     if (!err) {
         const uint8_t *q = p + b10;
@@ -371,9 +382,6 @@ __global__ __launch_bounds__(256) void bed_parse_kernel(const uint8_t *__restric
         else if (ml == 1 && m[0] == 'a') mt = 1;
         else if (ml == 5 && m[0] == '2' && m[1] == '1' && m[2] == '8' && m[3] == '3' && m[4] == '9') mt = 2;
         else flags |= 1u;
-        // '+' or '-' and nothing else: the scoring path compares the column with exactly these (find_motifs_bin.py:1308-1314)
-        if (e5 - b5 == 1 && (p[b5] == '+' || p[b5] == '-')) st = p[b5];
-        else err = E_STRAND;
     }
     int32_t nmod = 0, ndiff = 0;
     if constexpr (COUNTS) {
@@ -854,10 +862,13 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
             i = sl.last;
         }
     }
-    // slabs of whole lines (text read or inflated by the host)
+    // slabs of whole lines (text read or inflated by the host).  NM_BED_SLAB_BYTES (tests: slab borders within reach of a small file) lowers
+    // the slab size, never below 64 KiB and never above SLAB_BYTES; the compressed chunks of the device-inflate path keep the constant
+    uint64_t slab_bytes = SLAB_BYTES;
+    if (const char *v = getenv("NM_BED_SLAB_BYTES")) slab_bytes = std::min<uint64_t>(SLAB_BYTES, std::max<uint64_t>(1u << 16, strtoull(v, nullptr, 10)));
     std::vector<uint64_t> cut(1, 0);
     while (!dev_inflate && cut.back() < n) {
-        uint64_t e = std::min<uint64_t>(n, cut.back() + SLAB_BYTES);
+        uint64_t e = std::min<uint64_t>(n, cut.back() + slab_bytes);
         if (e < n) {                                       // back to the end of the last whole line (the tail of the slab is read in pieces)
             const uint64_t lo = cut.back();
             std::vector<uint8_t> win(1u << 16);
@@ -870,7 +881,7 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
                 if (k > w0) { e = k; found = true; }
                 else e = w0;
             }
-            if (!found) return fail_row(fail(NM_EINVAL, "%s: a line longer than %llu bytes", path, (unsigned long long)SLAB_BYTES));
+            if (!found) return fail_row(fail(NM_EINVAL, "%s: a line longer than %llu bytes", path, (unsigned long long)slab_bytes));
         }
         cut.push_back(e);
     }
@@ -903,7 +914,7 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
             if (cs && own) (void)hipStreamDestroy(cs);
         }
     } cleanup{h_ring, d_slab, dev_tmp, copy_stream, own_copy_stream, h2d_done, parsed, c};
-    const uint64_t slab_cap = dev_inflate ? inf_text_cap + CARRY_CAP + 64 : std::min<uint64_t>(SLAB_BYTES, std::max<uint64_t>(n, 1));
+    const uint64_t slab_cap = dev_inflate ? inf_text_cap + CARRY_CAP + 64 : std::min<uint64_t>(slab_bytes, std::max<uint64_t>(n, 1));
     const uint32_t max_blocks = (uint32_t)((slab_cap + BLOCK_BYTES - 1) / BLOCK_BYTES);
     const uint64_t max_lines = slab_cap / 2 + 1;                          // a non-empty line and its '\n'
     if (n_slabs) {
@@ -990,6 +1001,7 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
     } join{producers, mu, cv, stop};
 
     bool first_rows = true;                 // the next slab with rows holds row 0
+    uint32_t most_lines = 0;                // the largest line count of a slab (NM_BED_TIMING)
     size_t n_parsed = 0;                    // slabs with rows so far (ping-pong of the "hash of the row before")
     // the whole lines of text[0, len) (16-byte aligned, device memory) -> rows; text_base: the text offset of its first byte;
     // grow_hint: file size / slab size when this is the first of several slabs (sizes the columns once); counted(): called
@@ -1046,6 +1058,7 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
             n_parsed += 1;
         }
         b->n_rows += n_lines;
+        most_lines = std::max(most_lines, n_lines);
         return NM_OK;
     };
     // ---- bgzip, inflated on the device: per slab the compressed bytes of its blocks (packed, through the pinned ring) ->
@@ -1419,10 +1432,6 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
     unsigned long long first_error = ~0ull;
     HIP_TRY(hipMemcpyAsync(&first_error, d_first_error, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (first_error != ~0ull && (first_error & 0xFF) == E_DECLINE)
-        return fail(NM_EDECLINED, "%s: a count column (12 N_mod / 17 N_diff) the host reader decides (more than 18 digits, or beside a "
-                    "percentage left to the host): use nm_bed_open_counts", path);
-    if (first_error != ~0ull) return fail_row(fail(NM_EINVAL, "%s: %s", path, row_error_text((uint32_t)(first_error & 0xFF))));
     std::vector<char> line_buf(1u << 16);
     // k-th tab-separated field of the line at text offset `line` (buf: scratch of the calling thread).  A short window first:
     // in a bgzip file every window costs the inflation of the block(s) under it
@@ -1430,7 +1439,8 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
         if (buf.size() < (1u << 16)) buf.resize(1u << 16);
         uint64_t got = std::min<uint64_t>(1024, n - line);
         if (!read_at(line, buf.data(), got)) { *fb = *fe = buf.data(); return; }
-        if (!memchr(buf.data(), '\n', (size_t)got) && got < n - line) {
+        while (!memchr(buf.data(), '\n', (size_t)got) && got < n - line) {
+            if (got >= buf.size()) buf.resize(buf.size() * 2);           // (a line longer than the buffer — a contig name of 70 000 bytes — : twice the room)
             got = std::min<uint64_t>(buf.size(), n - line);
             if (!read_at(line, buf.data(), got)) { *fb = *fe = buf.data(); return; }
         }
@@ -1447,8 +1457,56 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
         *fe = t ? t : le;
     };
     auto field = [&](uint64_t line, int k, const char **fb, const char **fe) { field_in(line_buf, line, k, fb, fe); };
+    // The rows the kernel left to the host's routines (np of them), fetched and sorted by row, and judged IN FILE ORDER up to (not including)
+    // row `limit` by the host reader's rules, in its order within a row (percentage, then the code): one judge for the patch values and for
+    // the refusal order.  mods / fracs: what to patch into the columns.  More rows than the list holds: the host reader decides the file
+    auto judge_host_rows = [&](unsigned int np, unsigned long long limit, std::vector<uint4> &patch, std::vector<int8_t> &mods, std::vector<double> &fracs) -> int {
+        if (np > PATCH_CAP) return fail(NM_EDECLINED, "%s: more than %u rows need the host parser (unusual mod codes / number formats): use nm_bed_open", path, PATCH_CAP);
+        patch.resize(np);
+        mods.assign(np, 0);
+        fracs.assign(np, 0.0);
+        if (np) HIP_TRY(hipMemcpy(patch.data(), d_patch, (size_t)np * sizeof(uint4), hipMemcpyDeviceToHost));
+        std::sort(patch.begin(), patch.end(), [](const uint4 &x, const uint4 &y) { return x.x < y.x; });
+        for (unsigned int i = 0; i < np && patch[i].x < limit; ++i) {
+            const uint64_t off = ((uint64_t)patch[i].w << 32) | patch[i].z;
+            const char *fb, *fe;
+            if (patch[i].y & 2u) {
+                field(off, 10, &fb, &fe);
+                double pct = 0;
+                if (!nmbedparse::parse_double(fb, fe, &pct)) return fail_row(fail(NM_EINVAL, "%s: pileup column 11 (percent modified) is not a number", path));
+                fracs[i] = pct / 100.0;
+            }
+            if (patch[i].y & 1u) {
+                field(off, 3, &fb, &fe);
+                const std::string code(fb, fe);
+                size_t k = 0;
+                for (; k < b->other_mods.size(); ++k)
+                    if (b->other_mods[k] == code) break;
+                if (k == b->other_mods.size()) b->other_mods.push_back(code);
+                if (k > 100) return fail_row(fail(NM_EINVAL, "%s: more than 100 distinct modification codes in column 4", path));
+                mods[i] = (int8_t)(3 + k);
+            }
+        }
+        return NM_OK;
+    };
+    if (first_error != ~0ull) {
+        // The refusal is that of the FIRST bad row in file order, whichever side finds it (the host reader stops at its first bad row): the
+        // rows left to the host's routines that lie before the kernel's row are judged first
+        unsigned int np = 0;
+        HIP_TRY(hipMemcpy(&np, d_counters, 4, hipMemcpyDeviceToHost));
+        std::vector<uint4> patch;
+        std::vector<int8_t> mods;
+        std::vector<double> fracs;
+        const int rc = judge_host_rows(np, first_error >> 8, patch, mods, fracs);
+        if (rc) return rc;
+        if ((first_error & 0xFF) == E_DECLINE)
+            return fail(NM_EDECLINED, "%s: a count column (12 N_mod / 17 N_diff) the host reader decides (more than 18 digits, or beside a "
+                        "percentage left to the host): use nm_bed_open_counts", path);
+        return fail_row(fail(NM_EINVAL, "%s: %s", path, row_error_text((uint32_t)(first_error & 0xFF))));
+    }
     // ---- runs of equal contig names -> names, ids, the contig column
     const double t_after_slabs = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    unsigned int runs_seen = 0, rows_for_host = 0;            // (NM_BED_TIMING)
     if (b->n_rows) {
         unsigned int n_runs = 0;
         HIP_TRY(hipMemcpyAsync(&n_runs, d_counters + 1, 4, hipMemcpyDeviceToHost, c->stream));
@@ -1537,36 +1595,17 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
             fprintf(stderr, "[bed] after the last slab: %u runs and their names %.3f s, the two contig columns allocated %.3f s, filled (kernel + wait) %.3f s, %u rows for the host's routines\n",
                     n_runs, tt1 - tt0, tt2 - tt1, tt3 - tt2, np);
         }
-        if (np > PATCH_CAP) return fail(NM_EDECLINED, "%s: more than %u rows need the host parser (unusual mod codes / number formats): use nm_bed_open", path, PATCH_CAP);
+        runs_seen = n_runs;
+        rows_for_host = np;
+        std::vector<uint4> patch;
+        std::vector<int8_t> pmod;
+        std::vector<double> pfrac;
+        rc = judge_host_rows(np, ~0ull, patch, pmod, pfrac);
+        if (rc) return rc;
         if (np) {
-            std::vector<uint4> patch(np);
-            HIP_TRY(hipMemcpy(patch.data(), d_patch, (size_t)np * sizeof(uint4), hipMemcpyDeviceToHost));
-            std::sort(patch.begin(), patch.end(), [](const uint4 &x, const uint4 &y) { return x.x < y.x; });
-            std::vector<unsigned long long> prow(np), poff(np);
-            for (unsigned int i = 0; i < np; ++i) { prow[i] = patch[i].x; poff[i] = ((unsigned long long)patch[i].w << 32) | patch[i].z; }
-            std::vector<int8_t> pmod(np, 0);
-            std::vector<double> pfrac(np, 0.0);
+            std::vector<unsigned long long> prow(np);
             std::vector<uint8_t> pwhat(np, 0);
-            for (unsigned int i = 0; i < np; ++i) {
-                pwhat[i] = (uint8_t)patch[i].y;
-                const char *fb, *fe;
-                if (patch[i].y & 1u) {
-                    field(poff[i], 3, &fb, &fe);
-                    const std::string code(fb, fe);
-                    size_t k = 0;
-                    for (; k < b->other_mods.size(); ++k)
-                        if (b->other_mods[k] == code) break;
-                    if (k == b->other_mods.size()) b->other_mods.push_back(code);
-                    if (k > 100) return fail_row(fail(NM_EINVAL, "%s: more than 100 distinct modification codes in column 4", path));
-                    pmod[i] = (int8_t)(3 + k);
-                }
-                if (patch[i].y & 2u) {
-                    field(poff[i], 10, &fb, &fe);
-                    double pct = 0;
-                    if (!nmbedparse::parse_double(fb, fe, &pct)) return fail_row(fail(NM_EINVAL, "%s: pileup column 11 (percent modified) is not a number", path));
-                    pfrac[i] = pct / 100.0;
-                }
-            }
+            for (unsigned int i = 0; i < np; ++i) { prow[i] = patch[i].x; pwhat[i] = (uint8_t)patch[i].y; }
             unsigned long long *d_prow = nullptr;
             int8_t *d_pmod = nullptr;
             double *d_pfrac = nullptr;
@@ -1587,6 +1626,10 @@ int parse_device_impl(nm_ctx *c, const char *path, TextSource &src, uint32_t thr
     for (auto &s_ : b->names) b->name_ptrs.push_back(s_.c_str());
     b->t_read = t_read;
     b->t_total = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t_begin;
+    // (what the tests of the slab borders assert, so that a cell cannot pass on a path it did not take)
+    if (alloc_timing && !dev_inflate)
+        fprintf(stderr, "[bed] text slabs: %zu slabs of at most %llu bytes (%zu with rows), at most %u lines in a slab, %u runs, %u rows for the host's routines\n",
+                n_slabs, (unsigned long long)slab_bytes, n_parsed, most_lines, runs_seen, rows_for_host);
     if (alloc_timing) fprintf(stderr, "[bed] %.3f s in the parser; the runs, names and patched rows after the last slab took %.3f s\n", b->t_total, b->t_total - (t_after_slabs - t_begin));
     guard.keep = true;
     *out = b;

@@ -175,7 +175,7 @@ def write_bgzf_tabix(bed_text: bytes, gz_path: str, block_size: int = 0xFF00, le
     refs, order = {}, []
     pos = 0
     for line in bed_text.split(b"\n"):
-        if line:
+        if line.rstrip(b"\r"):                              # ("\r\n" alone is an empty line to both readers)
             f = line.split(b"\t")
             name, beg, end = f[0], int(f[1]), int(f[2])
             r = refs.get(name)
