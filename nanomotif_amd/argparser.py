@@ -67,21 +67,41 @@ def create_parser():
     return parser
 
 
-def _states(text):
-    from .engine import SITE_STATES
-    asked = [s.strip() for s in text.split(",") if s.strip()]
-    if not asked or any(s not in SITE_STATES for s in asked):
-        raise argparse.ArgumentTypeError(f"a comma-separated selection of {', '.join(SITE_STATES)} is expected, got {text!r}")
-    return tuple(s for s in SITE_STATES if s in asked)
+# ------------------------------------------------------------------------------------------------ what the export commands share
+def _selection(constant):
+    """An argparse ``type``: a comma-separated selection of the names in ``engine.<constant>``, returned in that tuple's order.  The
+    engine is imported when the first value is parsed, not when the parser is made."""
+    def parse(text):
+        from . import engine
+        names = getattr(engine, constant)
+        asked = [s.strip() for s in text.split(",") if s.strip()]
+        if not asked or any(s not in names for s in asked):
+            raise argparse.ArgumentTypeError(f"a comma-separated selection of {', '.join(names)} is expected, got {text!r}")
+        return tuple(s for s in names if s in asked)
+    return parse
 
 
-def add_motif_sites_parser(sub):
-    """motif_sites: the per-site view of a bin-motifs.tsv (no counterpart on the reference's command line; the data are what
-    motif_model_contig(save_motif_positions=True) returns, find_motifs_bin.py:1285-1331).  Assembly, pileup, bins, thresholds and
-    device are spelled as for motif_discovery: the pileup is ingested the same way."""
-    p = sub.add_parser("motif_sites", help="Exports where the motifs of a bin-motifs.tsv occur and which occurrences are methylated", add_help=False)
+def _checked(module, function, keep_text=False):
+    """An argparse ``type`` from ``nanomotif_amd.<module>.<function>``: its ValueError becomes the parser's error.  The module is
+    imported when the first value is parsed, not when the parser is made.  ``keep_text``: check only, the option keeps the text."""
+    def parse(text):
+        from importlib import import_module
+        try:
+            value = getattr(import_module("." + module, __package__), function)(text)
+        except ValueError as e:
+            raise argparse.ArgumentTypeError(str(e)) from None
+        return text if keep_text else value
+    return parse
+
+
+def _open_export(sub, name, help, bin_motifs=None, many=True, pileups=(("pileup", "path to the modkit pileup file."),)):
+    """Opens the subparser of an export command: assembly, pileup(s) and bins spelled as for motif_discovery (the pileup is ingested the
+    same way), then "Options" with ``--bin_motifs`` (``bin_motifs``: its help; ``many``: several paths or one; None: the command places
+    the option itself) and ``--out``.  Returns (parser, its "Options" group): the command adds its own options, then ``_close_export``."""
+    p = sub.add_parser(name, help=help, add_help=False)
     p.add_argument("assembly", type=str, help="path to the assembly file.")
-    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
+    for dest, text in pileups:
+        p.add_argument(dest, type=str, help=text)
     gm = p.add_argument_group("contig bin arguments, use one of:")
     g = gm.add_mutually_exclusive_group(required=True)
     g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
@@ -90,101 +110,76 @@ def add_motif_sites_parser(sub):
     gm.add_argument("--extension", type=str, default=".fasta",
                     help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
     o = p.add_argument_group("Options")
-    o.add_argument("--bin_motifs", type=str, required=True, help="Path to the bin-motifs.tsv whose motifs are exported (motif_discovery's output)")
+    if bin_motifs is not None:
+        o.add_argument("--bin_motifs", type=str, required=True, help=bin_motifs, **({"nargs": "+"} if many else {}))
     o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
-    o.add_argument("--states", type=_states, default=("mod", "nomod", "nocall"),
-                   help="Comma-separated states of the occurrences to export: mod, nomod, nocall. Default: all three")
-    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
-                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
-    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
-                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
-    o.add_argument("--threshold_valid_coverage", type=int, default=5,
-                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
+    return p, o
+
+
+def _close_export(p, o, filters="calls", more=()):
+    """Closes the subparser of an export command: the filter block — "calls": the three call thresholds; "reads": the two read filters of
+    the commands that read the pileup as READ STATISTICS; "reads and zones": those and the two thresholds as histogram zones — then
+    ``more`` ((flag, keywords) of options the command keeps behind the block), ``--device`` and the general arguments."""
+    if filters != "calls":
+        o.add_argument("--min_valid_read_coverage", type=int, default=5,
+                       help="Minimum valid base coverage (Nvalid_cov) for a pileup record to be read. Default: %(default)s")
+        o.add_argument("--min_valid_cov_to_diff_fraction", type=float, default=0.8,
+                       help="Minimum Nvalid_cov / (Nvalid_cov + Ndiff) for a pileup record to be read. Default: %(default)s")
+    if filters != "reads":
+        low, high = (("Upper edge of the unmethylated zone, snapped to a bin edge.", "Lower edge of the methylated zone, snapped to a bin edge.")
+                     if filters == "reads and zones" else
+                     ("A position is considered non-methylated if fraction of methylation is below this threshold.",
+                      "A position is considered methylated if fraction of methylated reads is above this threshold."))
+        o.add_argument("--methylation_threshold_low", type=float, default=0.30, help=low + " Default: %(default)s")
+        o.add_argument("--methylation_threshold_high", type=float, default=0.70, help=high + " Default: %(default)s")
+    if filters == "calls":
+        o.add_argument("--threshold_valid_coverage", type=int, default=5,
+                       help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
+    for flag, keywords in more:
+        o.add_argument(flag, **keywords)
     o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
     gen = p.add_argument_group("general arguments")
     gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
     gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
     gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
     gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
+
+
+# ------------------------------------------------------------------------------------------------ the commands: what is their own
+def add_motif_sites_parser(sub):
+    """motif_sites: the per-site view of a bin-motifs.tsv (no counterpart on the reference's command line; the data are what
+    motif_model_contig(save_motif_positions=True) returns, find_motifs_bin.py:1285-1331)."""
+    p, o = _open_export(sub, "motif_sites", "Exports where the motifs of a bin-motifs.tsv occur and which occurrences are methylated",
+                        "Path to the bin-motifs.tsv whose motifs are exported (motif_discovery's output)", many=False)
+    o.add_argument("--states", type=_selection("SITE_STATES"), default=("mod", "nomod", "nocall"),
+                   help="Comma-separated states of the occurrences to export: mod, nomod, nocall. Default: all three")
+    _close_export(p, o)
 
 
 def add_motif_coverage_parser(sub):
     """motif_coverage: how much of a bin's methylation the motifs of a bin-motifs.tsv explain (the reference only logs "% of sequences
-    remaining" inside find_best_candidates, find_motifs_bin.py:801-823).  Arguments are those of motif_sites: same ingest."""
-    p = sub.add_parser("motif_coverage", help="Reports how much of each bin's methylation the motifs of a bin-motifs.tsv explain", add_help=False)
-    p.add_argument("assembly", type=str, help="path to the assembly file.")
-    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
-    gm = p.add_argument_group("contig bin arguments, use one of:")
-    g = gm.add_mutually_exclusive_group(required=True)
-    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
-    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
-    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
-    gm.add_argument("--extension", type=str, default=".fasta",
-                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
-    o = p.add_argument_group("Options")
-    o.add_argument("--bin_motifs", type=str, required=True, help="Path to the bin-motifs.tsv whose motifs are assessed (motif_discovery's output)")
-    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
+    remaining" inside find_best_candidates, find_motifs_bin.py:801-823)."""
+    p, o = _open_export(sub, "motif_coverage", "Reports how much of each bin's methylation the motifs of a bin-motifs.tsv explain",
+                        "Path to the bin-motifs.tsv whose motifs are assessed (motif_discovery's output)", many=False)
     o.add_argument("--unexplained_sites", action="store_true",
                    help="Also write unexplained-sites.bed: the methylated positions no motif of their bin covers")
-    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
-                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
-    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
-                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
-    o.add_argument("--threshold_valid_coverage", type=int, default=5,
-                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
-    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
-    gen = p.add_argument_group("general arguments")
-    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
-    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
-    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
-    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
-
-
-def _transitions(text):
-    from .engine import TRANSITIONS
-    asked = [t.strip() for t in text.split(",") if t.strip()]
-    if not asked or any(t not in TRANSITIONS for t in asked):
-        raise argparse.ArgumentTypeError(f"a comma-separated selection of {', '.join(TRANSITIONS)} is expected, got {text!r}")
-    return tuple(t for t in TRANSITIONS if t in asked)
+    _close_export(p, o)
 
 
 def add_motif_compare_parser(sub):
     """motif_compare: per-motif methylation change between two pileups of one assembly (no counterpart on the reference's command line;
-    nearest: two runs of motif_model_contig(save_motif_positions=True), find_motifs_bin.py:1285-1331, joined by hand).  Arguments are
-    those of motif_sites with two pileups and one or more bin-motifs.tsv: both pileups are ingested as motif_discovery ingests its one."""
-    p = sub.add_parser("motif_compare", help="Compares the methylation of the motifs of bin-motifs.tsv files between two pileups of one assembly",
-                       add_help=False)
-    p.add_argument("assembly", type=str, help="path to the assembly file.")
-    p.add_argument("pileup_a", type=str, help="path to the modkit pileup file of sample A.")
-    p.add_argument("pileup_b", type=str, help="path to the modkit pileup file of sample B (same assembly).")
-    gm = p.add_argument_group("contig bin arguments, use one of:")
-    g = gm.add_mutually_exclusive_group(required=True)
-    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
-    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
-    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
-    gm.add_argument("--extension", type=str, default=".fasta",
-                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
-    o = p.add_argument_group("Options")
-    o.add_argument("--bin_motifs", type=str, nargs="+", required=True,
-                   help="Path(s) to the bin-motifs.tsv whose motifs are compared (typically motif_discovery's output on sample A and on sample B)")
-    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
+    nearest: two runs of motif_model_contig(save_motif_positions=True), find_motifs_bin.py:1285-1331, joined by hand).  Both pileups are
+    ingested as motif_discovery ingests its one."""
+    p, o = _open_export(sub, "motif_compare", "Compares the methylation of the motifs of bin-motifs.tsv files between two pileups of one assembly",
+                        "Path(s) to the bin-motifs.tsv whose motifs are compared (typically motif_discovery's output on sample A and on sample B)",
+                        pileups=(("pileup_a", "path to the modkit pileup file of sample A."),
+                                 ("pileup_b", "path to the modkit pileup file of sample B (same assembly).")))
     o.add_argument("--switched_sites", action="store_true",
                    help="Also write switched-sites.bed: the occurrences whose state changed between the samples (see --transitions)")
-    o.add_argument("--transitions", type=_transitions, default=("mod>nomod", "nomod>mod"),
+    o.add_argument("--transitions", type=_selection("TRANSITIONS"), default=("mod>nomod", "nomod>mod"),
                    help="Comma-separated transitions A>B written to switched-sites.bed, each of mod, nomod, nocall on either side. "
                         "Default: mod>nomod,nomod>mod")
-    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
-                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
-    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
-                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
-    o.add_argument("--threshold_valid_coverage", type=int, default=5,
-                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
-    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
-    gen = p.add_argument_group("general arguments")
-    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
-    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
-    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
-    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
+    _close_export(p, o)
 
 
 def add_binnary_parsers(sub):
@@ -224,264 +219,85 @@ def add_binnary_parsers(sub):
                        help="Indicate that the detect_contamination workflow should be run first")
 
 
-def _pairs(text):
-    from .engine import PAIRS
-    asked = [t.strip() for t in text.split(",") if t.strip()]
-    if not asked or any(t not in PAIRS for t in asked):
-        raise argparse.ArgumentTypeError(f"a comma-separated selection of {', '.join(PAIRS)} is expected, got {text!r}")
-    return tuple(t for t in PAIRS if t in asked)
-
-
 def add_motif_strands_parser(sub):
     """motif_strands: the state of both strands of every motif site — full, hemi, unmethylated (no counterpart on the reference's command
-    line, which pairs a motif with its complement by name only; modkit has pileup-hemi for CpG).  Arguments are those of motif_sites with
-    one or more bin-motifs.tsv: same ingest."""
-    p = sub.add_parser("motif_strands", help="Reports whether both strands of the motif sites of bin-motifs.tsv files are methylated", add_help=False)
-    p.add_argument("assembly", type=str, help="path to the assembly file.")
-    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
-    gm = p.add_argument_group("contig bin arguments, use one of:")
-    g = gm.add_mutually_exclusive_group(required=True)
-    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
-    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
-    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
-    gm.add_argument("--extension", type=str, default=".fasta",
-                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
-    o = p.add_argument_group("Options")
-    o.add_argument("--bin_motifs", type=str, nargs="+", required=True, help="Path(s) to the bin-motifs.tsv whose motif sites are assessed (motif_discovery's output)")
-    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
+    line, which pairs a motif with its complement by name only; modkit has pileup-hemi for CpG)."""
+    p, o = _open_export(sub, "motif_strands", "Reports whether both strands of the motif sites of bin-motifs.tsv files are methylated",
+                        "Path(s) to the bin-motifs.tsv whose motif sites are assessed (motif_discovery's output)")
     o.add_argument("--hemi_sites", action="store_true",
                    help="Also write hemi-sites.bed: the occurrences whose own base and partner base differ in state (see --pairs)")
-    o.add_argument("--pairs", type=_pairs, default=("mod-nomod", "nomod-mod"),
+    o.add_argument("--pairs", type=_selection("PAIRS"), default=("mod-nomod", "nomod-mod"),
                    help="Comma-separated pairs own-partner written to hemi-sites.bed, each of mod, nomod, nocall on either side. "
                         "Default: mod-nomod,nomod-mod")
-    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
-                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
-    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
-                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
-    o.add_argument("--threshold_valid_coverage", type=int, default=5,
-                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
-    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
-    gen = p.add_argument_group("general arguments")
-    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
-    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
-    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
-    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
-
-
-def _targets(text):
-    from .motif_profile import parse_targets
-    try:
-        return parse_targets(text)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e)) from None
-
-
-def _radius(text):
-    from .motif_profile import parse_radius
-    try:
-        return parse_radius(text)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e)) from None
+    _close_export(p, o)
 
 
 def add_motif_profile_parser(sub):
     """motif_profile: the methylation of every position around the sites of the motifs of bin-motifs.tsv files, both strands, every mod
-    type of the pileup (no counterpart on the reference's command line).  Arguments are those of motif_sites with one or more
-    bin-motifs.tsv: same ingest."""
-    p = sub.add_parser("motif_profile", help="Reports the methylation at every offset around the motif sites of bin-motifs.tsv files", add_help=False)
-    p.add_argument("assembly", type=str, help="path to the assembly file.")
-    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
-    gm = p.add_argument_group("contig bin arguments, use one of:")
-    g = gm.add_mutually_exclusive_group(required=True)
-    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
-    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
-    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
-    gm.add_argument("--extension", type=str, default=".fasta",
-                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
-    o = p.add_argument_group("Options")
-    o.add_argument("--bin_motifs", type=str, nargs="+", required=True, help="Path(s) to the bin-motifs.tsv whose motif sites are profiled (motif_discovery's output)")
-    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
-    o.add_argument("--radius", type=_radius, default=10, help="Offsets either side of the modified base that are profiled, 0..31. Default: %(default)s")
-    o.add_argument("--targets", type=_targets, default=None,
+    type of the pileup (no counterpart on the reference's command line)."""
+    p, o = _open_export(sub, "motif_profile", "Reports the methylation at every offset around the motif sites of bin-motifs.tsv files",
+                        "Path(s) to the bin-motifs.tsv whose motif sites are profiled (motif_discovery's output)")
+    o.add_argument("--radius", type=_checked("motif_profile", "parse_radius"), default=10,
+                   help="Offsets either side of the modified base that are profiled, 0..31. Default: %(default)s")
+    o.add_argument("--targets", type=_checked("motif_profile", "parse_targets"), default=None,
                    help="Comma-separated mod types whose calls are read at every offset: a, m, 21839. Default: every mod type the pileup holds rows of")
     o.add_argument("--min_called", type=int, default=20,
                    help="Called sites a cell needs to be considered for the summary's best cell. Default: %(default)s")
-    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
-                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
-    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
-                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
-    o.add_argument("--threshold_valid_coverage", type=int, default=5,
-                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
-    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
-    gen = p.add_argument_group("general arguments")
-    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
-    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
-    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
-    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
-
-
-def _window(text):
-    from .motif_tracks import parse_window
-    try:
-        return parse_window(text)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e)) from None
+    _close_export(p, o)
 
 
 def add_motif_context_parser(sub):
     """motif_context: the letter at every offset around the sites of the motifs of bin-motifs.tsv files, counted apart by the state of the
-    site: which position and letters separate the methylated sites from the rest (no counterpart on the reference's command line).
-    Arguments are those of motif_profile: same ingest."""
-    p = sub.add_parser("motif_context", help="Reports the sequence context of the motif sites of bin-motifs.tsv files by methylation state", add_help=False)
-    p.add_argument("assembly", type=str, help="path to the assembly file.")
-    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
-    gm = p.add_argument_group("contig bin arguments, use one of:")
-    g = gm.add_mutually_exclusive_group(required=True)
-    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
-    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
-    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
-    gm.add_argument("--extension", type=str, default=".fasta",
-                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
-    o = p.add_argument_group("Options")
-    o.add_argument("--bin_motifs", type=str, nargs="+", required=True, help="Path(s) to the bin-motifs.tsv whose motif sites are read (motif_discovery's output)")
-    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
-    o.add_argument("--radius", type=_radius, default=10, help="Offsets either side of the modified base whose letters are counted, 0..31. Default: %(default)s")
+    site: which position and letters separate the methylated sites from the rest (no counterpart on the reference's command line)."""
+    p, o = _open_export(sub, "motif_context", "Reports the sequence context of the motif sites of bin-motifs.tsv files by methylation state",
+                        "Path(s) to the bin-motifs.tsv whose motif sites are read (motif_discovery's output)")
+    o.add_argument("--radius", type=_checked("motif_context", "parse_radius"), default=10,
+                   help="Offsets either side of the modified base whose letters are counted, 0..31. Default: %(default)s")
     o.add_argument("--min_called", type=int, default=20,
                    help="Called sites a motif needs to be judged, and the dropped letters need for the underspecified flag. Default: %(default)s")
     o.add_argument("--min_gain", type=float, default=30.0,
                    help="Log-likelihood gain of the best offset's split by letter from which a motif is flagged underspecified. Default: %(default)s")
-    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
-                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
-    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
-                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
-    o.add_argument("--threshold_valid_coverage", type=int, default=5,
-                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
-    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
-    gen = p.add_argument_group("general arguments")
-    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
-    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
-    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
-    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
-
-
-def _half(text):
-    from .motif_gc import parse_half
-    try:
-        return parse_half(text)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e)) from None
-
-
-def _gc_bins(text):
-    from .motif_gc import parse_gc_bins
-    try:
-        return parse_gc_bins(text)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e)) from None
+    _close_export(p, o)
 
 
 def add_motif_gc_parser(sub):
     """motif_gc: the methylation of the motifs of bin-motifs.tsv files stratified by the GC content around their sites, beside the bin's
     background: is a motif methylated everywhere, or where the local GC is high (no counterpart on the reference's command line; its
-    known-issues page advises to check high-GC 5mC noise by hand).  Arguments are those of motif_context: same ingest."""
-    p = sub.add_parser("motif_gc", help="Reports the methylation of the motifs of bin-motifs.tsv files by the GC content around their sites", add_help=False)
-    p.add_argument("assembly", type=str, help="path to the assembly file.")
-    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
-    gm = p.add_argument_group("contig bin arguments, use one of:")
-    g = gm.add_mutually_exclusive_group(required=True)
-    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
-    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
-    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
-    gm.add_argument("--extension", type=str, default=".fasta",
-                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
-    o = p.add_argument_group("Options")
-    o.add_argument("--bin_motifs", type=str, nargs="+", required=True, help="Path(s) to the bin-motifs.tsv whose motif sites are read (motif_discovery's output)")
-    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
-    o.add_argument("--half", type=_half, default=31,
+    known-issues page advises to check high-GC 5mC noise by hand)."""
+    p, o = _open_export(sub, "motif_gc", "Reports the methylation of the motifs of bin-motifs.tsv files by the GC content around their sites",
+                        "Path(s) to the bin-motifs.tsv whose motif sites are read (motif_discovery's output)")
+    o.add_argument("--half", type=_checked("motif_gc", "parse_half"), default=31,
                    help="Positions either side of the modified base in the GC window, 0..31 (the window is 2 HALF + 1 positions). Default: %(default)s")
-    o.add_argument("--gc_bins", type=_gc_bins, default=8, help="Buckets of local GC the sites are written in (at most one per count of G + C). Default: %(default)s")
+    o.add_argument("--gc_bins", type=_checked("motif_gc", "parse_gc_bins"), default=8,
+                   help="Buckets of local GC the sites are written in (at most one per count of G + C). Default: %(default)s")
     o.add_argument("--min_called", type=int, default=20, help="Called sites a motif needs to be judged. Default: %(default)s")
     o.add_argument("--min_z", type=float, default=5.0,
                    help="|trend_z_within| from which a motif can be flagged gc_dependent. Default: %(default)s")
     o.add_argument("--min_delta", type=float, default=0.2,
                    help="|frac_mod of the high-GC third - frac_mod of the low-GC third| from which a motif can be flagged gc_dependent. Default: %(default)s")
-    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
-                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
-    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
-                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
-    o.add_argument("--threshold_valid_coverage", type=int, default=5,
-                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
-    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
-    gen = p.add_argument_group("general arguments")
-    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
-    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
-    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
-    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
+    _close_export(p, o)
 
 
 def add_motif_overlap_parser(sub):
     """motif_overlap: the sites the motifs of one bin share, which motif is nested in which, and how methylated a motif is outside the
-    motifs nested in it (the reference settles nesting by the motifs' spelling, postprocess.py).  Arguments are those of motif_sites:
-    same ingest."""
-    p = sub.add_parser("motif_overlap", help="Reports shared sites and nesting between the motifs of each bin of bin-motifs.tsv files", add_help=False)
-    p.add_argument("assembly", type=str, help="path to the assembly file.")
-    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
-    gm = p.add_argument_group("contig bin arguments, use one of:")
-    g = gm.add_mutually_exclusive_group(required=True)
-    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
-    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
-    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
-    gm.add_argument("--extension", type=str, default=".fasta",
-                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
-    o = p.add_argument_group("Options")
-    o.add_argument("--bin_motifs", type=str, nargs="+", required=True, help="Path(s) to the bin-motifs.tsv whose motifs are compared (motif_discovery's output)")
-    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
+    motifs nested in it (the reference settles nesting by the motifs' spelling, postprocess.py)."""
+    p, o = _open_export(sub, "motif_overlap", "Reports shared sites and nesting between the motifs of each bin of bin-motifs.tsv files",
+                        "Path(s) to the bin-motifs.tsv whose motifs are compared (motif_discovery's output)")
     o.add_argument("--all_pairs", action="store_true", help="Also write the pairs of motifs that share no site")
     o.add_argument("--min_called", type=int, default=20, help="Called sites a motif, or a part of one, needs to be judged. Default: %(default)s")
     o.add_argument("--max_outside", type=float, default=0.3,
                    help="Fraction of methylation outside its children up to which a motif can be flagged carried_by_children. Default: %(default)s")
     o.add_argument("--min_frac", type=float, default=0.7,
                    help="Fraction of methylation from which a part of a motif counts as methylated (carried_by_children, submotif). Default: %(default)s")
-    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
-                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
-    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
-                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
-    o.add_argument("--threshold_valid_coverage", type=int, default=5,
-                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
-    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
-    gen = p.add_argument_group("general arguments")
-    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
-    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
-    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
-    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
-
-
-def _shape(text):
-    from .engine import kmer_shape
-    try:
-        kmer_shape(text)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e)) from None
-    return text
+    _close_export(p, o)
 
 
 def add_motif_kmers_parser(sub):
     """motif_kmers: the methylation of every k-mer context of every bin, without a motif as input: what the greedy search missed and what
     it over-generalised (no counterpart on the reference's command line; modkit and nanodisco users know the table as the k-mer table).
-    Thresholds and filters are those of motif_sites: same ingest.  --bin_motifs is optional."""
-    p = sub.add_parser("motif_kmers", help="Reports the methylation of every k-mer context around the A / C of every bin", add_help=False)
-    p.add_argument("assembly", type=str, help="path to the assembly file.")
-    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
-    gm = p.add_argument_group("contig bin arguments, use one of:")
-    g = gm.add_mutually_exclusive_group(required=True)
-    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
-    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
-    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
-    gm.add_argument("--extension", type=str, default=".fasta",
-                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
-    o = p.add_argument_group("Options")
-    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
-    o.add_argument("--shape", type=_shape, default="NNN*NNN",
+    --bin_motifs is optional, and placed behind --shape."""
+    p, o = _open_export(sub, "motif_kmers", "Reports the methylation of every k-mer context around the A / C of every bin")
+    o.add_argument("--shape", type=_checked("engine", "kmer_shape", keep_text=True), default="NNN*NNN",
                    help="The counted positions: N counted, . skipped, exactly one * for the modified base; at most 10 N within 31 positions of "
                         "the *, e.g. 'NNN*......NNN'. Default: %(default)s")
     o.add_argument("--bin_motifs", type=str, nargs="+", default=None,
@@ -490,125 +306,43 @@ def add_motif_kmers_parser(sub):
     o.add_argument("--min_called", type=int, default=20, help="Called sites (n_mod + n_nomod) a k-mer needs to be written. Default: %(default)s")
     o.add_argument("--min_frac", type=float, default=0.7,
                    help="frac_mod from which a k-mer no motif accounts for is written to kmer-unexplained.tsv. Default: %(default)s")
-    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
-                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
-    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
-                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
-    o.add_argument("--threshold_valid_coverage", type=int, default=5,
-                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
-    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
-    gen = p.add_argument_group("general arguments")
-    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
-    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
-    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
-    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
+    _close_export(p, o)
 
 
 def add_motif_tracks_parser(sub):
     """motif_tracks: the methylation of the motifs of bin-motifs.tsv files per window along the contigs of their bins, and its breakpoints
-    (no counterpart on the reference's command line).  Arguments are those of motif_sites with one or more bin-motifs.tsv: same ingest."""
-    p = sub.add_parser("motif_tracks", help="Reports the methylation of the motifs of bin-motifs.tsv files along contigs, and its breakpoints", add_help=False)
-    p.add_argument("assembly", type=str, help="path to the assembly file.")
-    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
-    gm = p.add_argument_group("contig bin arguments, use one of:")
-    g = gm.add_mutually_exclusive_group(required=True)
-    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
-    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
-    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
-    gm.add_argument("--extension", type=str, default=".fasta",
-                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
-    o = p.add_argument_group("Options")
-    o.add_argument("--bin_motifs", type=str, nargs="+", required=True, help="Path(s) to the bin-motifs.tsv whose motifs are followed along the contigs (motif_discovery's output)")
-    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
-    o.add_argument("--window", type=_window, default=4096, help="Window size in bp, a multiple of 128 in [128, 2^30]. Default: %(default)s")
+    (no counterpart on the reference's command line)."""
+    p, o = _open_export(sub, "motif_tracks", "Reports the methylation of the motifs of bin-motifs.tsv files along contigs, and its breakpoints",
+                        "Path(s) to the bin-motifs.tsv whose motifs are followed along the contigs (motif_discovery's output)")
+    o.add_argument("--window", type=_checked("motif_tracks", "parse_window"), default=4096,
+                   help="Window size in bp, a multiple of 128 in [128, 2^30]. Default: %(default)s")
     o.add_argument("--min_gain", type=float, default=30.0,
                    help="Likelihood-ratio gain a split needs to be accepted as a breakpoint. Default: %(default)s")
     o.add_argument("--min_called", type=int, default=20, help="Called sites either side of a split needs. Default: %(default)s")
     o.add_argument("--max_segments", type=int, default=8, help="Segments a contig is split into at the most. Default: %(default)s")
     o.add_argument("--tracks", action="store_true", help="Also write motif-tracks.tsv: the six counts of every window that holds an occurrence")
-    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
-                   help="A position is considered non-methylated if fraction of methylation is below this threshold. Default: %(default)s")
-    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
-                   help="A position is considered methylated if fraction of methylated reads is above this threshold. Default: %(default)s")
-    o.add_argument("--threshold_valid_coverage", type=int, default=5,
-                   help="Minimum valid base coverage (Nvalid_cov) for a position to be considered. Default: %(default)s")
-    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
-    gen = p.add_argument_group("general arguments")
-    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
-    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
-    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
-    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
-
-
-def _bins(text):
-    from .motif_fractions import parse_bins
-    try:
-        return parse_bins(text)
-    except ValueError as e:
-        raise argparse.ArgumentTypeError(str(e)) from None
+    _close_export(p, o)
 
 
 def add_motif_fractions_parser(sub):
     """motif_fractions: the histogram of the read fractions n_modified / n_valid_cov over the sites of the motifs of bin-motifs.tsv files (no
     counterpart on the reference's command line).  The pileup is read as READ STATISTICS (binnary's filters), not as thresholded calls."""
-    p = sub.add_parser("motif_fractions", help="Reports the distribution of the read fractions at the motif sites of bin-motifs.tsv files", add_help=False)
-    p.add_argument("assembly", type=str, help="path to the assembly file.")
-    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
-    gm = p.add_argument_group("contig bin arguments, use one of:")
-    g = gm.add_mutually_exclusive_group(required=True)
-    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
-    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
-    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
-    gm.add_argument("--extension", type=str, default=".fasta",
-                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
-    o = p.add_argument_group("Options")
-    o.add_argument("--bin_motifs", type=str, nargs="+", required=True, help="Path(s) to the bin-motifs.tsv whose motif sites are read (motif_discovery's output)")
-    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
-    o.add_argument("--bins", type=_bins, default=20, help="Histogram bins over [0, 1], 2..64. Default: %(default)s")
-    o.add_argument("--min_valid_read_coverage", type=int, default=5,
-                   help="Minimum valid base coverage (Nvalid_cov) for a pileup record to be read. Default: %(default)s")
-    o.add_argument("--min_valid_cov_to_diff_fraction", type=float, default=0.8,
-                   help="Minimum Nvalid_cov / (Nvalid_cov + Ndiff) for a pileup record to be read. Default: %(default)s")
-    o.add_argument("--methylation_threshold_low", type=float, default=0.30,
-                   help="Upper edge of the unmethylated zone, snapped to a bin edge. Default: %(default)s")
-    o.add_argument("--methylation_threshold_high", type=float, default=0.70,
-                   help="Lower edge of the methylated zone, snapped to a bin edge. Default: %(default)s")
-    o.add_argument("--min_sites", type=int, default=20, help="Sites below which a row is flagged few_sites. Default: %(default)s")
-    o.add_argument("--minor_share", type=float, default=0.1,
-                   help="Share of the sites the smaller mode of a bimodal motif needs, and a methylated / unmethylated motif may miss. Default: %(default)s")
-    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
-    gen = p.add_argument_group("general arguments")
-    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
-    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
-    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
-    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
+    p, o = _open_export(sub, "motif_fractions", "Reports the distribution of the read fractions at the motif sites of bin-motifs.tsv files",
+                        "Path(s) to the bin-motifs.tsv whose motif sites are read (motif_discovery's output)")
+    o.add_argument("--bins", type=_checked("motif_fractions", "parse_bins"), default=20, help="Histogram bins over [0, 1], 2..64. Default: %(default)s")
+    _close_export(p, o, "reads and zones", more=(
+        ("--min_sites", dict(type=int, default=20, help="Sites below which a row is flagged few_sites. Default: %(default)s")),
+        ("--minor_share", dict(type=float, default=0.1,
+                               help="Share of the sites the smaller mode of a bimodal motif needs, and a methylated / unmethylated motif may miss. "
+                                    "Default: %(default)s"))))
 
 
 def add_motif_pileup_parser(sub):
     """motif_pileup: the n_valid_cov and n_modified of the pileup record under every site of the motifs of bin-motifs.tsv files (no
-    counterpart on the reference's command line; modkit motif bed + bedtools intersect yield the table).  Arguments are those of
-    motif_fractions without the histogram options: same ingest, the pileup read as READ STATISTICS."""
-    p = sub.add_parser("motif_pileup", help="Reports the read counts under every motif site of bin-motifs.tsv files", add_help=False)
-    p.add_argument("assembly", type=str, help="path to the assembly file.")
-    p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
-    gm = p.add_argument_group("contig bin arguments, use one of:")
-    g = gm.add_mutually_exclusive_group(required=True)
-    g.add_argument("-c", "--contig_bin", type=str, help="TSV file specifying which bin contigs belong.")
-    g.add_argument("-f", "--files", nargs="+", help="List of bin FASTA files with contig names as headers.")
-    g.add_argument("-d", "--directory", help="Directory containing bin FASTA files with contig names as headers.")
-    gm.add_argument("--extension", type=str, default=".fasta",
-                    help="File extension of the bin FASTA files if using -d (DIRECTORY) argument. Default is '.fasta'.")
-    o = p.add_argument_group("Options")
-    o.add_argument("--bin_motifs", type=str, nargs="+", required=True, help="Path(s) to the bin-motifs.tsv whose motif sites are read (motif_discovery's output)")
-    o.add_argument("--out", type=str, help="path to the output folder", default="nanomotif")
-    o.add_argument("--all_occurrences", action="store_true", help="Also write the occurrences whose modified base carries no kept pileup record (0, 0 and an empty percentage)")
-    o.add_argument("--min_valid_read_coverage", type=int, default=5,
-                   help="Minimum valid base coverage (Nvalid_cov) for a pileup record to be read. Default: %(default)s")
-    o.add_argument("--min_valid_cov_to_diff_fraction", type=float, default=0.8,
-                   help="Minimum Nvalid_cov / (Nvalid_cov + Ndiff) for a pileup record to be read. Default: %(default)s")
-    o.add_argument("--device", type=int, default=None, help="GPU to use (default: LOCAL_RANK or 0).")
-    gen = p.add_argument_group("general arguments")
-    gen.add_argument("-t", "--threads", type=int, default=1, help="Threads of the file readers.")
-    gen.add_argument("-v", "--verbose", action="store_true", help="Increase output verbosity. (set logger to debug level)")
-    gen.add_argument("--seed", type=int, default=1, help=argparse.SUPPRESS)
-    gen.add_argument("-h", "--help", action="help", help="show this help message and exit")
+    counterpart on the reference's command line; modkit motif bed + bedtools intersect yield the table).  The arguments of
+    motif_fractions without the histogram options: the pileup read as READ STATISTICS."""
+    p, o = _open_export(sub, "motif_pileup", "Reports the read counts under every motif site of bin-motifs.tsv files",
+                        "Path(s) to the bin-motifs.tsv whose motif sites are read (motif_discovery's output)")
+    o.add_argument("--all_occurrences", action="store_true",
+                   help="Also write the occurrences whose modified base carries no kept pileup record (0, 0 and an empty percentage)")
+    _close_export(p, o, "reads")

@@ -217,6 +217,30 @@ def _budget_groups(costs, limit):
         k = e
 
 
+def _byte_limit(max_bytes, default: int) -> int:
+    """The ``max_bytes`` of a generator over tables: ``default`` when None; ValueError below 1."""
+    limit = default if max_bytes is None else int(max_bytes)
+    if limit < 1:
+        raise ValueError("max_bytes must be at least 1")
+    return limit
+
+
+def _table_groups(b: CandidateBatch, names: dict, n_rows, row_bytes: int, limit: int, shape: tuple, dtype, call):
+    """The table loop of the generators over per-candidate tables (``ScanEngine.motif_tracks`` / ``motif_fractions`` / ``motif_gc`` /
+    ``motif_overlap``).  Candidate j of ``b`` owns ``n_rows[j]`` rows of ``row_bytes`` bytes; consecutive candidates [k, e) share one
+    zeroed table ``dtype[max(rows, 1), *shape]`` while their rows fit ``limit`` bytes (a group holds at least one candidate), filled by
+    ``call(k, e, b.slice(k, e), rows, table)`` with ``rows`` the uint64 row prefix of the group.  Yields (j, the contig names
+    ``names[bin id]`` of j's bin, j's rows of the table) in candidate order — the same under every ``limit``."""
+    bins = [int(x) for x in b.bins]
+    for k, e, _ in _budget_groups([int(n) * row_bytes for n in n_rows], limit):
+        rows = np.zeros(e - k + 1, dtype=np.uint64)
+        np.cumsum([int(n) for n in n_rows[k:e]], out=rows[1:])
+        table = np.zeros((max(int(rows[-1]), 1), *shape), dtype=dtype)
+        call(k, e, b.slice(k, e), rows, table)
+        for j in range(k, e):
+            yield j, names[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
+
+
 class DeviceWindowStore:
     """Window requests of the lock-step search served by the engine's window kernels (nm_win_*): same interface as
     search.HostWindowStore.  Windows are bit planes over windows in HBM; a ``pssm`` request returns integer counts,
@@ -1267,9 +1291,7 @@ class ScanEngine:
         tables fit ``max_bytes`` (default ``KMER_BUDGET_BYTES``; a request is 24 x 4^F bytes); a call holds at least one request.  The
         result does not depend on ``max_bytes``."""
         offsets = np.asarray(kmer_shape(shape), dtype=np.int8)
-        limit = KMER_BUDGET_BYTES if max_bytes is None else int(max_bytes)
-        if limit < 1:
-            raise ValueError("max_bytes must be at least 1")
+        limit = _byte_limit(max_bytes, KMER_BUDGET_BYTES)
         requests = list(requests)
         n, rows = len(requests), 4 ** len(offsets)
         bi, so = self.bin_index, self.slot_of_mod
@@ -1306,24 +1328,22 @@ class ScanEngine:
         one library call while their tables fit ``max_bytes`` (default ``TRACK_BUDGET_BYTES`` = 256 MiB at 24 bytes a row); a group
         always holds at least one candidate.  What is yielded does not depend on ``max_bytes``."""
         w = track_window(window)
-        limit = TRACK_BUDGET_BYTES if max_bytes is None else int(max_bytes)
-        if limit < 1:
-            raise ValueError("max_bytes must be at least 1")
-        b = self._as_batch(candidates)
-        return self._track_groups(b, w, limit)
+        limit = _byte_limit(max_bytes, TRACK_BUDGET_BYTES)
+        return self._track_groups(self._as_batch(candidates), w, limit)
+
+    def _bin_names(self, b: CandidateBatch) -> dict:
+        """{bin id: the names of its resident contigs} of the bins of a batch."""
+        return {bid: self.bin_contigs(bid) for bid in sorted({int(x) for x in b.bins})}
 
     def _track_groups(self, b: CandidateBatch, w: int, limit: int):
-        bins = [int(x) for x in b.bins]
-        names = {bid: self.bin_contigs(bid) for bid in sorted(set(bins))}
+        names = self._bin_names(b)
         prefix = {bid: self.track_windows(bid, w) for bid in names}
-        for k, e, _ in _budget_groups([int(prefix[bid][-1]) * TRACK_ROW_BYTES for bid in bins], limit):
-            rows = np.zeros(e - k + 1, dtype=np.uint64)
-            np.cumsum([int(prefix[bins[j]][-1]) for j in range(k, e)], out=rows[1:])
-            table = np.zeros((max(int(rows[-1]), 1), 6), dtype=np.uint32)
-            sub = b.slice(k, e)
+
+        def call(k, e, sub, rows, table):
             _lib.check(self.lib.nm_motif_tracks_count(self.ctx, *self._batch_args(sub), w, _ptr(rows, C.c_uint64), _ptr(table, C.c_uint32)))
-            for j in range(k, e):
-                yield names[bins[j]], prefix[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
+        n_rows = [int(prefix[int(bid)][-1]) for bid in b.bins]
+        for j, contigs, table in _table_groups(b, names, n_rows, TRACK_ROW_BYTES, limit, (6,), np.uint32, call):
+            yield contigs, prefix[int(b.bins[j])], table
 
     # ------------------------------------------------------------------ read-fraction histograms at motif sites (nm_motif_fractions_count)
     def motif_fractions(self, candidates, bins=20, max_bytes=None):
@@ -1339,9 +1359,7 @@ class ScanEngine:
         bins = int(bins)
         if not FRACTIONS_MIN_BINS <= bins <= FRACTIONS_MAX_BINS:
             raise ValueError(f"bins {bins} outside {FRACTIONS_MIN_BINS}..{FRACTIONS_MAX_BINS}")
-        limit = FRACTIONS_BUDGET_BYTES if max_bytes is None else int(max_bytes)
-        if limit < 1:
-            raise ValueError("max_bytes must be at least 1")
+        limit = _byte_limit(max_bytes, FRACTIONS_BUDGET_BYTES)
         candidates = list(candidates)
         return self._fraction_groups(candidates, self._readstats_batch(candidates), bins, limit)
 
@@ -1354,18 +1372,14 @@ class ScanEngine:
         return self.make_batch(candidates, slot_of=lambda mt: MOD_CODES.index(mt))
 
     def _fraction_groups(self, candidates, b: CandidateBatch, nb: int, limit: int):
-        bins = [int(x) for x in b.bins]
-        names = {bid: self.bin_contigs(bid) for bid in sorted(set(bins))}
+        names = self._bin_names(b)
         width = nb + FRACTIONS_EXTRA
-        row_bytes = 2 * width * 8
-        for k, e, _ in _budget_groups([len(names[bid]) * row_bytes for bid in bins], limit):
-            rows = np.zeros(e - k + 1, dtype=np.int64)
-            np.cumsum([len(names[bins[j]]) for j in range(k, e)], out=rows[1:])
-            table = np.zeros((max(int(rows[-1]), 1), 2, width), dtype=np.uint64)
-            sub = b.slice(k, e)
+
+        def call(k, e, sub, rows, table):                                 # (the library lays the rows out itself: no row prefix goes in)
             _lib.check(self.lib.nm_motif_fractions_count(self.ctx, *self._batch_args(sub), nb, _ptr(table, C.c_uint64)))
-            for j in range(k, e):
-                yield candidates[j], names[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
+        n_rows = [len(names[int(bid)]) for bid in b.bins]
+        for j, contigs, table in _table_groups(b, names, n_rows, 2 * width * 8, limit, (2, width), np.uint64, call):
+            yield candidates[j], contigs, table
 
     # ------------------------------------------------------------------ per-site read counts at motif sites (nm_motif_pileup_*)
     def _pileup_counts(self, b: CandidateBatch, select: int):
@@ -1415,25 +1429,18 @@ class ScanEngine:
         half = int(half)
         if not 0 <= half <= GC_MAX_HALF:
             raise ValueError(f"half {half} outside 0..{GC_MAX_HALF}")
-        limit = GC_BUDGET_BYTES if max_bytes is None else int(max_bytes)
-        if limit < 1:
-            raise ValueError("max_bytes must be at least 1")
-        b = self._as_batch(candidates)
-        return self._gc_groups(b, half, limit)
+        limit = _byte_limit(max_bytes, GC_BUDGET_BYTES)
+        return self._gc_groups(self._as_batch(candidates), half, limit)
 
     def _gc_groups(self, b: CandidateBatch, half: int, limit: int):
-        bins = [int(x) for x in b.bins]
-        names = {bid: self.bin_contigs(bid) for bid in sorted(set(bins))}
+        names = self._bin_names(b)
         width = 2 * half + 3
-        row_bytes = 6 * width * 8
-        for k, e, _ in _budget_groups([len(names[bid]) * row_bytes for bid in bins], limit):
-            rows = np.zeros(e - k + 1, dtype=np.uint64)
-            np.cumsum([len(names[bins[j]]) for j in range(k, e)], out=rows[1:])
-            table = np.zeros((max(int(rows[-1]), 1), 2, 3, width), dtype=np.int64)
-            sub = b.slice(k, e)
+
+        def call(k, e, sub, rows, table):
             _lib.check(self.lib.nm_motif_gc_count(self.ctx, *self._batch_args(sub), half, _ptr(rows, C.c_uint64), _ptr(table, C.c_int64)))
-            for j in range(k, e):
-                yield names[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])]
+        n_rows = [len(names[int(bid)]) for bid in b.bins]
+        for _, contigs, table in _table_groups(b, names, n_rows, 6 * width * 8, limit, (2, 3, width), np.int64, call):
+            yield contigs, table
 
     # ------------------------------------------------------------------ shared sites of a motif and its partners (nm_motif_overlap_count)
     def motif_overlap(self, candidates, partners, max_bytes=None):
@@ -1446,9 +1453,7 @@ class ScanEngine:
         shares with its q-th partner, the last block the REST: its sites no partner has (without partners: block 0 again).
         Consecutive candidates share one library call while their tables fit ``max_bytes`` (default ``OVERLAP_BUDGET_BYTES``); a
         group always holds at least one candidate.  What is yielded does not depend on ``max_bytes``."""
-        limit = OVERLAP_BUDGET_BYTES if max_bytes is None else int(max_bytes)
-        if limit < 1:
-            raise ValueError("max_bytes must be at least 1")
+        limit = _byte_limit(max_bytes, OVERLAP_BUDGET_BYTES)
         b = self._as_batch(candidates)
         partners = [list(p) for p in partners]
         if len(partners) != len(b):
@@ -1459,18 +1464,14 @@ class ScanEngine:
         return self._overlap_groups(b, partners, limit)
 
     def _overlap_groups(self, b: CandidateBatch, partners: list, limit: int):
-        bins = [int(x) for x in b.bins]
-        names = {bid: self.bin_contigs(bid) for bid in sorted(set(bins))}
+        names = self._bin_names(b)
         blocks = [len(p) + 2 for p in partners]
         part0 = np.zeros(len(b) + 1, dtype=np.int64)
         np.cumsum([len(p) for p in partners], out=part0[1:])
         flat = [(m, 0, 0) for p in partners for m in p]
         pb = self.make_batch(flat, slot_of=lambda mt: 0) if flat else None
-        for k, e, _ in _budget_groups([blocks[j] * len(names[bins[j]]) * OVERLAP_ROW_BYTES for j in range(len(b))], limit):
-            rows = np.zeros(e - k + 1, dtype=np.uint64)
-            np.cumsum([blocks[j] * len(names[bins[j]]) for j in range(k, e)], out=rows[1:])
-            table = np.zeros((max(int(rows[-1]), 1), 2, 3), dtype=np.int64)
-            sub = b.slice(k, e)
+
+        def call(k, e, sub, rows, table):
             q0, q1 = int(part0[k]), int(part0[e])
             off = (part0[k:e + 1] - q0).astype(np.uint32)
             if q1 > q0:
@@ -1480,9 +1481,9 @@ class ScanEngine:
                 pargs = (None, None, None, None)
             _lib.check(self.lib.nm_motif_overlap_count(self.ctx, *self._batch_args(sub), _ptr(off, C.c_uint32), *pargs, _ptr(rows, C.c_uint64),
                                                        _ptr(table, C.c_int64)))
-            for j in range(k, e):
-                n = len(names[bins[j]])
-                yield names[bins[j]], table[int(rows[j - k]):int(rows[j - k + 1])].reshape(blocks[j], n, 2, 3)
+        n_rows = [blocks[j] * len(names[int(bid)]) for j, bid in enumerate(b.bins)]
+        for j, contigs, table in _table_groups(b, names, n_rows, OVERLAP_ROW_BYTES, limit, (2, 3), np.int64, call):
+            yield contigs, table.reshape(blocks[j], len(contigs), 2, 3)
 
     # ------------------------------------------------------------------ coverage of a set of motifs (nm_motif_coverage_*)
     def _coverage_args(self, sets):

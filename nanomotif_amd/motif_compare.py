@@ -27,7 +27,6 @@ Files (tab-separated, header line):
 """
 from __future__ import annotations
 
-import logging as log
 import math
 import os
 import time
@@ -36,9 +35,9 @@ import numpy as np
 
 from . import fasta
 from .engine import SITE_STATES, SWITCHED, TRANSITIONS, ScanEngine
+from .export_run import background_candidates, bin_mod_keys, closing, finish, open_run, split_known, table_text, write_texts
 from .loading import kept_mod_types
-from .motif import MOD_TYPE_TO_CANONICAL, Motif
-from .motif_sites import candidates_of_files, open_run, table_text, write_site_batches      # (candidates_of_files: this command's reader of --bin_motifs)
+from .motif_sites import candidates_of_files, write_site_batches      # (candidates_of_files: this command's reader of --bin_motifs)
 
 MAIN_NAME = "motif-compare.tsv"
 CONTIGS_NAME = "motif-compare-contigs.tsv"
@@ -149,30 +148,20 @@ def run(args) -> int:
     eng, cands, status = open_run("motif_compare", args, TIMINGS, pileups=[(args.pileup_a, None), (args.pileup_b, lambda mt: mt + SAMPLE_B_SUFFIX)])
     if eng is None:
         return status
-    TIMINGS["ingest_a_s"], TIMINGS["ingest_b_s"] = (r["seconds"] for r in eng.pileup_ingests)
-    try:
+    with closing(eng):
+        TIMINGS["ingest_a_s"], TIMINGS["ingest_b_s"] = (r["seconds"] for r in eng.pileup_ingests)
         mod_types = kept_mod_types(eng)
-        known = []
-        for c in cands:
-            if c.bin not in eng.bin_index:
-                log.warning(f"{c!r}: the bin has no contig in the assembly; skipped")
-            elif c.mod_type not in mod_types:
-                log.warning(f"{c!r}: neither pileup holds rows of mod type {c.mod_type}; skipped")
-            else:
-                known.append(c)
-        bins = sorted(b for b in eng.bin_index if eng.bin_contigs(b))
-        bin_keys = [(b, mt) for b in bins for mt in mod_types]
+        known = split_known(cands, eng, mod_types, wording="neither pileup holds rows")
+        bin_keys = bin_mod_keys(eng, mod_types)
         os.makedirs(args.out, exist_ok=True)
         t0 = time.perf_counter()
         res = eng.motif_compare_counts([c.engine_candidate() for c in known], labels_of)
-        background = eng.motif_compare_counts([(Motif(MOD_TYPE_TO_CANONICAL[mt], 0), mt, b) for b, mt in bin_keys], labels_of)
+        background = eng.motif_compare_counts(background_candidates(bin_keys), labels_of)
         t_eng = time.perf_counter() - t0
         t0 = time.perf_counter()
-        for name, text in ((MAIN_NAME, format_main(known, [t for _, t in res])),
-                           (CONTIGS_NAME, format_contigs(known, [n for n, _ in res], [t for _, t in res])),
-                           (BINS_NAME, format_bins(bin_keys, [t for _, t in background]))):
-            with open(os.path.join(args.out, name), "w") as f:
-                f.write(text)
+        tables = [t for _, t in res]
+        write_texts(args.out, (MAIN_NAME, CONTIGS_NAME, BINS_NAME),
+                    (format_main(known, tables), format_contigs(known, [n for n, _ in res], tables), format_bins(bin_keys, [t for _, t in background])))
         t_text = time.perf_counter() - t0
         n_records = 0
         if args.switched_sites:
@@ -180,9 +169,6 @@ def run(args) -> int:
                 n_records, t_e, t_t = export_switched(eng, known, transitions, f)
             t_eng += t_e
             t_text += t_t
-        TIMINGS.update(kernels_s=t_eng, text_s=t_text, candidates=len(known), switched_records=n_records)
-        log.info(f"motif_compare: ingest {TIMINGS['ingest_s']:.2f}s (A {TIMINGS['ingest_a_s']:.2f}s, B {TIMINGS['ingest_b_s']:.2f}s), "
-                 f"engine {t_eng:.2f}s, text {t_text:.2f}s")
-    finally:
-        eng.close()
+        finish("motif_compare", TIMINGS, t_eng, t_text, ingest=f" (A {TIMINGS['ingest_a_s']:.2f}s, B {TIMINGS['ingest_b_s']:.2f}s)",
+               candidates=len(known), switched_records=n_records)
     return 0

@@ -43,20 +43,17 @@ Files (tab-separated, header line; candidates in file order, ascending offset, l
 """
 from __future__ import annotations
 
-import logging as log
 import os
 import time
 
 import numpy as np
 
 from .engine import CONTEXT_MAX_RADIUS, MAX_MOTIF_LEN, MAX_REACH
+from .export_run import (background_candidates, bin_mod_keys, closing, finish, frac_text, open_run, parse_int_in, share_text, split_known, table_text,
+                         write_texts)
 from .loading import kept_mod_types
 from .motif import _BIT, ANY, MOD_TYPE_TO_CANONICAL, Motif, iupac_to_regex
-from .motif_profile import frac_text, parse_radius
-from .motif_sites import open_run, table_text
 from .motif_tracks import log_likelihood
-
-assert CONTEXT_MAX_RADIUS == 31                   # parse_radius is motif_profile's: the two limits are one
 
 MAIN_NAME = "motif-context.tsv"
 BINS_NAME = "motif-context-bins.tsv"
@@ -70,9 +67,9 @@ FLAGS = ("none", "underspecified", "few_sites")
 TIMINGS = {}          # seconds per phase of the last run in this process (written to OUT/logs/timings.motif_context.json)
 
 
-def share_text(n: int, total: int) -> str:
-    """n / total as the neighbouring commands write a share; empty when the total is 0."""
-    return "%.6f" % (int(n) / int(total)) if int(total) else ""
+def parse_radius(value) -> int:
+    """``--radius``: an integer in 0..31; ValueError otherwise."""
+    return parse_int_in("--radius", value, 0, CONTEXT_MAX_RADIUS)
 
 
 def pooled(table) -> np.ndarray:
@@ -176,31 +173,18 @@ def run(args) -> int:
     eng, cands, status = open_run("motif_context", args, TIMINGS)
     if eng is None:
         return status
-    try:
+    with closing(eng):
         mod_types = kept_mod_types(eng)
-        known = [c for c in cands if c.bin in eng.bin_index and c.mod_type in mod_types]
-        for c in cands:
-            if c.bin not in eng.bin_index:
-                log.warning(f"{c!r}: the bin has no contig in the assembly; skipped")
-            elif c.mod_type not in mod_types:
-                log.warning(f"{c!r}: the pileup holds no rows of mod type {c.mod_type}; skipped")
-        bins = sorted(b for b in eng.bin_index if eng.bin_contigs(b))
-        bg_keys = [(b, mt) for b in bins for mt in mod_types]
+        known = split_known(cands, eng, mod_types)
+        bg_keys = bin_mod_keys(eng, mod_types)
         os.makedirs(args.out, exist_ok=True)
         t0 = time.perf_counter()
         # the background's one-letter candidates ride in the same engine call as the motifs
-        batch = [c.engine_candidate() for c in known] + [(Motif(MOD_TYPE_TO_CANONICAL[mt], 0), mt, b) for b, mt in bg_keys]
-        _, table = eng.motif_context(batch, radius=radius)
+        _, table = eng.motif_context([c.engine_candidate() for c in known] + background_candidates(bg_keys), radius=radius)
         t_eng = time.perf_counter() - t0
         t0 = time.perf_counter()
         n = len(known)
-        texts = format_files(known, table[:n], bg_keys, table[n:], int(args.min_called), float(args.min_gain))
-        for name, text in zip((MAIN_NAME, BINS_NAME, SUMMARY_NAME), texts):
-            with open(os.path.join(args.out, name), "w") as f:
-                f.write(text)
-        t_text = time.perf_counter() - t0
-        TIMINGS.update(kernels_s=t_eng, text_s=t_text, candidates=n, background_candidates=len(bg_keys), radius=radius)
-        log.info(f"motif_context: ingest {TIMINGS['ingest_s']:.2f}s, engine {t_eng:.2f}s, text {t_text:.2f}s")
-    finally:
-        eng.close()
+        write_texts(args.out, (MAIN_NAME, BINS_NAME, SUMMARY_NAME),
+                    format_files(known, table[:n], bg_keys, table[n:], int(args.min_called), float(args.min_gain)))
+        finish("motif_context", TIMINGS, t_eng, time.perf_counter() - t0, candidates=n, background_candidates=len(bg_keys), radius=radius)
     return 0

@@ -19,7 +19,6 @@ position, '+' before '-').
 """
 from __future__ import annotations
 
-import logging as log
 import os
 import time
 
@@ -27,8 +26,8 @@ import numpy as np
 
 from . import fasta
 from .engine import SITE_MINUS, ScanEngine
+from .export_run import closing, finish, open_run, resident_bins, split_known, table_text, write_texts
 from .loading import kept_mod_types
-from .motif_sites import open_run, table_text
 
 SETS_NAME = "motif-coverage.tsv"
 CONTIGS_NAME = "motif-coverage-contigs.tsv"
@@ -131,24 +130,16 @@ def run(args) -> int:
     eng, cands, status = open_run("motif_coverage", args, TIMINGS)
     if eng is None:
         return status
-    try:
+    with closing(eng):
         mod_types = kept_mod_types(eng)
-        for c in cands:
-            if c.bin not in eng.bin_index:
-                log.warning(f"{c!r}: the bin has no contig in the assembly; skipped")
-            elif c.mod_type not in mod_types:
-                log.warning(f"{c!r}: the pileup holds no rows of mod type {c.mod_type}; skipped")
-        bins = [b for b in eng.bin_index if eng.bin_contigs(b)]
-        sets = build_sets(bins, mod_types, cands)
+        sets = build_sets(resident_bins(eng), mod_types, split_known(cands, eng, mod_types))
         os.makedirs(args.out, exist_ok=True)
         t0 = time.perf_counter()
         names, set_tables, exclusive, site_counts = coverage_tables(eng, sets)
         t_eng = time.perf_counter() - t0
         t0 = time.perf_counter()
-        for name, text in ((SETS_NAME, format_sets(sets, set_tables)), (CONTIGS_NAME, format_contigs(sets, names, set_tables)),
-                           (MOTIFS_NAME, format_motifs(sets, site_counts, exclusive))):
-            with open(os.path.join(args.out, name), "w") as f:
-                f.write(text)
+        write_texts(args.out, (SETS_NAME, CONTIGS_NAME, MOTIFS_NAME),
+                    (format_sets(sets, set_tables), format_contigs(sets, names, set_tables), format_motifs(sets, site_counts, exclusive)))
         t_text = time.perf_counter() - t0
         n_records = 0
         if args.unexplained_sites:
@@ -162,8 +153,5 @@ def run(args) -> int:
                     t0 = time.perf_counter()
                     t_text += t0 - t1
                 t_eng += time.perf_counter() - t0
-        TIMINGS.update(kernels_s=t_eng, text_s=t_text, sets=len(sets), candidates=sum(len(s.candidates) for s in sets), unexplained_records=n_records)
-        log.info(f"motif_coverage: ingest {TIMINGS['ingest_s']:.2f}s, engine {t_eng:.2f}s, text {t_text:.2f}s")
-    finally:
-        eng.close()
+        finish("motif_coverage", TIMINGS, t_eng, t_text, sets=len(sets), candidates=sum(len(s.candidates) for s in sets), unexplained_records=n_records)
     return 0

@@ -39,12 +39,11 @@ import time
 
 import numpy as np
 
-from . import _lib, fasta
-from .contig_methylation import MOD_CODES
+from . import fasta
 from .engine import FRACTIONS_EXTRA, FRACTIONS_MAX_BINS, FRACTIONS_MIN_BINS
-from .motif import MOD_TYPE_TO_CANONICAL, Motif
-from .motif_sites import open_candidates, table_text
-from .motif_tracks import background_keys
+from .export_run import (READ_FILTER_SUFFIX, background_candidates, background_keys, closing, finish, open_readstats_run, parse_int_in,
+                         readstats_mod_types, share_text, split_known, table_text, write_texts)
+from .motif import MOD_TYPE_TO_CANONICAL
 
 SUMMARY_NAME = "motif-fractions.tsv"
 CONTIGS_NAME = "motif-fractions-contigs.tsv"
@@ -63,13 +62,7 @@ TIMINGS = {}          # seconds per phase of the last run in this process (writt
 
 def parse_bins(value) -> int:
     """``--bins``: 2..64; ValueError otherwise."""
-    try:
-        b = int(str(value).strip())
-    except ValueError:
-        b = -1
-    if not FRACTIONS_MIN_BINS <= b <= FRACTIONS_MAX_BINS:
-        raise ValueError(f"--bins takes a number in [{FRACTIONS_MIN_BINS}, {FRACTIONS_MAX_BINS}]; got {value!r}")
-    return b
+    return parse_int_in("--bins", value, FRACTIONS_MIN_BINS, FRACTIONS_MAX_BINS, what=f"a number in [{FRACTIONS_MIN_BINS}, {FRACTIONS_MAX_BINS}]")
 
 
 def site_bin(n_modified: int, n_valid_cov: int, bins: int) -> int:
@@ -116,10 +109,6 @@ def flag_of(hist, k_low: int, k_high: int, min_sites: int, minor_share: float) -
     return "partial"
 
 
-def _ratio(num: int, den: int) -> str:
-    return "%.6f" % (int(num) / int(den)) if int(den) else ""
-
-
 def _edge(x) -> str:
     return "" if x is None else "%.6f" % x
 
@@ -140,10 +129,10 @@ class Stats:
         self.quantiles = [quantile_edge(self.hist, q) for q in QUANTILES]
 
     def head(self):
-        return [self.n_occurrences, self.n_sites, _ratio(self.sum_valid, self.n_sites), _ratio(self.sum_mod, self.sum_valid)]
+        return [self.n_occurrences, self.n_sites, share_text(self.sum_valid, self.n_sites), share_text(self.sum_mod, self.sum_valid)]
 
     def shares(self):
-        return [_ratio(z, self.n_sites) for z in self.zones]
+        return [share_text(z, self.n_sites) for z in self.zones]
 
 
 def hist_rows(key, background: int, table, bins: int) -> list:
@@ -161,7 +150,7 @@ def candidate_rows(cand, names, table, bg_table, bins: int, k_low: int, k_high: 
         bg_cols = ["", "", "", "", ""]
     else:
         bg = Stats(bg_table, *args)
-        bg_cols = [bg.n_sites, _ratio(bg.sum_mod, bg.sum_valid)] + bg.shares()
+        bg_cols = [bg.n_sites, share_text(bg.sum_mod, bg.sum_valid)] + bg.shares()
     summary = [key + st.head() + [_edge(q) for q in st.quantiles] + st.shares() + ["%.6f" % (k_low / bins), "%.6f" % (k_high / bins), st.flag,
                                                                                   st.n_fwd, st.n_rev] + bg_cols]
     contigs = []
@@ -190,49 +179,27 @@ def format_files(cands, items, backgrounds, bins: int, k_low: int, k_high: int, 
 
 def run(args) -> int:
     """The command.  Returns the process's exit status."""
-    from .loading import AliasedContigs, load_readstats_engine
     bins = parse_bins(args.bins)
     try:
         k_low, k_high = snap_edges(args.methylation_threshold_low, args.methylation_threshold_high, bins)
     except ValueError as e:
         log.error(str(e))
         return 2
-    cands, device, status = open_candidates("motif_fractions", args, TIMINGS)
-    if cands is None:
+    eng, cands, status = open_readstats_run("motif_fractions", args, TIMINGS)
+    if eng is None:
         return status
-    wanted = sorted({c.mod_type for c in cands if c.mod_type in MOD_CODES})
-    t0 = time.perf_counter()
-    try:
-        eng = load_readstats_engine(args, device, wanted)
-    except AliasedContigs as e:
-        log.error(f"motif_fractions: {e}")
-        return 2
-    except _lib.NmScanError as e:
-        raise RuntimeError(f"nanomotif_amd needs an AMD GPU (MI355X); there is no CPU fallback ({e})") from e
-    TIMINGS["ingest_s"] = time.perf_counter() - t0
-    try:
-        have = {mt for mt, n in eng.readstats_kept.items() if n}
-        known = [c for c in cands if c.bin in eng.bin_index and c.mod_type in have]
-        for c in cands:
-            if c.bin not in eng.bin_index:
-                log.warning(f"{c!r}: the bin has no contig in the assembly; skipped")
-            elif c.mod_type not in have:
-                log.warning(f"{c!r}: the pileup holds no rows of mod type {c.mod_type} that pass the read filters; skipped")
+    with closing(eng):
+        known = split_known(cands, eng, readstats_mod_types(eng), suffix=READ_FILTER_SUFFIX)
         bg_keys = background_keys(known)
         os.makedirs(args.out, exist_ok=True)
         # the background's one-letter candidates ride in the same engine call, ahead of the motifs that are read against them
-        batch = [(Motif(MOD_TYPE_TO_CANONICAL[mt], 0), mt, b) for b, mt in bg_keys] + [c.engine_candidate() for c in known]
+        batch = background_candidates(bg_keys) + [c.engine_candidate() for c in known]
         t0 = time.perf_counter()
         items = [(names, table) for _, names, table in eng.motif_fractions(batch, bins=bins)]
         t1 = time.perf_counter()
-        texts = format_files(known, items[len(bg_keys):], [(key, items[k][1]) for k, key in enumerate(bg_keys)], bins, k_low, k_high,
-                             int(args.min_sites), float(args.minor_share))
-        for name, text in zip((SUMMARY_NAME, CONTIGS_NAME, HIST_NAME), texts):
-            with open(os.path.join(args.out, name), "w") as f:
-                f.write(text)
-        t_text = time.perf_counter() - t1
-        TIMINGS.update(kernels_s=t1 - t0, text_s=t_text, candidates=len(known), background_candidates=len(bg_keys), bins=bins)
-        log.info(f"motif_fractions: ingest {TIMINGS['ingest_s']:.2f}s, engine {t1 - t0:.2f}s, statistics and text {t_text:.2f}s")
-    finally:
-        eng.close()
+        write_texts(args.out, (SUMMARY_NAME, CONTIGS_NAME, HIST_NAME),
+                    format_files(known, items[len(bg_keys):], [(key, items[k][1]) for k, key in enumerate(bg_keys)], bins, k_low, k_high,
+                                 int(args.min_sites), float(args.minor_share)))
+        finish("motif_fractions", TIMINGS, t1 - t0, time.perf_counter() - t1, label="statistics and text", candidates=len(known),
+               background_candidates=len(bg_keys), bins=bins)
     return 0

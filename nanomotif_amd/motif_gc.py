@@ -43,7 +43,6 @@ Files (tab-separated, header line; candidates in file order):
 """
 from __future__ import annotations
 
-import logging as log
 import math
 import os
 import time
@@ -52,10 +51,10 @@ import numpy as np
 
 from . import fasta
 from .engine import GC_MAX_HALF
+from .export_run import (background_candidates, bin_mod_keys, closing, finish, frac_text, open_run, parse_int_in, share_text, split_known, table_text,
+                         write_texts)
 from .loading import kept_mod_types
-from .motif import MOD_TYPE_TO_CANONICAL, Motif
-from .motif_profile import frac_text
-from .motif_sites import open_run, table_text
+from .motif import MOD_TYPE_TO_CANONICAL
 
 MAIN_NAME = "motif-gc.tsv"
 BINS_NAME = "motif-gc-bins.tsv"
@@ -75,24 +74,12 @@ TIMINGS = {}          # seconds per phase of the last run in this process (writt
 
 def parse_half(value) -> int:
     """``--half``: an integer in 0..31 (the window is 2 half + 1 positions; one word of halo either side); ValueError otherwise."""
-    try:
-        h = int(str(value).strip())
-    except ValueError:
-        raise ValueError(f"--half takes an integer in 0..{GC_MAX_HALF}; got {value!r}") from None
-    if not 0 <= h <= GC_MAX_HALF:
-        raise ValueError(f"--half takes an integer in 0..{GC_MAX_HALF}; got {value!r}")
-    return h
+    return parse_int_in("--half", value, 0, GC_MAX_HALF)
 
 
 def parse_gc_bins(value) -> int:
     """``--gc_bins``: an integer of at least 1; ValueError otherwise."""
-    try:
-        b = int(str(value).strip())
-    except ValueError:
-        raise ValueError(f"--gc_bins takes an integer of at least 1; got {value!r}") from None
-    if b < 1:
-        raise ValueError(f"--gc_bins takes an integer of at least 1; got {value!r}")
-    return b
+    return parse_int_in("--gc_bins", value, 1)
 
 
 def effective_bins(bins: int, width: int) -> int:
@@ -293,20 +280,16 @@ def format_files(cands, results, bg_keys, bg_results, contig_gc, bin_gc, bins=8,
             table_text(SUMMARY_HEADER, summary_rows))
 
 
-def gc_share_text(gc: int, acgt: int) -> str:
-    return "%.6f" % (int(gc) / int(acgt)) if int(acgt) else ""
-
-
 def sequence_gc(eng):
     """(contig name -> G + C share of its A, C, G and T as text, bin name -> the same over the bin's contigs), from the resident
     sequence."""
     counts = {x: eng.contig_base_counts(x, 0).astype(np.int64) for x in "ACGT"}
     gc, acgt = counts["C"] + counts["G"], counts["A"] + counts["C"] + counts["G"] + counts["T"]
-    contig_gc = {name: gc_share_text(gc[i], acgt[i]) for i, name in enumerate(eng.contig_names)}
+    contig_gc = {name: share_text(gc[i], acgt[i]) for i, name in enumerate(eng.contig_names)}
     bin_gc = {}
     for b in eng.bin_index:
         ids = [eng.contig_index[n] for n in eng.bin_contigs(b)]
-        bin_gc[b] = gc_share_text(gc[ids].sum(), acgt[ids].sum()) if ids else ""
+        bin_gc[b] = share_text(gc[ids].sum(), acgt[ids].sum()) if ids else ""
     return contig_gc, bin_gc
 
 
@@ -316,32 +299,19 @@ def run(args) -> int:
     eng, cands, status = open_run("motif_gc", args, TIMINGS)
     if eng is None:
         return status
-    try:
+    with closing(eng):
         mod_types = kept_mod_types(eng)
-        known = [c for c in cands if c.bin in eng.bin_index and c.mod_type in mod_types]
-        for c in cands:
-            if c.bin not in eng.bin_index:
-                log.warning(f"{c!r}: the bin has no contig in the assembly; skipped")
-            elif c.mod_type not in mod_types:
-                log.warning(f"{c!r}: the pileup holds no rows of mod type {c.mod_type}; skipped")
-        bin_names = sorted(b for b in eng.bin_index if eng.bin_contigs(b))
-        bg_keys = [(b, mt) for b in bin_names for mt in mod_types]
+        known = split_known(cands, eng, mod_types)
+        bg_keys = bin_mod_keys(eng, mod_types)
         os.makedirs(args.out, exist_ok=True)
         t0 = time.perf_counter()
         # the background's one-letter candidates ride in the same engine calls as the motifs
-        batch = [c.engine_candidate() for c in known] + [(Motif(MOD_TYPE_TO_CANONICAL[mt], 0), mt, b) for b, mt in bg_keys]
-        results = list(eng.motif_gc(batch, half=half))
+        results = list(eng.motif_gc([c.engine_candidate() for c in known] + background_candidates(bg_keys), half=half))
         contig_gc, bin_gc = sequence_gc(eng)
         t_eng = time.perf_counter() - t0
         t0 = time.perf_counter()
         n = len(known)
-        texts = format_files(known, results[:n], bg_keys, results[n:], contig_gc, bin_gc, bins, int(args.min_called), float(args.min_z), float(args.min_delta))
-        for name, text in zip((MAIN_NAME, BINS_NAME, CONTIGS_NAME, SUMMARY_NAME), texts):
-            with open(os.path.join(args.out, name), "w") as f:
-                f.write(text)
-        t_text = time.perf_counter() - t0
-        TIMINGS.update(kernels_s=t_eng, text_s=t_text, candidates=n, background_candidates=len(bg_keys), half=half, gc_bins=bins)
-        log.info(f"motif_gc: ingest {TIMINGS['ingest_s']:.2f}s, engine {t_eng:.2f}s, text {t_text:.2f}s")
-    finally:
-        eng.close()
+        write_texts(args.out, (MAIN_NAME, BINS_NAME, CONTIGS_NAME, SUMMARY_NAME),
+                    format_files(known, results[:n], bg_keys, results[n:], contig_gc, bin_gc, bins, int(args.min_called), float(args.min_z), float(args.min_delta)))
+        finish("motif_gc", TIMINGS, t_eng, time.perf_counter() - t0, candidates=n, background_candidates=len(bg_keys), half=half, gc_bins=bins)
     return 0

@@ -44,16 +44,15 @@ not on real data.
 """
 from __future__ import annotations
 
-import logging as log
 import os
 import time
 
 import numpy as np
 
+from .export_run import closing, finish, open_run, resident_bins, split_known, table_text, write_texts
 from .loading import kept_mod_types
 from .motif import ANY, Motif, iupac_to_regex
 from .motif_coverage import build_sets
-from .motif_sites import open_run, table_text
 
 PAIRS_NAME = "motif-overlap.tsv"
 MOTIFS_NAME = "motif-overlap-motifs.tsv"
@@ -276,29 +275,16 @@ def run(args) -> int:
     eng, cands, status = open_run("motif_overlap", args, TIMINGS)
     if eng is None:
         return status
-    try:
+    with closing(eng):
         mod_types = kept_mod_types(eng)
-        for c in cands:
-            if c.bin not in eng.bin_index:
-                log.warning(f"{c!r}: the bin has no contig in the assembly; skipped")
-            elif c.mod_type not in mod_types:
-                log.warning(f"{c!r}: the pileup holds no rows of mod type {c.mod_type}; skipped")
-        bins = [b for b in eng.bin_index if eng.bin_contigs(b)]
-        sets = [s for s in build_sets(bins, mod_types, cands) if s.candidates]
+        sets = [s for s in build_sets(resident_bins(eng), mod_types, split_known(cands, eng, mod_types)) if s.candidates]
         os.makedirs(args.out, exist_ok=True)
         t0 = time.perf_counter()
         stats = overlap_stats(eng, sets)
         t_eng = time.perf_counter() - t0
         t0 = time.perf_counter()
-        texts = (format_pairs(sets, stats, bool(args.all_pairs)),
-                 format_motifs(sets, stats, int(args.min_called), float(args.max_outside), float(args.min_frac)))
-        for name, text in zip((PAIRS_NAME, MOTIFS_NAME), texts):
-            with open(os.path.join(args.out, name), "w") as f:
-                f.write(text)
-        t_text = time.perf_counter() - t0
-        TIMINGS.update(kernels_s=t_eng, text_s=t_text, sets=len(sets), candidates=sum(len(s.candidates) for s in sets),
-                       pairs=sum(len(s.candidates) * (len(s.candidates) - 1) // 2 for s in sets))
-        log.info(f"motif_overlap: ingest {TIMINGS['ingest_s']:.2f}s, engine {t_eng:.2f}s, text {t_text:.2f}s")
-    finally:
-        eng.close()
+        write_texts(args.out, (PAIRS_NAME, MOTIFS_NAME), (format_pairs(sets, stats, bool(args.all_pairs)),
+                                                          format_motifs(sets, stats, int(args.min_called), float(args.max_outside), float(args.min_frac))))
+        finish("motif_overlap", TIMINGS, t_eng, time.perf_counter() - t0, sets=len(sets), candidates=sum(len(s.candidates) for s in sets),
+               pairs=sum(len(s.candidates) * (len(s.candidates) - 1) // 2 for s in sets))
     return 0

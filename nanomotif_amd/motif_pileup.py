@@ -25,15 +25,13 @@ Files:
 from __future__ import annotations
 
 import ctypes as C
-import logging as log
 import os
 import time
 
 import numpy as np
 
 from . import _lib, fasta
-from .contig_methylation import MOD_CODES
-from .motif_sites import open_candidates, table_text
+from .export_run import READ_FILTER_SUFFIX, closing, finish, open_readstats_run, readstats_mod_types, share_text, split_known, table_text, write_texts
 
 BED_NAME = "motif-pileup.bed"
 SUMMARY_NAME = "motif-pileup-summary.tsv"
@@ -74,10 +72,6 @@ def format_pileup(contig, pos, code, n_valid, n_mod, seg_begin, seg_names, seg_b
     return buf.tobytes()
 
 
-def _ratio(num: int, den: int) -> str:
-    return "%.6f" % (int(num) / int(den)) if int(den) else ""
-
-
 def format_summary(summary) -> str:
     """motif-pileup-summary.tsv as text.  ``summary``: [(candidate, contig name, int64[4] = fwd site, fwd bare, rev site, rev bare,
     sum_valid_cov, sum_modified)] in candidate, contig order; a contig without an occurrence has no row."""
@@ -86,7 +80,7 @@ def format_summary(summary) -> str:
         fs, fb, rs, rb = (int(x) for x in four)
         if fs + fb + rs + rb:
             rows.append([c.bin, fasta.original_name(contig), c.motif, c.mod_type, c.mod_position, fs + fb, rs + rb, fs, rs, int(sum_valid), int(sum_mod),
-                         _ratio(sum_valid, fs + rs), _ratio(sum_mod, sum_valid)])
+                         share_text(sum_valid, fs + rs), share_text(sum_mod, sum_valid)])
     return table_text(SUMMARY_HEADER, rows)
 
 
@@ -129,36 +123,15 @@ def export_pileup(eng, cands: list, all_occurrences: bool, bed_file, max_records
 
 def run(args) -> int:
     """The command.  Returns the process's exit status."""
-    from .loading import AliasedContigs, load_readstats_engine
-    cands, device, status = open_candidates("motif_pileup", args, TIMINGS)
-    if cands is None:
+    eng, cands, status = open_readstats_run("motif_pileup", args, TIMINGS)
+    if eng is None:
         return status
-    wanted = sorted({c.mod_type for c in cands if c.mod_type in MOD_CODES})
-    t0 = time.perf_counter()
-    try:
-        eng = load_readstats_engine(args, device, wanted)
-    except AliasedContigs as e:
-        log.error(f"motif_pileup: {e}")
-        return 2
-    except _lib.NmScanError as e:
-        raise RuntimeError(f"nanomotif_amd needs an AMD GPU (MI355X); there is no CPU fallback ({e})") from e
-    TIMINGS["ingest_s"] = time.perf_counter() - t0
-    try:
-        have = {mt for mt, n in eng.readstats_kept.items() if n}
-        known = [c for c in cands if c.bin in eng.bin_index and c.mod_type in have]
-        for c in cands:
-            if c.bin not in eng.bin_index:
-                log.warning(f"{c!r}: the bin has no contig in the assembly; skipped")
-            elif c.mod_type not in have:
-                log.warning(f"{c!r}: the pileup holds no rows of mod type {c.mod_type} that pass the read filters; skipped")
+    with closing(eng):
+        known = split_known(cands, eng, readstats_mod_types(eng), suffix=READ_FILTER_SUFFIX)
         os.makedirs(args.out, exist_ok=True)
         with open(os.path.join(args.out, BED_NAME), "wb") as f:
             summary, (t_eng, t_text) = export_pileup(eng, known, bool(args.all_occurrences), f)
         t1 = time.perf_counter()
-        with open(os.path.join(args.out, SUMMARY_NAME), "w") as f:
-            f.write(format_summary(summary))
-        TIMINGS.update(kernels_s=t_eng, text_s=t_text + time.perf_counter() - t1, candidates=len(known))
-        log.info(f"motif_pileup: ingest {TIMINGS['ingest_s']:.2f}s, engine {t_eng:.2f}s, text {TIMINGS['text_s']:.2f}s")
-    finally:
-        eng.close()
+        write_texts(args.out, (SUMMARY_NAME,), (format_summary(summary),))
+        finish("motif_pileup", TIMINGS, t_eng, t_text + time.perf_counter() - t1, candidates=len(known))
     return 0

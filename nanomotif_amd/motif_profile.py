@@ -43,9 +43,9 @@ import time
 import numpy as np
 
 from .engine import PROFILE_MAX_RADIUS, ScanEngine
+from .export_run import closing, finish, frac_text, open_run, parse_int_in, resident_bins, table_text, write_texts
 from .loading import kept_mod_types
 from .motif import MOD_TYPE_TO_CANONICAL, Motif
-from .motif_sites import open_run, table_text
 from .pileup import MOD_TYPES
 
 MAIN_NAME = "motif-profile.tsv"
@@ -70,19 +70,7 @@ def parse_targets(text) -> tuple:
 
 def parse_radius(value) -> int:
     """``--radius``: an integer in 0..31 (one v_alignbit of two neighbouring words per offset); ValueError otherwise."""
-    try:
-        r = int(str(value).strip())
-    except ValueError:
-        raise ValueError(f"--radius takes an integer in 0..{PROFILE_MAX_RADIUS}; got {value!r}") from None
-    if not 0 <= r <= PROFILE_MAX_RADIUS:
-        raise ValueError(f"--radius takes an integer in 0..{PROFILE_MAX_RADIUS}; got {value!r}")
-    return r
-
-
-def frac_text(n_mod: int, n_nomod: int) -> str:
-    """n_mod / (n_mod + n_nomod) as the neighbouring commands write a share; empty when nothing is called."""
-    called = int(n_mod) + int(n_nomod)
-    return "%.6f" % (int(n_mod) / called) if called else ""
+    return parse_int_in("--radius", value, 0, PROFILE_MAX_RADIUS)
 
 
 def pooled(table) -> np.ndarray:
@@ -212,12 +200,12 @@ def run(args) -> int:
     eng, cands, status = open_run("motif_profile", args, TIMINGS)
     if eng is None:
         return status
-    try:
+    with closing(eng):
         targets = run_targets(eng, asked)
         if not targets:
             log.error("motif_profile: the pileup holds no rows of any target mod type")
             return 2
-        known = []
+        known = []          # this command's own rule, in one pass: a mod type outside the targets is kept (the targets are read under any motif)
         for c in cands:
             if c.bin not in eng.bin_index:
                 log.warning(f"{c!r}: the bin has no contig in the assembly; skipped")
@@ -225,8 +213,7 @@ def run(args) -> int:
                 known.append(c)
                 if c.mod_type not in targets:
                     log.warning(f"{c!r}: mod type {c.mod_type} is not among the targets; its own columns stay empty")
-        bins = sorted(b for b in eng.bin_index if eng.bin_contigs(b))
-        bg_keys = background_keys(bins, targets)
+        bg_keys = background_keys(resident_bins(eng), targets)
         os.makedirs(args.out, exist_ok=True)
         t0 = time.perf_counter()
         # the background's one-letter candidates ride in the same engine call as the motifs
@@ -235,13 +222,7 @@ def run(args) -> int:
         t_eng = time.perf_counter() - t0
         t0 = time.perf_counter()
         n = len(known)
-        texts = format_files(known, targets, sites[:n], table[:n], bg_keys, sites[n:], table[n:], int(args.min_called))
-        for name, text in zip((MAIN_NAME, BINS_NAME, SUMMARY_NAME), texts):
-            with open(os.path.join(args.out, name), "w") as f:
-                f.write(text)
-        t_text = time.perf_counter() - t0
-        TIMINGS.update(kernels_s=t_eng, text_s=t_text, candidates=n, background_candidates=len(bg_keys), targets=len(targets), radius=radius)
-        log.info(f"motif_profile: ingest {TIMINGS['ingest_s']:.2f}s, engine {t_eng:.2f}s, text {t_text:.2f}s")
-    finally:
-        eng.close()
+        write_texts(args.out, (MAIN_NAME, BINS_NAME, SUMMARY_NAME),
+                    format_files(known, targets, sites[:n], table[:n], bg_keys, sites[n:], table[n:], int(args.min_called)))
+        finish("motif_profile", TIMINGS, t_eng, time.perf_counter() - t0, candidates=n, background_candidates=len(bg_keys), targets=len(targets), radius=radius)
     return 0

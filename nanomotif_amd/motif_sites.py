@@ -19,7 +19,6 @@ from __future__ import annotations
 
 import csv
 import ctypes as C
-import logging as log
 import os
 import time
 
@@ -27,7 +26,7 @@ import numpy as np
 
 from . import _lib, fasta
 from .engine import SITE_STATES, ScanEngine
-from .loading import load_engine
+from .export_run import closing, finish, open_candidates, open_run, split_known, table_text, write_texts      # (open_*: also found here)
 from .motif import Motif, iupac_to_regex
 
 BED_NAME = "motif-sites.bed"
@@ -170,11 +169,6 @@ def format_summary(summary) -> str:
     return table_text(SUMMARY_HEADER, rows)
 
 
-def table_text(header, rows) -> str:
-    """A tab-separated table as text: the header line, then one line per row."""
-    return "\n".join(["\t".join(header)] + ["\t".join(str(x) for x in r) for r in rows]) + "\n"
-
-
 def candidates_of_files(paths) -> list:
     """The candidates of several bin-motifs.tsv in order; a (bin, motif, mod_type, position) seen before is not repeated."""
     out, seen = [], set()
@@ -186,58 +180,18 @@ def candidates_of_files(paths) -> list:
     return out
 
 
-def open_candidates(command: str, args, timings: dict):
-    """How every export command opens, before anything is loaded: the refusal of a multi-rank launch and the candidates of
-    ``--bin_motifs`` (one file or several).  Returns (candidates, the GPU to use, 0), or (None, None, the exit status) when the command
-    does not run."""
-    timings.clear()
-    if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
-        log.error("%s runs on one GPU: start it without a multi-rank launcher (WORLD_SIZE is %s)", command, os.environ["WORLD_SIZE"])
-        return None, None, 2
-    files = [args.bin_motifs] if isinstance(args.bin_motifs, str) else list(args.bin_motifs)
-    cands = candidates_of_files(files)
-    log.info(f"{len(cands)} (bin, motif) candidates from {', '.join(files)}")
-    device = args.device if args.device is not None else int(os.environ.get("LOCAL_RANK", "0") or 0)
-    return cands, device, 0
-
-
-def open_run(command: str, args, timings: dict, pileups=None):
-    """How the export commands that read the state planes open: ``open_candidates``, the loaded engine (``loading.load_engine`` with
-    ``pileups``) and ``timings["ingest_s"]``.  Returns (engine, candidates, 0), or (None, None, the exit status) when the command does
-    not run."""
-    cands, device, status = open_candidates(command, args, timings)
-    if cands is None:
-        return None, None, status
-    t0 = time.perf_counter()
-    try:
-        eng = load_engine(args, device, pileups)
-    except _lib.NmScanError as e:
-        raise RuntimeError(f"nanomotif_amd needs an AMD GPU (MI355X); there is no CPU fallback ({e})") from e
-    timings["ingest_s"] = time.perf_counter() - t0
-    return eng, cands, 0
-
-
 def run(args) -> int:
     """The command.  Returns the process's exit status."""
     states = args.states if isinstance(args.states, tuple) else parse_states(args.states)
     eng, cands, status = open_run("motif_sites", args, TIMINGS)
     if eng is None:
         return status
-    try:
-        known = [c for c in cands if c.bin in eng.bin_index and c.mod_type in eng.slot_of_mod]
-        for c in cands:
-            if c.bin not in eng.bin_index:
-                log.warning(f"{c!r}: the bin has no contig in the assembly; skipped")
-            elif c.mod_type not in eng.slot_of_mod:
-                log.warning(f"{c!r}: the pileup holds no rows of mod type {c.mod_type}; skipped")
+    with closing(eng):
+        known = split_known(cands, eng, eng.slot_of_mod)
         os.makedirs(args.out, exist_ok=True)
         with open(os.path.join(args.out, BED_NAME), "wb") as f:
             summary, (t_eng, t_text) = export_sites(eng, known, states, f)
         t1 = time.perf_counter()
-        with open(os.path.join(args.out, SUMMARY_NAME), "w") as f:
-            f.write(format_summary(summary))
-        TIMINGS.update(kernels_s=t_eng, text_s=t_text + time.perf_counter() - t1, candidates=len(known))
-        log.info(f"motif_sites: ingest {TIMINGS['ingest_s']:.2f}s, engine {t_eng:.2f}s, text {TIMINGS['text_s']:.2f}s")
-    finally:
-        eng.close()
+        write_texts(args.out, (SUMMARY_NAME,), (format_summary(summary),))
+        finish("motif_sites", TIMINGS, t_eng, t_text + time.perf_counter() - t1, candidates=len(known))
     return 0

@@ -44,9 +44,10 @@ import numpy as np
 
 from . import fasta
 from .engine import HEMI, PAIRS, SITE_STATES, ScanEngine, partner_offset
+from .export_run import closing, finish, open_run, split_known, table_text, write_texts
 from .motif import MOD_TYPE_TO_CANONICAL, Motif, iupac_to_regex
 from .motif_compare import mcnemar_p
-from .motif_sites import SiteCandidate, candidates_of_files, open_run, table_text, write_site_batches
+from .motif_sites import SiteCandidate, candidates_of_files, write_site_batches
 
 MAIN_NAME = "motif-strands.tsv"
 CONTIGS_NAME = "motif-strands-contigs.tsv"
@@ -190,25 +191,16 @@ def run(args) -> int:
     eng, cands, status = open_run("motif_strands", args, TIMINGS)
     if eng is None:
         return status
-    try:
+    with closing(eng):
         files = [args.bin_motifs] if isinstance(args.bin_motifs, str) else list(args.bin_motifs)
-        known = []
-        for c in strand_candidates(cands, complement_partners(files)):
-            if c.bin not in eng.bin_index:
-                log.warning(f"{c!r}: the bin has no contig in the assembly; skipped")
-            elif c.mod_type not in eng.slot_of_mod:
-                log.warning(f"{c!r}: the pileup holds no rows of mod type {c.mod_type}; skipped")
-            else:
-                known.append(c)
+        known = split_known(strand_candidates(cands, complement_partners(files)), eng, eng.slot_of_mod)
         os.makedirs(args.out, exist_ok=True)
         t0 = time.perf_counter()
         res = eng.motif_strand_counts([c.engine_candidate() for c in known])
         t_eng = time.perf_counter() - t0
         t0 = time.perf_counter()
-        for name, text in ((MAIN_NAME, format_main(known, [t for _, t in res])),
-                           (CONTIGS_NAME, format_contigs(known, [n for n, _ in res], [t for _, t in res]))):
-            with open(os.path.join(args.out, name), "w") as f:
-                f.write(text)
+        tables = [t for _, t in res]
+        write_texts(args.out, (MAIN_NAME, CONTIGS_NAME), (format_main(known, tables), format_contigs(known, [n for n, _ in res], tables)))
         t_text = time.perf_counter() - t0
         n_records = 0
         if args.hemi_sites:
@@ -216,8 +208,5 @@ def run(args) -> int:
                 n_records, t_e, t_t = export_hemi(eng, known, pairs, f)
             t_eng += t_e
             t_text += t_t
-        TIMINGS.update(kernels_s=t_eng, text_s=t_text, candidates=len(known), hemi_records=n_records)
-        log.info(f"motif_strands: ingest {TIMINGS['ingest_s']:.2f}s, engine {t_eng:.2f}s, text {t_text:.2f}s")
-    finally:
-        eng.close()
+        finish("motif_strands", TIMINGS, t_eng, t_text, candidates=len(known), hemi_records=n_records)
     return 0

@@ -34,17 +34,14 @@ Files (tab-separated, header line; candidates in file order, contigs in bin orde
 """
 from __future__ import annotations
 
-import logging as log
 import os
 import time
 
 import numpy as np
 
 from . import fasta
-from .engine import TRACKS_MIN_WINDOW, track_window
-from .motif import MOD_TYPE_TO_CANONICAL, Motif
-from .motif_profile import frac_text
-from .motif_sites import open_run, table_text
+from .engine import TRACKS_MAX_WINDOW, TRACKS_MIN_WINDOW
+from .export_run import background_candidates, background_keys, closing, finish, frac_text, open_run, parse_int_in, split_known, table_text
 
 CONTIGS_NAME = "motif-tracks-contigs.tsv"
 SEGMENTS_NAME = "motif-tracks-segments.tsv"
@@ -61,10 +58,8 @@ TIMINGS = {}          # seconds per phase of the last run in this process (writt
 
 def parse_window(value) -> int:
     """``--window``: a multiple of 128 in [128, 2^30] (128 = one lane's span of a wave-chunk); ValueError otherwise."""
-    try:
-        return track_window(int(str(value).strip()))
-    except ValueError:
-        raise ValueError(f"--window takes a multiple of {TRACKS_MIN_WINDOW} in [{TRACKS_MIN_WINDOW}, 2^30]; got {value!r}") from None
+    return parse_int_in("--window", value, TRACKS_MIN_WINDOW, TRACKS_MAX_WINDOW, step=TRACKS_MIN_WINDOW,
+                        what=f"a multiple of {TRACKS_MIN_WINDOW} in [{TRACKS_MIN_WINDOW}, 2^30]")
 
 
 # ------------------------------------------------------------------------------------------------ segmentation
@@ -182,15 +177,6 @@ def format_files(cands, items, bg_tables, lengths, window: int, min_gain=30.0, m
     return table_text(CONTIGS_HEADER, rows[0]), table_text(SEGMENTS_HEADER, rows[1]), table_text(TRACKS_HEADER, rows[2]) if tracks else None
 
 
-def background_keys(cands) -> list:
-    """[(bin, mod type)] of the background candidates: per bin in order of first appearance, the mod types present among its candidates."""
-    keys = []
-    for c in cands:
-        if (c.bin, c.mod_type) not in keys:
-            keys.append((c.bin, c.mod_type))
-    return keys
-
-
 def _body(text: str) -> str:
     return text[text.index("\n") + 1:]
 
@@ -201,18 +187,13 @@ def run(args) -> int:
     eng, cands, status = open_run("motif_tracks", args, TIMINGS)
     if eng is None:
         return status
-    try:
-        known = [c for c in cands if c.bin in eng.bin_index and c.mod_type in eng.slot_of_mod]
-        for c in cands:
-            if c.bin not in eng.bin_index:
-                log.warning(f"{c!r}: the bin has no contig in the assembly; skipped")
-            elif c.mod_type not in eng.slot_of_mod:
-                log.warning(f"{c!r}: the pileup holds no rows of mod type {c.mod_type}; skipped")
+    with closing(eng):
+        known = split_known(cands, eng, eng.slot_of_mod)
         bg_keys = background_keys(known)
         lengths = {n: int(eng.contig_lengths[eng.contig_index[n]]) for b in {c.bin for c in known} for n in eng.bin_contigs(b)}
         os.makedirs(args.out, exist_ok=True)
         # the background's one-letter candidates ride in the same engine calls, ahead of the motifs that are read against them
-        batch = [(Motif(MOD_TYPE_TO_CANONICAL[mt], 0), mt, b) for b, mt in bg_keys] + [c.engine_candidate() for c in known]
+        batch = background_candidates(bg_keys) + [c.engine_candidate() for c in known]
         items = eng.motif_tracks(batch, window=window)
         t_eng = t_text = 0.0
         bg_tables = {}
@@ -238,8 +219,5 @@ def run(args) -> int:
         finally:
             for f in files:
                 f.close()
-        TIMINGS.update(kernels_s=t_eng, text_s=t_text, candidates=len(known), background_candidates=len(bg_keys), window=window)
-        log.info(f"motif_tracks: ingest {TIMINGS['ingest_s']:.2f}s, engine {t_eng:.2f}s, segmentation and text {t_text:.2f}s")
-    finally:
-        eng.close()
+        finish("motif_tracks", TIMINGS, t_eng, t_text, label="segmentation and text", candidates=len(known), background_candidates=len(bg_keys), window=window)
     return 0
