@@ -717,6 +717,48 @@ int nm_motif_pileup_text(uint64_t n_records, const uint32_t *site_contig, const 
                          const char *seg_text, const uint64_t *seg_text_off, uint32_t n_contigs, const char *contig_text,
                          const uint64_t *contig_text_off, char *out, uint64_t capacity, uint64_t *n_bytes);
 
+/* ---- PER-SITE READ-FRACTION CHANGE between two pileups: the join of two samples at every motif site -----------------------------------
+ * Reference: none (people run `modkit dmr pair` with a motif BED and join the result).  nm_motif_compare_* reads the thresholded state
+ * planes, so a motif that goes from 90 % to 45 % methylated is "mod > nocall" and one that goes from 60 % to 35 % never leaves "nocall >
+ * nocall"; nm_motif_fractions_count run twice gives the marginals of the joint table.  This pair joins two read-statistics slots per site.
+ *
+ * SAMPLES A and B are two read-statistics slots, cand_rs_slot_a[k] and cand_rs_slot_b[k]: any two slots that hold a pileup, the same slot
+ *   twice included (NM_MAX_MOD_SLOTS = 8 holds two pileups x three mod codes).
+ * CANDIDATES and OCCURRENCES are nm_motif_fractions_count's.  Per strand an occurrence is PAIRED (a kept record at the modified base in
+ *   both samples), ONLY_A, ONLY_B (a kept record in that sample only) or BARE (in neither).
+ * Per PAIRED site with records (vA, mA) and (vB, mB) = (n_valid_cov, n_modified), every value below 2^31 and v >= 1:
+ *   x = mB vA and y = mA vB in unsigned 64 bits, both exact and below 2^62.  Direction: UP if x > y (B's fraction is the higher), DOWN if
+ *   x < y, otherwise EQUAL (2 / 4 against 3 / 6 is equal).
+ *   Joint bin, n_bins = B (NM_SHIFT_MIN_BINS..NM_SHIFT_MAX_BINS): cell qa B + qb with q = min(B - 1, m B / v), nm_motif_fractions_count's rule.
+ *   SHIFTED at min_delta_permille = t (0..1000): x != y and 1000 |x - y| >= t vA vB, that is |mB / vB - mA / vA| >= t / 1000, evaluated
+ *   exactly for every admissible input (the two sides reach 2^72: 128-bit integers on the device past 2^54).  No floating point takes part.
+ * nm_motif_shift_count: rows = (candidate, contig of its bin) numbered as in nm_motif_fractions_count; counts = uint64[rows][2 (strand)]
+ *   [B B + NM_SHIFT_EXTRA]: the joint histogram over the paired sites, then occurrences, n_paired, n_only_a, n_only_b, sum_valid_a,
+ *   sum_mod_a, sum_valid_b, sum_mod_b (the four sums over the paired sites), n_up, n_down, n_shift_up, n_shift_down.  The caller's table
+ *   need not be zeroed.  Launches: at most 3.
+ * nm_motif_shift_sites: count + prefix + fill.  A record = a shifted paired site whose direction is in select (NM_SHIFT_UP |
+ *   NM_SHIFT_DOWN): (contig id, contig-local 0-based position of the modified base, code = (NM_SHIFT_MINUS on '-') | (NM_SHIFT_CODE_DOWN
+ *   for a site that goes down), vA, mA, vB, mB).  ORDER, cand_offset and windows exactly as in nm_motif_pileup_sites.
+ * Refusals, each before any device is touched, in the order of nm_motif_fractions_count with slot A checked before slot B: NM_EINVAL for
+ * NULLs, n_bins or min_delta_permille out of range, an empty select or bits above NM_SHIFT_DOWN, and a bad bin; NM_ESTATE without an
+ * assembly or for a slot without read statistics; NM_ERANGE as in nm_motif_fractions_count.  n_cand = 0 is NM_OK.  A refusal leaves the
+ * ctx usable. */
+#define NM_SHIFT_MIN_BINS 2
+#define NM_SHIFT_MAX_BINS 16
+#define NM_SHIFT_EXTRA 12
+#define NM_SHIFT_UP 1u              /* select: sites whose fraction is higher in B */
+#define NM_SHIFT_DOWN 2u            /* select: sites whose fraction is lower in B */
+#define NM_SHIFT_CODE_DOWN 1u       /* bit 0 of a record's code: the site goes down */
+#define NM_SHIFT_MINUS 4u           /* strand bit of a record's code */
+int nm_motif_shift_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_rs_slot_a, const uint8_t *cand_rs_slot_b,
+                         const uint8_t *cand_len, const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks,
+                         uint32_t n_bins, uint32_t min_delta_permille, uint64_t *counts);
+int nm_motif_shift_sites(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_rs_slot_a, const uint8_t *cand_rs_slot_b,
+                         const uint8_t *cand_len, const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks,
+                         uint32_t min_delta_permille, uint32_t select, uint64_t first_record, uint64_t capacity, uint32_t *site_contig,
+                         uint32_t *site_pos, uint8_t *site_code, uint32_t *site_valid_a, uint32_t *site_mod_a, uint32_t *site_valid_b,
+                         uint32_t *site_mod_b, uint64_t *cand_offset, uint64_t *n_written);
+
 /* ---- MOTIF METHYLATION BY LOCAL GC CONTENT: the sites of a motif counted apart by the G + C around them ------------------------------
  * Reference: none (its known-issues page names "high systematic 5mC noise in high GC% regions" and advises to check by hand).  A true
  * methyltransferase motif is methylated whatever its surroundings; a noise motif where the local GC is high, and then so is the bin's

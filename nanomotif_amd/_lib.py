@@ -33,6 +33,7 @@ SYMBOLS = [
     "nm_motif_pileup_count", "nm_motif_pileup_sites", "nm_motif_pileup_text",
     "nm_motif_gc_count",
     "nm_motif_overlap_count",
+    "nm_motif_shift_count", "nm_motif_shift_sites",
 ]
 
 class SearchParams(C.Structure):
@@ -175,7 +176,10 @@ def _load_locked():
                                           u64p, u64p]
     lib.nm_motif_pileup_text.argtypes = [C.c_uint64, u32p, u32p, u8p, u32p, u32p, C.c_uint32, u64p, C.c_char_p, u64p, C.c_uint32, C.c_char_p, u64p, p,
                                          C.c_uint64, u64p]
-    lib.nm_motif_gc_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, i64p]
+    lib.nm_motif_shift_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint32, u64p]
+    lib.nm_motif_shift_sites.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, u32p, u32p, u8p,
+                                         u32p, u32p, u32p, u32p, u64p, u64p]
+    lib.nm_motif_gc_count.argtypes =[p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, i64p]
     lib.nm_motif_overlap_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, u32p, u8p, u8p, u32p, u8p, u64p, i64p]
     lib.nm_motif_sites_text.argtypes = [C.c_uint64, u32p, u32p, u8p, C.c_uint32, u64p, C.c_char_p, u64p, C.c_uint32, C.c_char_p, u64p, p,
                                         C.c_uint64, u64p]

@@ -58,6 +58,7 @@ def create_parser():
     add_motif_tracks_parser(sub)
     add_motif_fractions_parser(sub)
     add_motif_pileup_parser(sub)
+    add_motif_shift_parser(sub)
     add_motif_context_parser(sub)
     add_motif_gc_parser(sub)
     add_motif_overlap_parser(sub)
@@ -346,3 +347,25 @@ def add_motif_pileup_parser(sub):
     o.add_argument("--all_occurrences", action="store_true",
                    help="Also write the occurrences whose modified base carries no kept pileup record (0, 0 and an empty percentage)")
     _close_export(p, o, "reads")
+
+
+def add_motif_shift_parser(sub):
+    """motif_shift: the per-site change of the read fraction n_modified / n_valid_cov between two pileups of one assembly at the sites of the
+    motifs of bin-motifs.tsv files (no counterpart on the reference's command line; `modkit dmr pair` with a motif BED and a join yield the
+    table).  Both pileups are read as READ STATISTICS, as motif_fractions reads its one."""
+    p, o = _open_export(sub, "motif_shift", "Reports how the read fractions at the motif sites of bin-motifs.tsv files change between two pileups",
+                        "Path(s) to the bin-motifs.tsv whose motif sites are read (motif_discovery's output)",
+                        pileups=(("pileup_a", "path to the modkit pileup file of sample A."),
+                                 ("pileup_b", "path to the modkit pileup file of sample B (same assembly).")))
+    o.add_argument("--bins", type=_checked("motif_shift", "parse_bins"), default=10, help="Bins per axis of the joint histogram, 2..16. Default: %(default)s")
+    o.add_argument("--min_delta", type=_checked("motif_shift", "parse_min_delta"), default=250,
+                   help="Difference of the two read fractions from which a site counts as shifted: 0..1 with at most three decimals. Default: 0.25")
+    o.add_argument("--shifted_sites", action="store_true", help="Also write shifted-sites.bed: the shifted sites (see --directions)")
+    o.add_argument("--directions", type=_selection("SHIFT_SELECT"), default=("up", "down"),
+                   help="Comma-separated directions A to B written to shifted-sites.bed: up, down. Default: up,down")
+    _close_export(p, o, "reads and zones", more=(
+        ("--min_sites", dict(type=int, default=20, help="Paired sites below which a row is flagged few_sites. Default: %(default)s")),
+        ("--min_share", dict(type=float, default=0.5, help="Share of the paired sites that must be shifted in one direction for gained / lost. "
+                                                           "Default: %(default)s")),
+        ("--minor_share", dict(type=float, default=0.1, help="Share of the paired sites shifted in each direction from which a motif is mixed. "
+                                                             "Default: %(default)s"))))

@@ -42,10 +42,13 @@ def parse_motif_mod(text: str):
 
 
 def upload_read_statistics(engine, mod_type, contig_local, position, strand, n_valid_cov, n_modified, n_diff=None,
-                           min_valid_read_coverage=3, min_valid_cov_to_diff_fraction=0.8) -> int:
+                           min_valid_read_coverage=3, min_valid_cov_to_diff_fraction=0.8, slot=None) -> int:
     """Records of ONE mod code -> the engine's read-statistics slot of that code (nm_readstats_upload).  ``contig_local``:
-    engine contig index per record, 0xFFFFFFFF for contigs the engine does not hold.  Returns the records kept."""
-    slot = MOD_CODES.index(mod_type)
+    engine contig index per record, 0xFFFFFFFF for contigs the engine does not hold.  ``slot``: another slot than the code's own
+    (a second pileup: ``engine.SHIFT_SLOT_B`` + the code's index, sample B of ``ScanEngine.motif_shift``); the code then does not
+    become resident for the single-sample calls.  Returns the records kept."""
+    own = MOD_CODES.index(mod_type)
+    slot = own if slot is None else int(slot)
     cid = np.ascontiguousarray(contig_local, dtype=np.uint32)
     pos = np.ascontiguousarray(position, dtype=np.uint32)
     st = np.ascontiguousarray(strand, dtype=np.uint8)
@@ -59,7 +62,8 @@ def upload_read_statistics(engine, mod_type, contig_local, position, strand, n_v
     kept = C.c_uint64(0)
     _lib.check(engine.lib.nm_readstats_upload(engine.ctx, slot, n, vp(cid), vp(pos), vp(st), vp(nv), vp(nm), vp(nd),
                                               int(min_valid_read_coverage), float(min_valid_cov_to_diff_fraction), 0, C.byref(kept)))
-    engine.readstats_mods.add(mod_type)
+    if slot == own:
+        engine.readstats_mods.add(mod_type)
     return int(kept.value)
 
 
@@ -172,10 +176,11 @@ def _check_mod_code(mt):
 
 
 def read_statistics_device(eng, lib, pileup, threads, local, wanted, allow_assembly_pileup_mismatch, min_valid_read_coverage,
-                           min_valid_cov_to_diff_fraction):
+                           min_valid_cov_to_diff_fraction, slot_base=0):
     """The pileup parsed on the device with its count columns -> one read-statistics slot per wanted mod code, straight from the
-    device columns (rows of the other codes are skipped in place).  ``local``: contig name -> engine contig index.  Returns
-    {mod code: records kept}."""
+    device columns (rows of the other codes are skipped in place).  ``local``: contig name -> engine contig index.  ``slot_base``: the
+    slot of a code is ``slot_base`` + its index in ``MOD_CODES`` (a second pileup: ``engine.SHIFT_SLOT_B``); only base 0 makes a code
+    resident for the single-sample calls.  Returns {mod code: records kept}."""
     h = C.c_void_p()
     n_kept = {}
     try:
@@ -191,11 +196,12 @@ def read_statistics_device(eng, lib, pileup, threads, local, wanted, allow_assem
         _lib.check(lib.nm_bedcols_map_contigs(h, lut.ctypes.data_as(C.POINTER(C.c_uint32)), len(lut)))
         for mt in sorted(wanted):
             _check_mod_code(mt)
-            slot = MOD_CODES.index(mt)            # (the parser's mod ids: 0 m, 1 a, 2 21839 — MOD_CODES' order)
+            mod_id = MOD_CODES.index(mt)          # (the parser's mod ids: 0 m, 1 a, 2 21839 — MOD_CODES' order; the slot moves, the id stays)
             kept = C.c_uint64(0)
-            _lib.check(lib.nm_readstats_upload_bedcols(eng.ctx, h, slot, slot, int(min_valid_read_coverage),
+            _lib.check(lib.nm_readstats_upload_bedcols(eng.ctx, h, int(slot_base) + mod_id, mod_id, int(min_valid_read_coverage),
                                                        float(min_valid_cov_to_diff_fraction), C.byref(kept)))
-            eng.readstats_mods.add(mt)
+            if not slot_base:
+                eng.readstats_mods.add(mt)
             n_kept[mt] = int(kept.value)
     finally:
         if h:
@@ -204,7 +210,7 @@ def read_statistics_device(eng, lib, pileup, threads, local, wanted, allow_assem
 
 
 def read_statistics_host(eng, lib, pileup, threads, local, wanted, allow_assembly_pileup_mismatch, min_valid_read_coverage,
-                         min_valid_cov_to_diff_fraction):
+                         min_valid_cov_to_diff_fraction, slot_base=0):
     """The same from the host reader's rows (nm_bed_open_counts), uploaded per mod code."""
     h = C.c_void_p()
     n_kept = {}
@@ -230,7 +236,8 @@ def read_statistics_host(eng, lib, pileup, threads, local, wanted, allow_assembl
             _check_mod_code(mt)
             sel = np.flatnonzero(mod == MOD_CODES.index(mt))
             n_kept[mt] = upload_read_statistics(eng, mt, lut[contig[sel]], position[sel], strand[sel], np.clip(nvalid[sel], -1, 2**31 - 1), nmod[sel],
-                                                ndiff[sel], min_valid_read_coverage, min_valid_cov_to_diff_fraction)
+                                                ndiff[sel], min_valid_read_coverage, min_valid_cov_to_diff_fraction,
+                                                slot=int(slot_base) + MOD_CODES.index(mt))
     finally:
         if h:
             lib.nm_bed_close(h)

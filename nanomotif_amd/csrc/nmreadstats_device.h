@@ -1,4 +1,4 @@
-// Device side of the read-statistics lookup (included by nmmeth.hip, nmfractions.hip and nmpileup.hip, the units that read a site's
+// Device side of the read-statistics lookup (included by nmmeth.hip, nmfractions.hip, nmpileup.hip and nmshift.hip, the units that read a site's
 // (n_valid_cov, n_modified) by rank): a mod code's presence plane says where kept records sit, the rank table counts the records of
 // the contig before every 512-bp block, and the records' values lie in plane (= position) order per strand — nothing is stored per
 // base pair.  One wave holds one chunk, a lane T_WORDS = 4 words of it, so a 16-word rank block is four consecutive lanes.

@@ -52,7 +52,19 @@ PILEUP_BARE = 1                                  # ... and NM_PILEUP_CODE_BARE: 
 PILEUP_RECORD_BYTES = 17                         # a record on the device: contig (4), position (4), code (1), n_valid_cov (4), n_modified (4)
 PILEUP_DTYPE = np.dtype([("candidate", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8), ("n_valid", np.uint32),
                          ("n_mod", np.uint32)])
-GC_MAX_HALF = 31                               # NM_GC_MAX_HALF: positions a GC window reaches either side of the modified base
+SHIFT_MIN_BINS, SHIFT_MAX_BINS = 2, 16            # NM_SHIFT_MIN_BINS / NM_SHIFT_MAX_BINS: bins per axis of the joint histogram of ScanEngine.motif_shift_counts
+SHIFT_EXTRA = 12                                 # NM_SHIFT_EXTRA: the sums behind a strand's joint histogram, in the order of SHIFT_SUMS
+SHIFT_SUMS = ("occurrences", "n_paired", "n_only_a", "n_only_b", "sum_valid_a", "sum_mod_a", "sum_valid_b", "sum_mod_b", "n_up", "n_down", "n_shift_up",
+              "n_shift_down")
+SHIFT_BUDGET_BYTES = 256 << 20                   # default size of the table of one library call of ScanEngine.motif_shift_counts
+SHIFT_SELECT = ("up", "down")                    # NM_SHIFT_UP / NM_SHIFT_DOWN: the read fraction is higher / lower in sample B
+SHIFT_MINUS = 4                                  # NM_SHIFT_MINUS: the strand bit of a record of nm_motif_shift_sites ...
+SHIFT_DOWN = 1                                   # ... and NM_SHIFT_CODE_DOWN: the site goes down
+SHIFT_RECORD_BYTES = 25                          # a record on the device: contig (4), position (4), code (1), n_valid / n_mod of A and of B (4 x 4)
+SHIFT_SLOT_B = 3                                 # read-statistics slot of sample B = SHIFT_SLOT_B + the mod code's index (loading: the second pileup's base)
+SHIFT_DTYPE = np.dtype([("candidate", np.uint32), ("contig", np.uint32), ("pos", np.uint32), ("code", np.uint8), ("n_valid_a", np.uint32),
+                        ("n_mod_a", np.uint32), ("n_valid_b", np.uint32), ("n_mod_b", np.uint32)])
+GC_MAX_HALF = 31                            # NM_GC_MAX_HALF: positions a GC window reaches either side of the modified base
 GC_BUDGET_BYTES = 256 << 20                    # default size of the table of one library call of ScanEngine.motif_gc
 OVERLAP_MAX_PARTNERS = 4095                    # NM_OVERLAP_MAX_PARTNERS: partner motifs of one candidate of ScanEngine.motif_overlap
 OVERLAP_ROW_BYTES = 48                         # one (block, contig) row of nm_motif_overlap_count: 2 strands x 3 states, int64
@@ -137,6 +149,26 @@ def pileup_select(select) -> int:
     if bits == 0:
         raise ValueError("no selection given")
     return bits
+
+
+def shift_select(select) -> int:
+    """("up", "down") -> NM_SHIFT_UP | NM_SHIFT_DOWN; ValueError for an unknown name or an empty selection."""
+    bits = 0
+    for s in select:
+        if s not in SHIFT_SELECT:
+            raise ValueError(f"unknown direction {s!r} (expected a selection of {SHIFT_SELECT})")
+        bits |= 1 << SHIFT_SELECT.index(s)
+    if bits == 0:
+        raise ValueError("no direction given")
+    return bits
+
+
+def shift_permille(min_delta_permille) -> int:
+    """The threshold of ``ScanEngine.motif_shift*`` as the library takes it: an integer in 0..1000, else ValueError."""
+    t = int(min_delta_permille)
+    if t != min_delta_permille or not 0 <= t <= 1000:
+        raise ValueError(f"min_delta_permille {min_delta_permille!r} is not an integer in 0..1000")
+    return t
 
 
 def transition_set(transitions) -> int:
@@ -1415,6 +1447,72 @@ class ScanEngine:
             return (self.ctx, *self._batch_args(sub), sel)
         windows = self._record_windows(self.lib.nm_motif_pileup_sites, group_args, totals, limit, PILEUP_DTYPE, "candidate", "batch", values=("n_valid", "n_mod"))
         yield from self._site_batches(windows, b, names, rows, table)
+
+    # ------------------------------------------------------------------ read-fraction change between two pileups (nm_motif_shift_*)
+    def _shift_slots(self, candidates: list, slot_b) -> np.ndarray:
+        """uint8 read-statistics slots of sample B.  ``slot_b``: None (``SHIFT_SLOT_B`` + the mod code's index: the second pileup of
+        ``upload_read_statistics(..., slot=)``), a base number (0: sample A against itself) or a callable from a mod type to a slot."""
+        from .contig_methylation import MOD_CODES
+        of = slot_b if callable(slot_b) else (lambda mt, base=SHIFT_SLOT_B if slot_b is None else int(slot_b): base + MOD_CODES.index(mt))
+        return np.fromiter((of(c[1]) for c in candidates), dtype=np.uint8, count=len(candidates))
+
+    def motif_shift_counts(self, candidates, bins=10, min_delta_permille=250, slot_b=None, max_bytes=None):
+        """Generator over the JOIN of two pileups at the sites of ``candidates`` (sequence of (Motif, mod_type, bin)),
+        nm_motif_shift_count: sample A is the read statistics of the candidate's mod code as ``motif_fractions`` reads them, sample B the
+        slot ``slot_b`` names (``_shift_slots``).  Yields one item per candidate, in call order: (the candidate, contig names in
+        ``bin_contigs`` order, uint64[n_contigs, 2, bins * bins + 12]) — per strand the joint histogram over the PAIRED sites (a kept
+        record in both samples; cell = bin in A * bins + bin in B, a bin as in ``motif_fractions``), then the twelve sums ``SHIFT_SUMS``.
+        A paired site goes up when n_mod_b / n_valid_b > n_mod_a / n_valid_a and is shifted when the two differ by at least
+        ``min_delta_permille`` / 1000, both decided in exact integers.  ``bins``: 2..16.  Consecutive candidates share one library call
+        while their table fits ``max_bytes`` (default ``SHIFT_BUDGET_BYTES``); what is yielded does not depend on it."""
+        bins = int(bins)
+        if not SHIFT_MIN_BINS <= bins <= SHIFT_MAX_BINS:
+            raise ValueError(f"bins {bins} outside {SHIFT_MIN_BINS}..{SHIFT_MAX_BINS}")
+        t = shift_permille(min_delta_permille)
+        limit = _byte_limit(max_bytes, SHIFT_BUDGET_BYTES)
+        candidates = list(candidates)
+        return self._shift_groups(candidates, self._readstats_batch(candidates), self._shift_slots(candidates, slot_b), bins, t, limit)
+
+    def _shift_groups(self, candidates, b: CandidateBatch, slots_b, nb: int, t: int, limit: int):
+        names = self._bin_names(b)
+        width = nb * nb + SHIFT_EXTRA
+
+        def call(k, e, sub, rows, table):                                 # (the library lays the rows out itself: no row prefix goes in)
+            _lib.check(self.lib.nm_motif_shift_count(self.ctx, *self._compare_args(sub, slots_b[k:e]), nb, t, _ptr(table, C.c_uint64)))
+        n_rows = [len(names[int(bid)]) for bid in b.bins]
+        for j, contigs, table in _table_groups(b, names, n_rows, 2 * width * 8, limit, (2, width), np.uint64, call):
+            yield candidates[j], contigs, table
+
+    def motif_shift(self, candidates, min_delta_permille=250, select=SHIFT_SELECT, max_records=None, slot_b=None):
+        """Generator over the SHIFTED paired sites of ``candidates`` whose direction is in ``select`` (a selection of "up", "down"),
+        nm_motif_shift_sites; samples, directions and the threshold as in ``motif_shift_counts``.  Yields ``SiteBatch`` objects in
+        candidate order; their ``records`` (fields candidate, contig, pos, code, n_valid_a, n_mod_a, n_valid_b, n_mod_b; code = 4 for the
+        '-' strand | 1 for a site that goes down) concatenated are the sites in the order candidate, contig (``bin_contigs`` order),
+        position, '+' before '-'; ``counts``: per candidate (contig names, uint64[n_contigs, 2, 12]), the sums ``SHIFT_SUMS``.  No batch
+        holds more than ``max_records`` records (default: ``SITE_BUDGET_BYTES`` of device records, 25 bytes each).  The concatenation
+        does not depend on ``max_records``."""
+        candidates = list(candidates)
+        b = self._readstats_batch(candidates)
+        slots_b = self._shift_slots(candidates, slot_b)
+        sel, t = shift_select(select), shift_permille(min_delta_permille)
+        limit = self._record_limit(max_records, SHIFT_RECORD_BYTES)
+        return self._shift_windows(candidates, b, slots_b, sel, t, limit)
+
+    def _shift_windows(self, candidates, b: CandidateBatch, slots_b, sel: int, t: int, limit: int):
+        # the candidates' totals under `sel` are sums of the count table: n_shift_up / n_shift_down over contigs and strands
+        nb = SHIFT_MIN_BINS
+        names, rows = self._site_rows(b)
+        sums = np.zeros((int(rows[-1]), 2, SHIFT_EXTRA), dtype=np.uint64)
+        for j, (_, _, table) in enumerate(self._shift_groups(candidates, b, slots_b, nb, t, SHIFT_BUDGET_BYTES)):
+            sums[int(rows[j]):int(rows[j + 1])] = table[:, :, nb * nb:]
+        wanted = [SHIFT_SUMS.index(n) for n, d in (("n_shift_up", 1), ("n_shift_down", 2)) if sel & d]
+        totals = np.array([int(sums[int(rows[j]):int(rows[j + 1])][:, :, wanted].sum()) for j in range(len(b))], dtype=np.uint64)
+
+        def group_args(k, e):
+            return (self.ctx, *self._compare_args(b.slice(k, e), slots_b[k:e]), t, sel)
+        windows = self._record_windows(self.lib.nm_motif_shift_sites, group_args, totals, limit, SHIFT_DTYPE, "candidate", "batch",
+                                       values=("n_valid_a", "n_mod_a", "n_valid_b", "n_mod_b"))
+        yield from self._site_batches(windows, b, names, rows, sums)
 
     # ------------------------------------------------------------------ motif methylation by local GC content (nm_motif_gc_count)
     def motif_gc(self, candidates, half=31, max_bytes=None):

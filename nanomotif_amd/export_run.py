@@ -97,12 +97,14 @@ def open_run(command: str, args, timings: dict, pileups=None, with_candidates=Tr
     return _open(command, args, timings, lambda cands, device: load_engine(args, device, pileups), with_candidates)
 
 
-def open_readstats_run(command: str, args, timings: dict):
-    """``open_run`` for the commands that read the READ STATISTICS (``loading.load_readstats_engine`` of the candidates' mod codes); a
-    contig listed under several bins is logged as an error of ``command`` and ends it with status 2."""
+def open_readstats_run(command: str, args, timings: dict, pileups=None):
+    """``open_run`` for the commands that read the READ STATISTICS (``loading.load_readstats_engine`` of the candidates' mod codes, with
+    ``pileups``: default the one of ``args.pileup``); a contig listed under several bins is logged as an error of ``command`` and ends it
+    with status 2."""
     from .contig_methylation import MOD_CODES
     return _open(command, args, timings,
-                 lambda cands, device: load_readstats_engine(args, device, sorted({c.mod_type for c in cands if c.mod_type in MOD_CODES})))
+                 lambda cands, device: load_readstats_engine(args, device, sorted({c.mod_type for c in cands if c.mod_type in MOD_CODES}),
+                                                            **({} if pileups is None else {"pileups": pileups})))
 
 
 # ------------------------------------------------------------------------------------------------ known and skipped

@@ -11,7 +11,7 @@ import time
 import numpy as np
 
 from . import _lib, fasta, pileup as pileup_mod
-from .engine import ScanEngine
+from .engine import SHIFT_SLOT_B, ScanEngine
 from .motif import MOD_TYPE_TO_CANONICAL
 
 
@@ -180,15 +180,17 @@ class AliasedContigs(ValueError):
     """A contig is listed under several bins where the command cannot serve that (``load_readstats_engine``)."""
 
 
-def load_readstats_engine(args, device: int, mod_types) -> ScanEngine:
+def load_readstats_engine(args, device: int, mod_types, pileups=None) -> ScanEngine:
     """Assembly and pileup of the command line -> an engine that holds the BINNED assembly exactly as ``load_engine`` puts it (same
     readers, the binned contigs the assembly holds, the run's bins) and the READ STATISTICS of ``mod_types`` (the mod codes wanted) in
     place of the state planes: every pileup record with ``n_valid_cov >= args.min_valid_read_coverage`` and ``n_valid_cov / (n_valid_cov
     + n_diff) >= args.min_valid_cov_to_diff_fraction`` keeps its (n_valid_cov, n_modified).  The pileup goes through
     ``contig_methylation.read_statistics_device`` (parsed on the device, one upload per mod code from the parser's columns), or
     ``read_statistics_host`` when the device parser declines or NANOMOTIF_HOST_PARSER=1; pileup contigs outside the bins are ignored.
-    ``eng.readstats_kept``: mod code -> records kept.  A contig listed under several bins would need its rows twice in one upload:
-    ``AliasedContigs`` names it before any device is touched."""
+    ``eng.readstats_kept``: mod code -> records kept.  ``pileups``: the paths to read, default the one of ``args.pileup``; a second path
+    (sample B of ``motif_shift``) goes to the slots from ``engine.SHIFT_SLOT_B`` on the same assembly and its records kept to
+    ``eng.readstats_kept_b``, ``eng.readstats_kept`` stays sample A's.  A contig listed under several bins would need its rows twice in one
+    upload: ``AliasedContigs`` names it before any device is touched."""
     from . import contig_methylation as cm
     bin_contig = fasta.generate_contig_bin(args)
     if not bin_contig:
@@ -210,19 +212,27 @@ def load_readstats_engine(args, device: int, mod_types) -> ScanEngine:
         local = {c: i for i, c in enumerate(names)}
         wanted = set(mod_types)
         filters = (int(args.min_valid_read_coverage), float(args.min_valid_cov_to_diff_fraction))
-        kept = None
-        if os.environ.get("NANOMOTIF_HOST_PARSER") != "1":
-            try:
-                kept = cm.read_statistics_device(eng, eng.lib, args.pileup, threads, local, wanted, True, *filters)
-                log.info("pileup: read statistics from the device parser's columns")
-            except _lib.NmScanError as e:
-                if e.code != _lib.NM_EDECLINED:
-                    raise
-                log.info(f"pileup: the device parser declined ({e}); using the host parser")
-        if kept is None:
-            kept = cm.read_statistics_host(eng, eng.lib, args.pileup, getattr(args, "threads", 1), local, wanted, True, *filters)
-            log.info("pileup: read statistics from the host parser's rows")
-        eng.readstats_kept = kept
+        paths = [args.pileup] if pileups is None else list(pileups)
+        if not 1 <= len(paths) <= 2:
+            raise ValueError("the read statistics hold one or two pileups")
+        both = []
+        for path, base in zip(paths, (0, SHIFT_SLOT_B)):
+            kept, more = None, ({"slot_base": base} if base else {})       # (the first pileup is read exactly as ever)
+            if os.environ.get("NANOMOTIF_HOST_PARSER") != "1":
+                try:
+                    kept = cm.read_statistics_device(eng, eng.lib, path, threads, local, wanted, True, *filters, **more)
+                    log.info("pileup: read statistics from the device parser's columns")
+                except _lib.NmScanError as e:
+                    if e.code != _lib.NM_EDECLINED:
+                        raise
+                    log.info(f"pileup: the device parser declined ({e}); using the host parser")
+            if kept is None:
+                kept = cm.read_statistics_host(eng, eng.lib, path, getattr(args, "threads", 1), local, wanted, True, *filters, **more)
+                log.info("pileup: read statistics from the host parser's rows")
+            both.append(kept)
+        eng.readstats_kept = both[0]
+        if len(both) == 2:
+            eng.readstats_kept_b = both[1]
         return eng
     except BaseException:
         eng.close()
