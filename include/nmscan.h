@@ -785,6 +785,57 @@ int nm_motif_gc_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, co
                       const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t half,
                       const uint64_t *cand_row0 /* [n_cand + 1] */, int64_t *counts);
 
+/* ---- MOTIF METHYLATION INSIDE ANNOTATED REGIONS: a user's intervals as class planes, the sites counted and exported against them ------
+ * Reference: none (people intersect motif-sites.bed with a prophage / gene / repeat annotation by `bedtools intersect` and group by hand).
+ *
+ * REGION SET (nm_regions): up to NM_REGION_MAX_CLASSES classes of intervals rasterised into bit planes in the chunk space of the RESIDENT
+ *   assembly, in a handle of its own (not in the ctx).  Interval i = positions [start[i], end[i]) of contig contig[i], 0-based, half-open,
+ *   class cls[i] < n_classes.  The intervals of one class are a union (overlapping, nested, identical, adjacent ones included); the
+ *   classes are independent.  Zero intervals is valid: every plane is empty.
+ *   nm_regions_create refuses, in this order: NULLs; n_classes 0 or above NM_REGION_MAX_CLASSES (NM_EINVAL); no assembly (NM_ESTATE);
+ *   then the FIRST interval in call order that is wrong, by contig >= n_contigs, cls >= n_classes, start >= end, end > the contig's
+ *   length (NM_EINVAL, the message names the interval's index).  The work runs on the ctx's stream and is complete on return.
+ *   NM_REGIONS_PIECE_WORDS=<n> in the environment (read at every call, clamped to 1..2048, the default) sets the plane words one wave
+ *   rasterises; the planes do not depend on it.
+ *   nm_regions_destroy never touches a ctx: it may come after nm_ctx_destroy.  A handle made before another assembly was uploaded is
+ *   refused by every call that takes (ctx, regions) with NM_ESTATE; it can still be read and destroyed.
+ *   nm_regions_shape: the classes, the contigs of the layout, the pieces the last rasterisation was cut into (any pointer may be NULL).
+ *   nm_regions_covered: bp = uint64[n_classes][n_contigs], the set positions per class and contig.
+ *   nm_regions_plane: the ceil(length / 32) words of one contig of one plane; position p is bit p % 32 of word p / 32.
+ *   nm_regions_chunk_classes: per chunk of 8192 positions of ONE contig (ceil(length / 8192) of them, returned in *n_chunks) one byte, the
+ *     classes with a position in the chunk; classes == NULL asks for *n_chunks alone, a capacity below it is NM_ERANGE.
+ * CANDIDATES, OCCURRENCES and their STATE (mod / nomod / nocall) are nm_motif_sites_count's.  A site is INSIDE class c when the position
+ *   of its MODIFIED BASE is set in plane c — the motif's span does not matter — and OUTSIDE when it is inside none of the set's classes.
+ * nm_motif_regions_count: rows = (candidate, contig of its bin) from cand_row0 as in nm_motif_gc_count; counts = int64[rows]
+ *   [n_classes + 1][2 (occurrence strand)][3 (mod, nomod, nocall)], cell n_classes = outside.  A site inside several classes is counted
+ *   in each.  The caller's table need not be zeroed.  cand_total (may be NULL) = the records nm_motif_regions_sites delivers per
+ *   candidate under (state_set, class_set, want_outside).  Launches: at most 3 (+ 2 with cand_total).
+ * nm_motif_regions_sites: count + prefix + fill.  A record = an occurrence whose state is in state_set and that is inside at least one
+ *   class of class_set (bit c = class c) or, with want_outside, outside: nm_motif_sites' three columns with its code, and site_classes =
+ *   the mask of ALL classes of the set the site is inside (0 for an outside record), whatever class_set says.  ORDER, cand_offset and
+ *   windows exactly as in nm_motif_sites.
+ * Refusals of the two, each before any device is touched, in this order: NULLs; regions NULL (NM_ESTATE: no region set); state_set empty or above 7; class_set with a bit at or
+ *   above n_classes, or empty without want_outside (NM_EINVAL); no assembly; a region set of another assembly (NM_ESTATE); then per
+ *   candidate as in nm_motif_sites_count (bin, slot, program, rows, work items).  n_cand = 0 is NM_OK.  A refusal leaves the ctx usable. */
+#define NM_REGION_MAX_CLASSES 8
+typedef struct nm_regions nm_regions;
+int nm_regions_create(nm_ctx *ctx, uint64_t n_intervals, const uint32_t *contig, const uint64_t *start, const uint64_t *end, const uint8_t *cls,
+                      uint32_t n_classes, nm_regions **out);
+int nm_regions_destroy(nm_regions *regions);
+int nm_regions_shape(const nm_regions *regions, uint32_t *n_classes, uint32_t *n_contigs, uint64_t *n_pieces);
+int nm_regions_covered(const nm_regions *regions, uint64_t *bp);
+int nm_regions_plane(const nm_regions *regions, uint32_t cls, uint32_t contig, uint32_t *words);
+int nm_regions_chunk_classes(const nm_regions *regions, uint32_t contig, uint8_t *classes, uint32_t capacity, uint32_t *n_chunks);
+int nm_motif_regions_count(nm_ctx *ctx, const nm_regions *regions, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot,
+                           const uint8_t *cand_len, const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks,
+                           uint32_t state_set, uint32_t class_set, int want_outside, const uint64_t *cand_row0 /* [n_cand + 1] */,
+                           uint64_t *cand_total, int64_t *counts);
+int nm_motif_regions_sites(nm_ctx *ctx, const nm_regions *regions, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot,
+                           const uint8_t *cand_len, const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks,
+                           uint32_t state_set, uint32_t class_set, int want_outside, uint64_t first_record, uint64_t capacity,
+                           uint32_t *site_contig, uint32_t *site_pos, uint8_t *site_code, uint8_t *site_classes, uint64_t *cand_offset,
+                           uint64_t *n_written);
+
 /* ---- MOTIF OVERLAP: the sites a motif shares with other motifs of its bin, and the sites it has alone ------------------------------
  * Reference: none on sites (remove_sub_motifs / merge_motifs of postprocess.py settle nesting by the motifs' spelling).  What decides
  * whether a parent motif or its child is the real one is the methylation of the parent OUTSIDE the child: a set difference on the

@@ -34,6 +34,8 @@ SYMBOLS = [
     "nm_motif_gc_count",
     "nm_motif_overlap_count",
     "nm_motif_shift_count", "nm_motif_shift_sites",
+    "nm_regions_create", "nm_regions_destroy", "nm_regions_shape", "nm_regions_covered", "nm_regions_plane", "nm_regions_chunk_classes",
+    "nm_motif_regions_count", "nm_motif_regions_sites",
 ]
 
 class SearchParams(C.Structure):
@@ -181,6 +183,15 @@ def _load_locked():
                                          u32p, u32p, u32p, u32p, u64p, u64p]
     lib.nm_motif_gc_count.argtypes =[p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, u64p, i64p]
     lib.nm_motif_overlap_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, u32p, u8p, u8p, u32p, u8p, u64p, i64p]
+    lib.nm_regions_create.argtypes = [p, C.c_uint64, u32p, u64p, u64p, u8p, C.c_uint32, C.POINTER(p)]
+    lib.nm_regions_destroy.argtypes = [p]
+    lib.nm_regions_shape.argtypes = [p, u32p, u32p, u64p]
+    lib.nm_regions_covered.argtypes = [p, u64p]
+    lib.nm_regions_plane.argtypes = [p, C.c_uint32, C.c_uint32, u32p]
+    lib.nm_regions_chunk_classes.argtypes = [p, C.c_uint32, u8p, C.c_uint32, u32p]
+    lib.nm_motif_regions_count.argtypes = [p, p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint32, C.c_int, u64p, u64p, i64p]
+    lib.nm_motif_regions_sites.argtypes = [p, p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, u32p, u32p,
+                                           u8p, u8p, u64p, u64p]
     lib.nm_motif_sites_text.argtypes = [C.c_uint64, u32p, u32p, u8p, C.c_uint32, u64p, C.c_char_p, u64p, C.c_uint32, C.c_char_p, u64p, p,
                                         C.c_uint64, u64p]
     lib.nm_readstats_upload.argtypes = [p, C.c_uint32, C.c_uint64, p, p, p, p, p, p, C.c_int32, C.c_double, C.c_int, u64p]

@@ -1,6 +1,6 @@
 """Command line of the MI355X build: the ``motif_discovery`` sub-command with the reference's arguments
 (nanomotif/argparser.py:13-136), plus ``--device`` for the GPU to use, the project's own ``motif_sites`` / ``motif_coverage`` /
-``motif_compare`` / ``motif_strands`` / ``motif_profile`` / ``motif_tracks`` / ``motif_fractions`` / ``motif_pileup`` / ``motif_context`` / ``motif_gc`` / ``motif_overlap`` on a finished ``bin-motifs.tsv``, ``motif_kmers`` (which needs none), and the binnary sub-commands ``detect_contamination`` and
+``motif_compare`` / ``motif_strands`` / ``motif_profile`` / ``motif_tracks`` / ``motif_fractions`` / ``motif_pileup`` / ``motif_shift`` / ``motif_context`` / ``motif_gc`` / ``motif_overlap`` / ``motif_regions`` on a finished ``bin-motifs.tsv``, ``motif_kmers`` (which needs none), and the binnary sub-commands ``detect_contamination`` and
 ``include_contigs`` with the reference's flags (argparser.py:139-236).  MTase-linker is out of scope."""
 import argparse
 
@@ -13,7 +13,7 @@ def create_parser():
                                      formatter_class=formatter)
     parser.add_argument("--version", action="version", version="%(prog)s {}".format(__version__))
     sub = parser.add_subparsers(help="-- Command descriptions --", dest="command", title="commands",
-                                metavar="{motif_discovery, motif_sites, motif_coverage, motif_compare, motif_strands, motif_profile, motif_tracks, motif_fractions, motif_pileup, motif_context, motif_gc, motif_overlap, motif_kmers, detect_contamination, include_contigs, check_installation}")
+                                metavar="{motif_discovery, motif_sites, motif_coverage, motif_compare, motif_strands, motif_profile, motif_tracks, motif_fractions, motif_pileup, motif_shift, motif_context, motif_gc, motif_overlap, motif_regions, motif_kmers, detect_contamination, include_contigs, check_installation}")
     p = sub.add_parser("motif_discovery", help="Finds motifs directly on bin level in provided assembly", add_help=False)
     p.add_argument("assembly", type=str, help="path to the assembly file.")
     p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
@@ -62,6 +62,7 @@ def create_parser():
     add_motif_context_parser(sub)
     add_motif_gc_parser(sub)
     add_motif_overlap_parser(sub)
+    add_motif_regions_parser(sub)
     add_motif_kmers_parser(sub)
     add_binnary_parsers(sub)
     sub.add_parser("check_installation", help="Run motif_discovery on a small synthetic data set", add_help=True)
@@ -290,6 +291,31 @@ def add_motif_overlap_parser(sub):
                    help="Fraction of methylation outside its children up to which a motif can be flagged carried_by_children. Default: %(default)s")
     o.add_argument("--min_frac", type=float, default=0.7,
                    help="Fraction of methylation from which a part of a motif counts as methylated (carried_by_children, submotif). Default: %(default)s")
+    _close_export(p, o)
+
+
+def add_motif_regions_parser(sub):
+    """motif_regions: the methylation of the motifs of bin-motifs.tsv files inside the classes of a BED / GFF3 annotation — prophages,
+    genes and what lies in front of them, repeat masks — beside the bin's background (no counterpart on the reference's command line;
+    people intersect motif-sites.bed with bedtools and group by hand)."""
+    p, o = _open_export(sub, "motif_regions", "Reports the methylation of the motifs of bin-motifs.tsv files inside the regions of an annotation",
+                        "Path(s) to the bin-motifs.tsv whose motif sites are read (motif_discovery's output)")
+    o.add_argument("--regions", type=str, required=True, metavar="FILE",
+                   help="BED or GFF3 file of annotated regions, plain or .gz. The class of an interval is BED column 4 (without it: region) / GFF3 column 3")
+    o.add_argument("--classes", type=_checked("regions", "parse_classes"), default=None,
+                   help="Comma-separated classes to read, in this order (at most 8). Default: every class, in order of first appearance")
+    o.add_argument("--upstream", type=_checked("regions", "parse_upstream"), default=0,
+                   help="Adds the class upstream: this many bases in front of every stranded interval. Default: %(default)s (off)")
+    o.add_argument("--min_called", type=int, default=20, help="Called sites a class and the rest need for a motif to be judged. Default: %(default)s")
+    o.add_argument("--min_z", type=float, default=5.0, help="|z| from which a motif can be flagged depleted / enriched in a class. Default: %(default)s")
+    o.add_argument("--min_delta", type=float, default=0.2,
+                   help="|frac_mod in the class - frac_mod of the rest| from which a motif can be flagged depleted / enriched. Default: %(default)s")
+    o.add_argument("--region_sites", action="store_true", help="Also write region-sites.bed: the selected sites with the classes they are inside")
+    o.add_argument("--states", type=_selection("SITE_STATES"), default=("mod", "nomod", "nocall"),
+                   help="Comma-separated states of the sites of region-sites.bed: mod, nomod, nocall. Default: all three")
+    o.add_argument("--inside", type=_checked("motif_regions", "parse_inside"), default=None,
+                   help="Comma-separated classes (and / or outside) whose sites go to region-sites.bed. Default: every class")
+    o.add_argument("--intervals", action="store_true", help="Also write motif-regions-intervals.tsv: the six counts per interval and motif")
     _close_export(p, o)
 
 

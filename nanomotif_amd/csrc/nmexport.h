@@ -1,4 +1,4 @@
-// The scaffold the twelve export units share; included by them and by nothing else.  Each hands out one wave per work item = (owner,
+// The scaffold the thirteen export units share; included by them and by nothing else.  Each hands out one wave per work item = (owner,
 // chunk of the owner's bin) — an owner is a candidate, in nmcoverage.hip a set of candidates — and runs up to three steps:
 //   count  the unit's kernel writes the number of records of every work item into the item table (and its own count tables)
 //   scan   one device-wide exclusive prefix (rocPRIM) over the work items, which are numbered in (owner, contig rank, chunk)
@@ -8,8 +8,8 @@
 // Owners of different width (word-groups G = 1, 2, 3 either side of the modified base) run in one launch per width and pass: at
 // most 3 + 1 + 1 + 3 launches whatever a call holds.
 //   all three steps (records): nmsites.hip, nmcoverage.hip, nmcompare.hip, nmstrands.hip — export_begin(with_scan) + export_window;
-//                              nmpileup.hip and nmshift.hip, whose records carry two / four gathered columns more, with a window half and a
-//                              fill loop of their own
+//                              nmpileup.hip, nmshift.hip and nmregions.hip, whose records carry two / four gathered columns / one class byte more,
+//                              with a window half and a fill loop of their own
 //   the count step only (tables): nmprofile.hip, nmtracks.hip, nmfractions.hip, nmcontext.hip, nmgc.hip, nmoverlap.hip — export_begin alone
 // Two more pieces belong to every unit and are owned by none:
 //   stage_candidates  the host loop over a call's candidates: programs, widths, the work-item count and, on request, the state-plane

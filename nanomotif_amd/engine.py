@@ -66,6 +66,11 @@ SHIFT_DTYPE = np.dtype([("candidate", np.uint32), ("contig", np.uint32), ("pos",
                         ("n_mod_a", np.uint32), ("n_valid_b", np.uint32), ("n_mod_b", np.uint32)])
 GC_MAX_HALF = 31                            # NM_GC_MAX_HALF: positions a GC window reaches either side of the modified base
 GC_BUDGET_BYTES = 256 << 20                    # default size of the table of one library call of ScanEngine.motif_gc
+REGION_MAX_CLASSES = 8                         # NM_REGION_MAX_CLASSES: one byte of class mask per record and per chunk
+REGIONS_BUDGET_BYTES = 256 << 20               # default size of the table of one library call of ScanEngine.motif_regions_counts
+REGION_RECORD_BYTES = 10                       # a record on the device: contig (4), position (4), code (1), classes (1)
+REGION_DTYPE = np.dtype(SITE_DTYPE.descr + [("classes", np.uint8)])
+REGION_OUTSIDE = "outside"                     # the cell behind the classes, and its name in a selection
 OVERLAP_MAX_PARTNERS = 4095                    # NM_OVERLAP_MAX_PARTNERS: partner motifs of one candidate of ScanEngine.motif_overlap
 OVERLAP_ROW_BYTES = 48                         # one (block, contig) row of nm_motif_overlap_count: 2 strands x 3 states, int64
 OVERLAP_BUDGET_BYTES = 256 << 20               # default size of the table of one library call of ScanEngine.motif_overlap
@@ -137,6 +142,20 @@ def site_state_set(states) -> int:
     if bad or not states:
         raise ValueError(f"states must be a non-empty selection of {SITE_STATES}, got {states!r}")
     return sum(1 << SITE_STATES.index(s) for s in set(states))
+
+
+def region_class_set(names, selection) -> tuple:
+    """(class_set, want_outside) of nm_motif_regions_sites for ``selection``, a sequence of class names of ``names`` (the uploaded
+    classes in order) and / or "outside"; None selects every class and not the outside.  ValueError for an unknown name and for an empty
+    selection."""
+    names = list(names)
+    if selection is None:
+        return (1 << len(names)) - 1, False
+    selection = [selection] if isinstance(selection, str) else list(selection)
+    unknown = [s for s in selection if s != REGION_OUTSIDE and s not in names]
+    if unknown or not selection:
+        raise ValueError(f"classes: a non-empty selection of {', '.join(names + [REGION_OUTSIDE])} is expected, got {selection!r}")
+    return sum(1 << names.index(s) for s in set(selection) if s != REGION_OUTSIDE), REGION_OUTSIDE in selection
 
 
 def pileup_select(select) -> int:
@@ -649,8 +668,11 @@ class ScanEngine:
         self.slot_of_mod = {}
         self.readstats_mods = set()      # mod codes whose read statistics are resident (contig_methylation.upload_read_statistics)
         self.comm_world = 0
+        self.regions = C.c_void_p()      # nm_regions * of ``upload_regions``, bound to the resident assembly
+        self.region_classes = []
 
     def close(self):
+        self.clear_regions()
         if self.ctx:
             self.lib.nm_ctx_destroy(self.ctx)
             self.ctx = C.c_void_p()
@@ -691,6 +713,7 @@ class ScanEngine:
         self.bin_names = sorted(set(bin_of_contig)) if bin_names is None else list(bin_names)
         self.bin_index = {b: i for i, b in enumerate(self.bin_names)}
         bin_ids = np.array([self.bin_index[b] for b in bin_of_contig], dtype=np.uint32) if names else np.zeros(1, np.uint32)
+        self.clear_regions()                   # the planes of a region set are laid out for the assembly they were made on
         _lib.check(self.lib.nm_upload_contigs(self.ctx, len(names), _ptr(offsets, C.c_uint64), _ptr(bin_ids, C.c_uint32),
                                               len(self.bin_names), _ptr(ascii_all, C.c_uint8)))
         self.contig_names = names
@@ -711,6 +734,7 @@ class ScanEngine:
         self.bin_names = sorted(set(bin_of_contig)) if bin_names is None else list(bin_names)
         self.bin_index = {b: i for i, b in enumerate(self.bin_names)}
         bin_ids = np.array([self.bin_index[b] for b in bin_of_contig], dtype=np.uint32)
+        self.clear_regions()                   # the planes of a region set are laid out for the assembly they were made on
         _lib.check(self.lib.nm_upload_contigs_device(self.ctx, len(names), _ptr(offsets, C.c_uint64), _ptr(bin_ids, C.c_uint32),
                                                      len(self.bin_names), C.c_void_p(int(device_ptr))))
         self.contig_names = names
@@ -728,6 +752,7 @@ class ScanEngine:
         self.bin_names = sorted(set(bin_of_contig)) if bin_names is None else list(bin_names)
         self.bin_index = {b: i for i, b in enumerate(self.bin_names)}
         bin_ids = np.array([self.bin_index[b] for b in bin_of_contig], dtype=np.uint32)
+        self.clear_regions()                   # the planes of a region set are laid out for the assembly they were made on
         _lib.check(self.lib.nm_upload_contigs_fasta(self.ctx, assembly._h, len(names), _ptr(records, C.c_uint32), _ptr(bin_ids, C.c_uint32),
                                                     len(self.bin_names)))
         self.contig_names = names
@@ -1070,9 +1095,11 @@ class ScanEngine:
         ``limit``, and every group is fetched in windows of at most ``limit`` records — one, unless a single owner exceeds the limit.
         ``call``: the library's *_sites function; ``group_args(k, e)``: its arguments before first_record for the owners [k, e);
         ``dtype``: the records' type, whose ``owner`` field is filled in here; ``unit``: what the library's message calls a group;
-        ``values``: the uint32 fields of ``dtype`` the call writes after the code (nm_motif_pileup_sites: n_valid, n_mod).
+        ``values``: the fields of ``dtype`` the call writes after the code, in the call's order — a name (a uint32 column;
+        nm_motif_pileup_sites: n_valid, n_mod) or (name, numpy type) (nm_motif_regions_sites: the class byte).
         The ctypes pointers of those arguments keep their arrays alive.  Yields (k, e, first_record, records of the group, the window's
         records)."""
+        columns = [(v, np.uint32) if isinstance(v, str) else v for v in values]
         for k, e, held in _budget_groups(totals, limit):
             args = group_args(k, e)
             first = 0
@@ -1080,15 +1107,15 @@ class ScanEngine:
                 cap = min(limit, held - first) if held else 0
                 rec = np.zeros(cap, dtype=dtype)
                 contig, pos, code = (np.zeros(max(cap, 1), dtype=t) for t in (np.uint32, np.uint32, np.uint8))
-                more = [np.zeros(max(cap, 1), dtype=np.uint32) for _ in values]
+                more = [np.zeros(max(cap, 1), dtype=t) for _, t in columns]
                 off = np.zeros(e - k + 1, dtype=np.uint64)
                 written = C.c_uint64(0)
                 _lib.check(call(*args, first, cap, _ptr(contig, C.c_uint32), _ptr(pos, C.c_uint32), _ptr(code, C.c_uint8),
-                                *(_ptr(m, C.c_uint32) for m in more), _ptr(off, C.c_uint64), C.byref(written)))
+                                *(_ptr(m, np.ctypeslib.as_ctypes_type(m.dtype)) for m in more), _ptr(off, C.c_uint64), C.byref(written)))
                 if int(off[-1]) != held or written.value != cap:
                     raise _lib.NmScanError(f"{call.__name__} delivered {written.value} of {cap} records ({int(off[-1])} in the {unit}, {held} counted)")
                 rec["contig"], rec["pos"], rec["code"] = contig[:cap], pos[:cap], code[:cap]
-                for name, m in zip(values, more):
+                for (name, _), m in zip(columns, more):
                     rec[name] = m[:cap]
                 # the owner of every record of the window: the prefix of the group, cut to [first, first + cap)
                 cut = np.clip(off.astype(np.int64) - first, 0, cap)
@@ -1539,6 +1566,98 @@ class ScanEngine:
         n_rows = [len(names[int(bid)]) for bid in b.bins]
         for _, contigs, table in _table_groups(b, names, n_rows, 6 * width * 8, limit, (2, 3, width), np.int64, call):
             yield contigs, table
+
+    # ------------------------------------------------------------------ motif methylation inside annotated regions (nm_regions_*, nm_motif_regions_*)
+    def upload_regions(self, contig_ids, starts, ends, classes, class_names):
+        """Intervals [starts[i], ends[i]) (0-based, half-open) of contig ``contig_ids[i]``, class ``classes[i]`` = index into
+        ``class_names`` (1..8 names), rasterised into class planes on the resident assembly (nm_regions_create).  The intervals of a
+        class are a union; a class may have none.  Replaces a previous set; ``close`` and every ``upload_assembly*`` drop it."""
+        class_names = list(class_names)
+        cid, st, en, cl = (np.ascontiguousarray(a, dtype=t) for a, t in ((contig_ids, np.uint32), (starts, np.uint64), (ends, np.uint64), (classes, np.uint8)))
+        if not len(cid) == len(st) == len(en) == len(cl):
+            raise ValueError("contig_ids, starts, ends and classes differ in length")
+        h = C.c_void_p()
+        _lib.check(self.lib.nm_regions_create(self.ctx, len(cid), _ptr(cid, C.c_uint32), _ptr(st, C.c_uint64), _ptr(en, C.c_uint64), _ptr(cl, C.c_uint8),
+                                              len(class_names), C.byref(h)))
+        self.clear_regions()
+        self.regions, self.region_classes = h, class_names
+
+    def clear_regions(self):
+        """Drop the region set (nm_regions_destroy); nothing happens without one."""
+        if getattr(self, "regions", None):
+            self.lib.nm_regions_destroy(self.regions)
+        self.regions, self.region_classes = C.c_void_p(), []
+
+    def region_covered(self) -> np.ndarray:
+        """int64[n_classes, n_contigs]: the positions of every contig inside every class (nm_regions_covered)."""
+        out = np.zeros((max(len(self.region_classes), 1), max(len(self.contig_names), 1)), dtype=np.uint64)
+        _lib.check(self.lib.nm_regions_covered(self.regions, _ptr(out, C.c_uint64)))
+        return out[:len(self.region_classes), :len(self.contig_names)].astype(np.int64)
+
+    def region_mask(self, contig, cls) -> np.ndarray:
+        """bool[L]: the positions of ``contig`` (name or id) inside class ``cls`` (name or index), read back from the plane."""
+        i = self.contig_index[contig] if isinstance(contig, str) else int(contig)
+        c = self.region_classes.index(cls) if isinstance(cls, str) else int(cls)
+        length = int(self.contig_lengths[i])
+        words = np.zeros(max((length + 31) // 32, 1), dtype=np.uint32)
+        _lib.check(self.lib.nm_regions_plane(self.regions, c, i, _ptr(words, C.c_uint32)))
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:length].astype(bool)
+
+    def region_chunk_classes(self, contig) -> np.ndarray:
+        """uint8 per chunk of 8192 positions of ``contig`` (name or id): the classes with a position in the chunk, as the count pass
+        reads them (nm_regions_chunk_classes; the library says how many chunks there are)."""
+        i = self.contig_index[contig] if isinstance(contig, str) else int(contig)
+        n = C.c_uint32(0)
+        _lib.check(self.lib.nm_regions_chunk_classes(self.regions, i, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        _lib.check(self.lib.nm_regions_chunk_classes(self.regions, i, _ptr(out, C.c_uint8), n.value, C.byref(n)))
+        return out[:n.value]
+
+    def motif_regions_counts(self, candidates, max_bytes=None):
+        """Generator over the sites of ``candidates`` (sequence of (Motif, mod_type, bin), or a CandidateBatch with slots from
+        ``slot_of_mod``) counted per class of the uploaded region set (nm_motif_regions_count).  A site is an occurrence of
+        ``motif_site_counts`` with its state; it is inside a class when its MODIFIED BASE lies in an interval of the class, and outside
+        when it is inside none.  Yields one item per candidate, in call order: (contig names in ``bin_contigs`` order,
+        int64[n_contigs, K + 1, 2 (occurrence strand), 3 (mod, nomod, nocall)]), K = the uploaded classes, cell K = outside.  A site
+        inside several classes is counted in each.  Consecutive candidates share one library call while their tables fit ``max_bytes``
+        (default ``REGIONS_BUDGET_BYTES``); what is yielded does not depend on it."""
+        limit = _byte_limit(max_bytes, REGIONS_BUDGET_BYTES)
+        return self._regions_groups(self._as_batch(candidates), limit)
+
+    def _regions_groups(self, b: CandidateBatch, limit: int):
+        names = self._bin_names(b)
+        cells = len(self.region_classes) + 1
+
+        def call(k, e, sub, rows, table):
+            _lib.check(self.lib.nm_motif_regions_count(self.ctx, self.regions, *self._batch_args(sub), 7, 0, 1, _ptr(rows, C.c_uint64), None, _ptr(table, C.c_int64)))
+        n_rows = [len(names[int(bid)]) for bid in b.bins]
+        for _, contigs, table in _table_groups(b, names, n_rows, cells * 48, limit, (cells, 2, 3), np.int64, call):
+            yield contigs, table
+
+    def motif_regions_sites(self, candidates, states=SITE_STATES, classes=None, outside=False, max_records=None):
+        """Generator over the sites of ``candidates`` inside the uploaded regions (nm_motif_regions_sites): the occurrences whose state
+        is in ``states`` and that are inside at least one class of ``classes`` (names, default every class; "outside" among them, or
+        ``outside`` True, adds the sites outside every uploaded class).  Yields ``SiteBatch`` objects in candidate order; their
+        ``records`` (``REGION_DTYPE``: ``motif_sites``' fields and ``classes``, the mask of ALL uploaded classes the site is inside, 0 for
+        an outside site) concatenated are the sites in ``motif_sites``' order; ``counts`` as ``motif_regions_counts`` yields them.  No
+        batch holds more than ``max_records`` records; the concatenation does not depend on it."""
+        b = self._as_batch(candidates)
+        state_set = site_state_set(states)
+        class_set, want = region_class_set(self.region_classes, classes)
+        want = int(bool(want or outside))
+        limit = self._record_limit(max_records, REGION_RECORD_BYTES)
+        names, rows = self._site_rows(b)
+        cells = len(self.region_classes) + 1
+        table = np.zeros((max(int(rows[-1]), 1), cells, 2, 3), dtype=np.int64)
+        totals = np.zeros(max(len(b), 1), dtype=np.uint64)
+        _lib.check(self.lib.nm_motif_regions_count(self.ctx, self.regions, *self._batch_args(b), state_set, class_set, want, _ptr(rows, C.c_uint64),
+                                                   _ptr(totals, C.c_uint64), _ptr(table, C.c_int64)))
+
+        def group_args(k, e):
+            return (self.ctx, self.regions, *self._batch_args(b.slice(k, e)), state_set, class_set, want)
+        windows = self._record_windows(self.lib.nm_motif_regions_sites, group_args, totals[:len(b)], limit, REGION_DTYPE, "candidate", "batch",
+                                       values=(("classes", np.uint8),))
+        yield from self._site_batches(windows, b, names, rows, table[:int(rows[-1])])
 
     # ------------------------------------------------------------------ shared sites of a motif and its partners (nm_motif_overlap_count)
     def motif_overlap(self, candidates, partners, max_bytes=None):
