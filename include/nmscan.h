@@ -836,6 +836,40 @@ int nm_motif_regions_sites(nm_ctx *ctx, const nm_regions *regions, uint32_t n_ca
                            uint32_t *site_contig, uint32_t *site_pos, uint8_t *site_code, uint8_t *site_classes, uint64_t *cand_offset,
                            uint64_t *n_written);
 
+/* ---- RUNS OF SAME-STATE MOTIF SITES: the ORDER of a motif's sites along a contig ---------------------------------------------------
+ * Reference: none (people export motif-sites.bed twice and group consecutive rows on the host).  A protein that sits on the DNA leaves a
+ * footprint of consecutive unmethylated sites; a caller with a strand bias makes the states of a palindrome alternate.
+ *
+ * CANDIDATES, OCCURRENCES and their STATE (mod / nomod / nocall) are nm_motif_sites_count's.  On one contig the occurrences of both
+ *   strands are taken by ascending position of the modified base (a position carries at most one site: the canonical base stands on one
+ *   strand; should a motif be given that matches both strands at a position, the position is ONE element, mod before nomod before nocall).
+ * SEQUENCE: the called sites (mod, nomod) — nocall sites are transparent, they neither extend nor break a run; with nocall_breaks all
+ *   three states take part.  RUN: a maximal stretch of consecutive sequence elements of one state within one contig: state, n_sites,
+ *   start / last = the positions of its first / last element's modified base.
+ * nm_motif_runs_count: rows = (candidate, contig of its bin) from row_offset as in nm_motif_sites_count; contig_rows =
+ *   int64[rows][3 (mod, nomod, nocall)][3 + R], R = max_run (2..64): [s][0] runs of state s, [s][1] sites of state s on the contig (both
+ *   strands; counted also when nocall does not take part), [s][2] the longest run, [s][3 + j] runs of exactly j + 1 sites (j < R - 1),
+ *   [s][3 + R - 1] runs of R or more.  Without nocall_breaks the nocall row holds [2][1] only.  The caller's table need not be zeroed.
+ * nm_motif_runs_sites: a record per run whose state is in state_set (NM_SITES_MOD | NOMOD | NOCALL) and whose n_sites >= min_run, in the
+ *   order candidate, contig (nm_bin_contigs order), ascending start: site_pos = start, site_code = state (0 / 1 / 2), site_last = last,
+ *   site_n = n_sites.  cand_offset and the window [first_record, first_record + capacity) as in nm_motif_sites; capacity 0 returns the
+ *   offsets alone.
+ * How: a segmented scan inside the wave per (candidate, chunk) work item, whose first and last run go into a per-item summary, and one
+ *   thread per (candidate, contig) that stitches the summaries in chunk order (csrc/nmruns.hip).  Launches: at most 3 + 1 (count), + 2 + 3 (records).
+ * Refusals, each before any device is touched, in this order: NULLs; max_run outside 2..64 / min_run 0, state_set empty or above 7,
+ *   NM_SITES_NOCALL in state_set without nocall_breaks (NM_EINVAL); ctx NULL; no assembly (NM_ESTATE); row_offset[0] != 0; then per
+ *   candidate as in nm_motif_sites_count (bin, slot, program, rows, work items).  n_cand = 0 is NM_OK.  A refusal leaves the ctx usable. */
+#define NM_RUNS_MIN_MAX_RUN 2
+#define NM_RUNS_MAX_MAX_RUN 64
+int nm_motif_runs_count(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot, const uint8_t *cand_len,
+                        const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t max_run,
+                        int nocall_breaks, const uint64_t *row_offset /* [n_cand + 1] */, int64_t *contig_rows);
+int nm_motif_runs_sites(nm_ctx *ctx, uint32_t n_cand, const uint32_t *cand_bin, const uint8_t *cand_mod_slot, const uint8_t *cand_len,
+                        const uint8_t *cand_modpos, const uint32_t *cand_mask_offset, const uint8_t *cand_masks, uint32_t state_set,
+                        uint32_t min_run, int nocall_breaks, uint64_t first_record, uint64_t capacity, uint32_t *site_contig,
+                        uint32_t *site_pos, uint8_t *site_code, uint32_t *site_last, uint32_t *site_n, uint64_t *cand_offset,
+                        uint64_t *n_written);
+
 /* ---- MOTIF OVERLAP: the sites a motif shares with other motifs of its bin, and the sites it has alone ------------------------------
  * Reference: none on sites (remove_sub_motifs / merge_motifs of postprocess.py settle nesting by the motifs' spelling).  What decides
  * whether a parent motif or its child is the real one is the methylation of the parent OUTSIDE the child: a set difference on the

@@ -36,6 +36,7 @@ SYMBOLS = [
     "nm_motif_shift_count", "nm_motif_shift_sites",
     "nm_regions_create", "nm_regions_destroy", "nm_regions_shape", "nm_regions_covered", "nm_regions_plane", "nm_regions_chunk_classes",
     "nm_motif_regions_count", "nm_motif_regions_sites",
+    "nm_motif_runs_count", "nm_motif_runs_sites",
 ]
 
 class SearchParams(C.Structure):
@@ -192,6 +193,9 @@ def _load_locked():
     lib.nm_motif_regions_count.argtypes = [p, p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint32, C.c_int, u64p, u64p, i64p]
     lib.nm_motif_regions_sites.argtypes = [p, p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, u32p, u32p,
                                            u8p, u8p, u64p, u64p]
+    lib.nm_motif_runs_count.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_int, u64p, i64p]
+    lib.nm_motif_runs_sites.argtypes = [p, C.c_uint32, u32p, u8p, u8p, u8p, u32p, u8p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, u32p, u32p, u8p,
+                                        u32p, u32p, u64p, u64p]
     lib.nm_motif_sites_text.argtypes = [C.c_uint64, u32p, u32p, u8p, C.c_uint32, u64p, C.c_char_p, u64p, C.c_uint32, C.c_char_p, u64p, p,
                                         C.c_uint64, u64p]
     lib.nm_readstats_upload.argtypes = [p, C.c_uint32, C.c_uint64, p, p, p, p, p, p, C.c_int32, C.c_double, C.c_int, u64p]

@@ -1,6 +1,6 @@
 """Command line of the MI355X build: the ``motif_discovery`` sub-command with the reference's arguments
 (nanomotif/argparser.py:13-136), plus ``--device`` for the GPU to use, the project's own ``motif_sites`` / ``motif_coverage`` /
-``motif_compare`` / ``motif_strands`` / ``motif_profile`` / ``motif_tracks`` / ``motif_fractions`` / ``motif_pileup`` / ``motif_shift`` / ``motif_context`` / ``motif_gc`` / ``motif_overlap`` / ``motif_regions`` on a finished ``bin-motifs.tsv``, ``motif_kmers`` (which needs none), and the binnary sub-commands ``detect_contamination`` and
+``motif_compare`` / ``motif_strands`` / ``motif_profile`` / ``motif_tracks`` / ``motif_fractions`` / ``motif_pileup`` / ``motif_shift`` / ``motif_context`` / ``motif_gc`` / ``motif_overlap`` / ``motif_regions`` / ``motif_runs`` on a finished ``bin-motifs.tsv``, ``motif_kmers`` (which needs none), and the binnary sub-commands ``detect_contamination`` and
 ``include_contigs`` with the reference's flags (argparser.py:139-236).  MTase-linker is out of scope."""
 import argparse
 
@@ -13,7 +13,7 @@ def create_parser():
                                      formatter_class=formatter)
     parser.add_argument("--version", action="version", version="%(prog)s {}".format(__version__))
     sub = parser.add_subparsers(help="-- Command descriptions --", dest="command", title="commands",
-                                metavar="{motif_discovery, motif_sites, motif_coverage, motif_compare, motif_strands, motif_profile, motif_tracks, motif_fractions, motif_pileup, motif_shift, motif_context, motif_gc, motif_overlap, motif_regions, motif_kmers, detect_contamination, include_contigs, check_installation}")
+                                metavar="{motif_discovery, motif_sites, motif_coverage, motif_compare, motif_strands, motif_profile, motif_tracks, motif_fractions, motif_pileup, motif_shift, motif_context, motif_gc, motif_overlap, motif_regions, motif_runs, motif_kmers, detect_contamination, include_contigs, check_installation}")
     p = sub.add_parser("motif_discovery", help="Finds motifs directly on bin level in provided assembly", add_help=False)
     p.add_argument("assembly", type=str, help="path to the assembly file.")
     p.add_argument("pileup", type=str, help="path to the modkit pileup file.")
@@ -63,6 +63,7 @@ def create_parser():
     add_motif_gc_parser(sub)
     add_motif_overlap_parser(sub)
     add_motif_regions_parser(sub)
+    add_motif_runs_parser(sub)
     add_motif_kmers_parser(sub)
     add_binnary_parsers(sub)
     sub.add_parser("check_installation", help="Run motif_discovery on a small synthetic data set", add_help=True)
@@ -316,6 +317,27 @@ def add_motif_regions_parser(sub):
     o.add_argument("--inside", type=_checked("motif_regions", "parse_inside"), default=None,
                    help="Comma-separated classes (and / or outside) whose sites go to region-sites.bed. Default: every class")
     o.add_argument("--intervals", action="store_true", help="Also write motif-regions-intervals.tsv: the six counts per interval and motif")
+    _close_export(p, o)
+
+
+def add_motif_runs_parser(sub):
+    """motif_runs: runs of consecutive same-state sites of the motifs of bin-motifs.tsv files along the contigs — footprints of
+    unmethylated sites, alternating states of a strand-biased caller — with the Wald-Wolfowitz runs test beside the bin's background (no
+    counterpart on the reference's command line; people export motif-sites.bed and group consecutive rows by hand)."""
+    p, o = _open_export(sub, "motif_runs", "Reports runs of consecutive same-state motif sites of bin-motifs.tsv files along the contigs",
+                        "Path(s) to the bin-motifs.tsv whose motif sites are read (motif_discovery's output)")
+    o.add_argument("--max_run", type=_checked("motif_runs", "parse_max_run"), default=16,
+                   help="Run lengths counted apart, 2..64: the last bucket of motif-runs-hist.tsv holds the runs of MAX_RUN sites or more. Default: %(default)s")
+    o.add_argument("--nocall_breaks", action="store_true",
+                   help="A site without a call takes part and ends a run. Default: such a site is transparent, it neither extends nor breaks a run")
+    o.add_argument("--min_called", type=int, default=20, help="Called sites a motif needs to be judged. Default: %(default)s")
+    o.add_argument("--min_z", type=float, default=5.0,
+                   help="|runs_z_within| from which a motif is flagged clustered (negative) or alternating (positive). Default: %(default)s")
+    o.add_argument("--runs", action="store_true", help="Also write motif-runs.bed: one line per run of --states with at least --min_run sites")
+    o.add_argument("--states", type=_checked("motif_runs", "parse_run_states"), default=("nomod",),
+                   help="Comma-separated states of the runs of motif-runs.bed: mod, nomod, and with --nocall_breaks nocall. Default: nomod")
+    o.add_argument("--min_run", type=_checked("motif_runs", "parse_min_run"), default=3,
+                   help="Sites a run needs to be written to motif-runs.bed, at least 1. Default: %(default)s")
     _close_export(p, o)
 
 

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 SRC_HIP = [os.path.join(_CSRC, f) for f in ("nmscan.hip", "nmscore_classes.hip", "nmingest.hip", "nmwindows.hip", "nmmeth.hip", "nmbedgpu.hip", "nmfasta.hip", "nmsites.hip",
                                                   "nmcoverage.hip", "nmcompare.hip", "nmstrands.hip", "nmprofile.hip", "nmtracks.hip", "nmfractions.hip", "nmpileup.hip",
-                                                  "nmcontext.hip", "nmkmers.hip", "nmgc.hip", "nmoverlap.hip", "nmshift.hip", "nmregions.hip")]
+                                                  "nmcontext.hip", "nmkmers.hip", "nmgc.hip", "nmoverlap.hip", "nmshift.hip", "nmregions.hip", "nmruns.hip")]
 SRC_HOST = [os.path.join(_CSRC, f) for f in ("nmbed.cpp", "nmhost.cpp", "nmcomm.cpp", "nmsearch.cpp", "nmpost.cpp", "nmpool.cpp", "nmsitestext.cpp")]
 OUT = os.path.join(_HERE, "libnmscan.so")
 # synthetic-data tooling of bench.py and the tests (a bedMethyl text writer, a bgzip + tabix writer): its own small library,

@@ -1,4 +1,4 @@
-// The scaffold the thirteen export units share; included by them and by nothing else.  Each hands out one wave per work item = (owner,
+// The scaffold the fourteen export units share; included by them and by nothing else.  Each hands out one wave per work item = (owner,
 // chunk of the owner's bin) — an owner is a candidate, in nmcoverage.hip a set of candidates — and runs up to three steps:
 //   count  the unit's kernel writes the number of records of every work item into the item table (and its own count tables)
 //   scan   one device-wide exclusive prefix (rocPRIM) over the work items, which are numbered in (owner, contig rank, chunk)
@@ -11,6 +11,9 @@
 //                              nmpileup.hip, nmshift.hip and nmregions.hip, whose records carry two / four gathered columns / one class byte more,
 //                              with a window half and a fill loop of their own
 //   the count step only (tables): nmprofile.hip, nmtracks.hip, nmfractions.hip, nmcontext.hip, nmgc.hip, nmoverlap.hip — export_begin alone
+//   the fourteenth, nmruns.hip: export_begin without the scan, then a stitch of its own over the work items of every (candidate, contig)
+//                              BEFORE the prefix — a run crosses work items, so an item's record count is final only after it —, the
+//                              prefix + gather enqueued by the unit, and a window half with two columns more
 // Two more pieces belong to every unit and are owned by none:
 //   stage_candidates  the host loop over a call's candidates: programs, widths, the work-item count and, on request, the state-plane
 //                     addresses of a per-candidate mod slot and the row prefix of a (candidate, contig) table.  Its refusals come in ONE

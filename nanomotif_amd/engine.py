@@ -71,7 +71,11 @@ REGIONS_BUDGET_BYTES = 256 << 20               # default size of the table of on
 REGION_RECORD_BYTES = 10                       # a record on the device: contig (4), position (4), code (1), classes (1)
 REGION_DTYPE = np.dtype(SITE_DTYPE.descr + [("classes", np.uint8)])
 REGION_OUTSIDE = "outside"                     # the cell behind the classes, and its name in a selection
-OVERLAP_MAX_PARTNERS = 4095                    # NM_OVERLAP_MAX_PARTNERS: partner motifs of one candidate of ScanEngine.motif_overlap
+RUNS_MIN_MAX_RUN, RUNS_MAX_MAX_RUN = 2, 64     # NM_RUNS_MIN_MAX_RUN / NM_RUNS_MAX_MAX_RUN: the run-length buckets R of ScanEngine.motif_run_counts
+RUNS_BUDGET_BYTES = 256 << 20                  # default size of the table of one library call of ScanEngine.motif_run_counts
+RUN_RECORD_BYTES = 17                          # a record on the device: contig (4), start (4), state (1), last (4), n_sites (4)
+RUN_DTYPE = np.dtype(SITE_DTYPE.descr + [("last", np.uint32), ("n_sites", np.uint32)])
+OVERLAP_MAX_PARTNERS = 4095                   # NM_OVERLAP_MAX_PARTNERS: partner motifs of one candidate of ScanEngine.motif_overlap
 OVERLAP_ROW_BYTES = 48                         # one (block, contig) row of nm_motif_overlap_count: 2 strands x 3 states, int64
 OVERLAP_BUDGET_BYTES = 256 << 20               # default size of the table of one library call of ScanEngine.motif_overlap
 KMER_MAX_FLANKS = 10                           # NM_KMER_MAX_FLANKS: counted positions of a k-mer shape ...
@@ -142,6 +146,23 @@ def site_state_set(states) -> int:
     if bad or not states:
         raise ValueError(f"states must be a non-empty selection of {SITE_STATES}, got {states!r}")
     return sum(1 << SITE_STATES.index(s) for s in set(states))
+
+
+def run_state_set(states, nocall_breaks=False) -> int:
+    """("nomod",) -> the state_set bits of nm_motif_runs_sites: ``site_state_set``, and ValueError for "nocall" without
+    ``nocall_breaks`` — a nocall site is transparent then, runs of them do not exist."""
+    bits = site_state_set(states)
+    if bits & 4 and not nocall_breaks:
+        raise ValueError(f"states {tuple(states)!r}: runs of nocall sites exist with nocall_breaks only")
+    return bits
+
+
+def run_length_limit(max_run) -> int:
+    """The R of ``ScanEngine.motif_run_counts``: an integer in 2..64, else ValueError."""
+    r = int(max_run)
+    if r != max_run or not RUNS_MIN_MAX_RUN <= r <= RUNS_MAX_MAX_RUN:
+        raise ValueError(f"max_run {max_run!r} outside {RUNS_MIN_MAX_RUN}..{RUNS_MAX_MAX_RUN}")
+    return r
 
 
 def region_class_set(names, selection) -> tuple:
@@ -1658,6 +1679,58 @@ class ScanEngine:
         windows = self._record_windows(self.lib.nm_motif_regions_sites, group_args, totals[:len(b)], limit, REGION_DTYPE, "candidate", "batch",
                                        values=(("classes", np.uint8),))
         yield from self._site_batches(windows, b, names, rows, table[:int(rows[-1])])
+
+    # ------------------------------------------------------------------ runs of same-state sites along contigs (nm_motif_runs_*)
+    def motif_run_counts(self, candidates, max_run=16, nocall_breaks=False, max_bytes=None):
+        """The RUNS of the sites of ``candidates`` (sequence of (Motif, mod_type, bin), or a CandidateBatch with slots from
+        ``slot_of_mod``) counted per contig (nm_motif_runs_count).  A site is an occurrence of ``motif_site_counts`` with its state; on a
+        contig the sites of both strands are taken by ascending position, the called ones form the sequence (nocall sites are
+        transparent; with ``nocall_breaks`` they take part and end a run like any change of state), and a run is a maximal stretch of
+        consecutive sequence elements of one state.  Returns a list, per candidate, of (contig names in ``bin_contigs`` order,
+        int64[n_contigs, 3 (mod, nomod, nocall), 3 + R]), R = ``max_run`` (2..64): [s][0] runs, [s][1] sites (both strands; the nocall
+        sites also when they do not take part), [s][2] the longest run, [s][3 + j] runs of exactly j + 1 sites, the last cell runs of R
+        or more.  Consecutive candidates share one library call while their tables fit ``max_bytes`` (default ``RUNS_BUDGET_BYTES``);
+        what is returned does not depend on it."""
+        r = run_length_limit(max_run)
+        limit = _byte_limit(max_bytes, RUNS_BUDGET_BYTES)
+        b = self._as_batch(candidates)
+        names = self._bin_names(b)
+        nb = int(bool(nocall_breaks))
+
+        def call(k, e, sub, rows, table):
+            _lib.check(self.lib.nm_motif_runs_count(self.ctx, *self._batch_args(sub), r, nb, _ptr(rows, C.c_uint64), _ptr(table, C.c_int64)))
+        n_rows = [len(names[int(bid)]) for bid in b.bins]
+        return [(contigs, table) for _, contigs, table in _table_groups(b, names, n_rows, 3 * (3 + r) * 8, limit, (3, 3 + r), np.int64, call)]
+
+    def motif_runs(self, candidates, states=("nomod",), min_run=3, nocall_breaks=False, max_records=None):
+        """Generator over the runs of ``candidates`` (as ``motif_run_counts`` defines them) whose state is in ``states`` and that hold
+        at least ``min_run`` sites (nm_motif_runs_sites).  Yields ``SiteBatch`` objects in candidate order; their ``records``
+        (``RUN_DTYPE``: candidate, contig, pos = the position of the run's first site, code = state 0 mod / 1 nomod / 2 nocall, last =
+        the position of its last site, n_sites) concatenated are the runs in the order candidate, contig (``bin_contigs`` order),
+        ascending start; ``counts`` is None.  "nocall" in ``states`` needs ``nocall_breaks``.  No batch holds more than ``max_records``
+        records (default: ``SITE_BUDGET_BYTES`` of device records, 17 bytes each); the concatenation does not depend on it."""
+        b = self._as_batch(candidates)
+        state_set = run_state_set(states, nocall_breaks)
+        min_run = int(min_run)
+        if min_run < 1:
+            raise ValueError(f"min_run {min_run}: at least 1")
+        nb = int(bool(nocall_breaks))
+        limit = self._record_limit(max_records, RUN_RECORD_BYTES)
+        return self._run_windows(b, state_set, min_run, nb, limit)
+
+    def _run_windows(self, b: CandidateBatch, state_set: int, min_run: int, nb: int, limit: int):
+        # the candidates' totals: the offsets of one call that asks for no record
+        off = np.zeros(len(b) + 1, dtype=np.uint64)
+        written = C.c_uint64(0)
+        _lib.check(self.lib.nm_motif_runs_sites(self.ctx, *self._batch_args(b), state_set, min_run, nb, 0, 0, None, None, None, None, None, _ptr(off, C.c_uint64),
+                                                C.byref(written)))
+        totals = np.diff(off)
+
+        def group_args(k, e):
+            return (self.ctx, *self._batch_args(b.slice(k, e)), state_set, min_run, nb)
+        for k, e, first, held, rec in self._record_windows(self.lib.nm_motif_runs_sites, group_args, totals, limit, RUN_DTYPE, "candidate", "batch",
+                                                           values=("last", "n_sites")):
+            yield SiteBatch(first_candidate=k, n_candidates=e - k, first_record=first, batch_records=held, records=rec, counts=None)
 
     # ------------------------------------------------------------------ shared sites of a motif and its partners (nm_motif_overlap_count)
     def motif_overlap(self, candidates, partners, max_bytes=None):

@@ -594,7 +594,7 @@ def main(argv=None):
         if result is None and rank == 0:
             with open(os.path.join(args.out, "bin-motifs.tsv"), "w") as f:     # main.py:317-321
                 f.write(HEADER)
-    elif args.command in ("motif_sites", "motif_coverage", "motif_compare", "motif_strands", "motif_profile", "motif_tracks", "motif_fractions", "motif_pileup", "motif_shift", "motif_context", "motif_gc", "motif_overlap", "motif_regions", "motif_kmers"):
+    elif args.command in ("motif_sites", "motif_coverage", "motif_compare", "motif_strands", "motif_profile", "motif_tracks", "motif_fractions", "motif_pileup", "motif_shift", "motif_context", "motif_gc", "motif_overlap", "motif_regions", "motif_runs", "motif_kmers"):
         import importlib
         if int(os.environ.get("WORLD_SIZE", "1") or 1) > 1:
             sys.stderr.write(f"nanomotif {args.command} runs on one GPU: start it without a multi-rank launcher\n")
